@@ -8,6 +8,23 @@ per-GPU batch fixed (weak scaling) unless --global-batch splits a fixed total
 RCCL/xGMI; no collective on the data path.  Rank 0 prints one JSON line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G] [--params 128]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing more: keys and
+inputs, W warm-up steps, the K timed steps, the result line.  --full adds what
+the line reported beside it before: the decryption check of the warm-up
+outputs, the margin guard's recompute count, an untimed profiled pass (HIP
+events around every launch) with the roofline objects built from it and from the
+committed records under profiles/, and the CPU baseline (--no-cpu-baseline is
+--full without that one; TFHE_BENCH_FULL=1 in the environment is --full, for a
+script whose every call wants the full line).  --full governs this default (nand)
+path only: the other workloads and --single-process are chosen by their own
+options and run their checks and host-buffer timings on every run, as before.
+Every line names the kernels it launched in `kernels`.  --dump-outputs DIR
+writes the ciphertext words the last timed step left in the output buffer as
+DIR/gate_out.npy (float64, exact for 32-bit torus words; DIR/<workload>_out.npy
+for another workload); keys and inputs are seeded, so two builds run with the
+same arguments can be compared word for word.
 
 --gpus N > 1 without RANK in the environment: this process starts
 `torch.distributed.run --nproc-per-node N` on itself (a child process; this
@@ -331,6 +348,25 @@ def rocprof_record():
     return rec, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much over all files and ranks
+
+
+def dump_outputs(dirpath, arrays, rank=0, world=1):
+    """--dump-outputs DIR: every array of `arrays` as DIR/<name>.npy (DIR/<name>_rank<r>.npy
+    with several ranks) in float64, which holds a 32-bit torus word exactly.  An output too
+    large for its share of DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its rows, in
+    their order."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (world * len(arrays)) - 4096  # the .npy header
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+        rows = max(1, share // (a.shape[1] * 8))
+        if a.shape[0] > rows:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(dirpath, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a.astype(np.float64))
+
+
 def timed(fn, steps, warmup, world, device):
     for _ in range(warmup):
         fn()
@@ -525,6 +561,8 @@ def run_workload(args, rank, world, device):
                                   "note": "tfhe_gpu_bootstrap_lut_batch: PCIe copies in the timed region"}}
         workload = (f"{total} UINT4 LUT bootstraps over {world} GPU(s) (f(x) = x^2+3 mod 16; n=820, L=1, "
                     f"Bg=2^22, t=3, basebit 5; device-resident, tfhe_gpu_bootstrap_lut_batch_dev)")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {args.workload + "_out": outs}, rank, world)
     ok_all = torch.tensor([0.0 if extra.get("decrypt_check", extra.get("sums_check", True)) else 1.0],
                           dtype=torch.float64, device=device)
     if world > 1:
@@ -602,6 +640,8 @@ def run_single_process(args):
         out = run(ctx)
     el = time.perf_counter() - t0
     per_dev = ((ctx.device_bootstraps() - boots0) // max(1, args.steps)).tolist()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {("gate" if args.workload == "nand" else args.workload) + "_out": out})
     ok = check(out)
     if args.workload == "mixed":
         extra["level_issue_us"] = ctx.get_option("level_issue_us")  # the level split's host issue time
@@ -642,7 +682,9 @@ def spawn_ranks(args) -> int:
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  --no-cpu-baseline, and TFHE_BENCH_FULL=1 in the environment (how a
+    measurement script asks for the full line in every call it makes), both mean --full."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)  # 0.3 s of GPU time at 6.2 ms per step
@@ -651,10 +693,15 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="gates per step over all GPUs, split ceil(G/N) per GPU (strong scaling)")
     ap.add_argument("--params", default="128")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="the default (nand) workload: also the decryption check, the margin guard's count, the profiled pass with the "
+                         "roofline objects and the CPU baseline (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: length of the CPU baseline")
     ap.add_argument("--prof-steps", type=int, default=50,
-                    help="steps of the untimed profiled pass (HIP events per launch) after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: steps of the untimed profiled pass (HIP events per launch) after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline (implies --full)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--single-process", action="store_true",
                     help="one process drives --gpus devices through the library's multi-device context")
@@ -666,8 +713,15 @@ def main():
                     help="tfhe_gpu_set_option before the run (A/B of kernel forms), e.g. br_loader=0, arith=1")
     ap.add_argument("--workload", default="nand", choices=["nand", "adder", "mixed", "lut", "reenc"],
                     help="nand = the headline metric (default); others: BASELINE configs 3-5")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    args.full = args.full or args.no_cpu_baseline or os.environ.get("TFHE_BENCH_FULL") == "1"
+    return args
 
+
+def main():
+    args = parse_args()
     if args.single_process:
         return run_single_process(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -691,7 +745,7 @@ def main():
     ctx = tfhe_amd.Context(args.params, device.index)
     apply_opts(ctx, args)
     p = ctx.params
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     bk = ksk = None
     if rank == 0:
         sk, (bk, ksk) = ctx.keygen(42, 43, want_host_copy=want_cpu)
@@ -724,14 +778,16 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(device)
-    out = t_o.cpu().numpy().view(np.uint32).copy()
-    correct = bool(np.array_equal(sk.decrypt_bool(out), ~(a_bits.astype(bool) & b_bits.astype(bool))))
+    correct = True
+    if args.full:
+        out = t_o.cpu().numpy().view(np.uint32).copy()
+        correct = bool(np.array_equal(sk.decrypt_bool(out), ~(a_bits.astype(bool) & b_bits.astype(bool))))
 
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(device)
     ctx.sync()
-    ties0 = ctx.near_tie_items()
+    ties0 = ctx.near_tie_items() if args.full else 0
     # the timed region: K steps and nothing else (no per-launch events: they cost 0.5-0.9 ms
     # per step at 2,048-4,096 gates, profiles/r04k_batch_sizes.txt)
     t0 = time.perf_counter()
@@ -742,14 +798,17 @@ def main():
     if world > 1:
         dist.barrier()
     ctx.sync()  # the device error word of the timed launches, and the guard's counter
-    recomputed = ctx.near_tie_items() - ties0
-    # kernel averages from a separate, untimed pass of the same steps with HIP events
-    # recorded around every blind-rotation and key-switch launch on the launch stream
-    prof_steps = max(1, min(args.steps, args.prof_steps))
-    ctx.profile_begin()
-    for _ in range(prof_steps):
-        step()
-    br_ms, ks_ms, launches = ctx.profile_end()
+    if args.dump_outputs:  # the output buffer as the last timed step left it
+        dump_outputs(args.dump_outputs, {"gate_out": t_o.cpu().numpy().view(np.uint32)}, rank, world)
+    if args.full:
+        recomputed = ctx.near_tie_items() - ties0
+        # kernel averages from a separate, untimed pass of the same steps with HIP events
+        # recorded around every blind-rotation and key-switch launch on the launch stream
+        prof_steps = max(1, min(args.steps, args.prof_steps))
+        ctx.profile_begin()
+        for _ in range(prof_steps):
+            step()
+        br_ms, ks_ms, launches = ctx.profile_end()
 
     stats = torch.tensor([elapsed, 0.0 if correct else 1.0], dtype=torch.float64, device=device)
     if world > 1:
@@ -759,10 +818,7 @@ def main():
 
     if rank == 0:
         value = total * args.steps / elapsed
-        br_avg_s = br_ms / 1e3 / max(1, launches)
-        ks_avg_s = ks_ms / 1e3 / max(1, launches)
         kernels = ctx.last_kernels()
-        roof, hbm = rooflines(p, B, args.params, br_avg_s, kernels.split(" + ")[0])
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "gate-bootstraps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -771,22 +827,29 @@ def main():
             "config": {"workload": f"{B} NAND gate bootstraps per GPU per step, SECURITY_128_BIT "
                                    f"(n={p.n}, N={p.N}, L={p.L}, Bg=2^{p.bgbit}, t={p.iks_t})",
                        "global_batch": total, "params": args.params, "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "key_bytes_consumed": hbm,
-            "key_switch": {"kernel": " + ".join(kernels.split(" + ")[1:]), "avg_ms": round(ks_avg_s * 1e3, 3)},
-            "kernel_timing": {"profiled_steps": prof_steps, "launches": launches,
-                              "note": "kernel averages (roofline.kernel_avg_ms, key_switch.avg_ms) come from an "
-                                      "untimed pass of profiled_steps steps after the timed region, HIP events "
-                                      "around each launch on its stream; the timed steps carry no events"},
-            "margin_guard": {"recomputed_items": recomputed, "items": B * args.steps,
-                             "note": ("fused arithmetic; items that round a value 1/4 or more off its integer are "
-                                      "redone in the reference's expression trees inside the timed launches "
-                                      "(DESIGN.md §6.1)") if "fused" in kernels else
-                                     "reference expression trees throughout (no guard, no admission assumption)"},
+            "kernels": kernels,
             "kernel_build_id": kernel_build_id(),
             "kernel_source_sha256": kernel_source_hash(),
-            "decrypt_check": all_correct,
         }
+        if args.full:
+            br_avg_s = br_ms / 1e3 / max(1, launches)
+            ks_avg_s = ks_ms / 1e3 / max(1, launches)
+            roof, hbm = rooflines(p, B, args.params, br_avg_s, kernels.split(" + ")[0])
+            line.update({
+                "roofline": roof,
+                "key_bytes_consumed": hbm,
+                "key_switch": {"kernel": " + ".join(kernels.split(" + ")[1:]), "avg_ms": round(ks_avg_s * 1e3, 3)},
+                "kernel_timing": {"profiled_steps": prof_steps, "launches": launches,
+                                  "note": "kernel averages (roofline.kernel_avg_ms, key_switch.avg_ms) come from an "
+                                          "untimed pass of profiled_steps steps after the timed region, HIP events "
+                                          "around each launch on its stream; the timed steps carry no events"},
+                "margin_guard": {"recomputed_items": recomputed, "items": B * args.steps,
+                                 "note": ("fused arithmetic; items that round a value 1/4 or more off its integer are "
+                                          "redone in the reference's expression trees inside the timed launches "
+                                          "(DESIGN.md §6.1)") if "fused" in kernels else
+                                         "reference expression trees throughout (no guard, no admission assumption)"},
+                "decrypt_check": all_correct,
+            })
         if want_cpu:
             line["cpu_baseline"] = cpu_baseline(p, sk, bk, ksk, A, Bc, out, args.cpu_seconds)
         print(json.dumps(line), flush=True)

@@ -35,6 +35,47 @@ def test_rank_split(world):
     assert all(p[1:] == (65541, "strong") for p in parts)
 
 
+def test_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files that hold every 32-bit word exactly; an output above its share
+    of the size limit keeps the same seeded row sample, in order, on every run."""
+    import numpy as np
+    words = np.random.default_rng(5).integers(0, 1 << 32, (37, 11), dtype=np.uint64).astype(np.uint32)
+    words[0, :2] = 0, 0xFFFFFFFF
+    bench.dump_outputs(str(tmp_path / "a"), {"gate_out": words})
+    got = np.load(tmp_path / "a" / "gate_out.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), words)
+    # a limit that 2 ranks x 1 array x 37 rows of 88 bytes (+ header) overrun: 10 rows each
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (4096 + 10 * 88 + 40))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"gate_out": words}, rank=1, world=2)
+    b, c = (np.load(tmp_path / d / "gate_out_rank1.npy") for d in ("b", "c"))
+    assert b.shape == (10, 11) and np.array_equal(b, c)
+    rows = [int(np.flatnonzero((words == r.astype(np.uint32)).all(axis=1))[0]) for r in b]
+    assert rows == sorted(set(rows))
+    assert os.path.getsize(tmp_path / "b" / "gate_out_rank1.npy") <= bench.DUMP_LIMIT_BYTES // 2
+
+
+def test_full_is_opt_in_and_what_implies_it(monkeypatch):
+    """A plain command line is the lean run; --full, --no-cpu-baseline (what the tools/ scripts
+    pass) and TFHE_BENCH_FULL=1 (what tools/gpu_run.sh exports) each ask for the full line, and
+    --steps sets the timed steps, at least one."""
+    monkeypatch.delenv("TFHE_BENCH_FULL", raising=False)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.full, plain.steps, plain.warmup, plain.dump_outputs, plain.workload) == (False, 7, 2, "", "nand")
+    assert bench.parse_args(["--full"]).full and not bench.parse_args(["--full"]).no_cpu_baseline
+    assert bench.parse_args(["--steps", "10", "--no-cpu-baseline"]).full
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d" and not bench.parse_args(["--dump-outputs", "d"]).full
+    monkeypatch.setenv("TFHE_BENCH_FULL", "0")
+    assert not bench.parse_args([]).full
+    monkeypatch.setenv("TFHE_BENCH_FULL", "1")
+    assert bench.parse_args([]).full and not bench.parse_args([]).no_cpu_baseline
+    for bad in ("0", "-3"):
+        with pytest.raises(SystemExit):
+            bench.parse_args(["--steps", bad])
+    # the measurement script asks for the full line once, for all its calls
+    assert "export TFHE_BENCH_FULL=1" in open(os.path.join(ROOT, "tools", "gpu_run.sh")).read()
+
+
 def test_roofline_from_committed_records(monkeypatch):
     """roofline.frac_rocprof and roofline.valu_issue from profiles/ reproduce by hand
     from the committed csv and PMC file, for the build id those records carry."""

@@ -15,6 +15,10 @@
 #   adder     config 3 (one 16-bit adder) only     hp      single-process one-device host path
 # Everything lands under gpurun_out/<TAG>*; copy what is judged into profiles/.
 set -o pipefail
+# every bench.py call of this script prints the full line (= bench.py --full: decrypt check,
+# kernel averages and rooflines from the records just measured, CPU baseline unless the call
+# says --no-cpu-baseline); bench.py reads this from the environment
+export TFHE_BENCH_FULL=1
 R=$GRAFT_REPO_ROOT
 TAG=${1:?tag}
 STEPS=${2:-tests,smoke,prof,bench}
