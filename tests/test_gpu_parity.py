@@ -889,3 +889,103 @@ def test_worst_admitted_key_under_the_product_guard(oracle):
         print(f"worst admitted key: {c.near_tie_items()} item(s) recomputed by the guard")
     finally:
         c.close()
+
+
+# ---- kernel names and dispatch, pinned to a record --------------------------
+def _last_kernels_matrix(pname):
+    """(entry point, options, B) of test_last_kernels_match_parent_record for one
+    parameter set.  B = 5 leaves idle item slots in every form, 65 crosses the key
+    switch's B > 64 branches and starts a second item group, 1,027 (128-bit, default
+    options) is one whole-form round plus a 3-item tail on a 256-CU device."""
+    for B in (5, 65):
+        for form in ("auto", "whole", "wide") + (("octo",) if pname == "uint4" else ()):
+            for arith in (0, 1):
+                yield "blind_rotate", {"br_form": form, "arith": arith}, B
+        for ks_form in (3, 2, 0, 1):
+            yield "bootstrap", {"ks_form": ks_form}, B
+        if pname == "uint4":  # the lane form's item groups (basebit 5)
+            for groups in (0, 1, 2, 4, 8):
+                yield "bootstrap", {"ks_form": 0, "ks_item_groups": groups}, B
+        else:  # wide / narrow lane blocks (basebit 2)
+            for narrow in (0, 1):
+                yield "bootstrap", {"ks_form": 0, "ks_narrow": narrow}, B
+    if pname == "128":
+        yield "blind_rotate", {}, 1027  # not pipelined: launch_blind_rotate's own plan
+        yield "bootstrap", {}, 1027     # host-buffer pipeline: whole form per chunk
+        for narrow in (0, 1):  # 1,024 items spread better over 44-word x 8-wave lane blocks
+            yield "key_switch", {"ks_form": 0, "ks_narrow": narrow}, 1024
+
+
+def _record_key(pname, entry, opts, B):
+    return "|".join([pname, entry, ",".join(f"{k}={v}" for k, v in sorted(opts.items())), f"B={B}"])
+
+
+_LAST_KERNELS_REF = {}
+
+
+def _observed_last_kernels(oracle, pname):
+    """last_kernels() after every call of the matrix, by record key; the B = 5 outputs
+    are checked against the oracle on the way, the 1,027-item ones against the small
+    batches' words (every form computes the same words)."""
+    c, k = ctx_for(oracle, pname)
+    p = k.p
+    if pname not in _LAST_KERNELS_REF:
+        cts = u32rand(rng(41), 1027 if pname == "128" else 65, p.n + 1)
+        _LAST_KERNELS_REF[pname] = (
+            cts,
+            {"blind_rotate": np.array([oracle.blind_rotate(p, t, k.ck.testvec, k.ck.bk, k.ck.offset) for t in cts[:5]]),
+             "bootstrap": np.array([oracle.bootstrap(p, t, k.ck) for t in cts[:5]])})
+    cts, want5 = _LAST_KERNELS_REF[pname]
+    call = {"blind_rotate": c.blind_rotate_batch, "bootstrap": c.bootstrap_batch}
+    seen = {}
+    for entry, opts, B in _last_kernels_matrix(pname):
+        with c.options(**opts):
+            if entry == "key_switch":  # names only (the words: test_key_switch_vs_oracle), after the call before's blind rotation
+                c.key_switch(u32rand(rng(42), B, 1025))
+            else:
+                got = call[entry](cts[:B])
+            seen[_record_key(pname, entry, opts, B)] = c.last_kernels()
+        if B == 5:
+            assert np.array_equal(got, want5[entry]), (entry, opts)
+        if B == 1027:
+            assert np.array_equal(got[:5], want5[entry]), entry
+            assert np.array_equal(got[1024:], call[entry](cts[1024:])), entry
+    if pname != "128":
+        return seen
+    # re-encryption on a fresh context (no blind rotation named before it): a key with
+    # the GEMM layout (the set's own base and levels) and one without (basebit 4, t 4)
+    a0, b0 = oracle.secret_key(p, 21)[0], oracle.secret_key(p, 22)[0]
+    ctx = tfhe_amd.Context(pname, 0)
+    try:
+        for basebit, t in ((p.basebit, p.iks_t), (4, 4)):
+            key = oracle.reenc_key_gen(p.n, a0, p.alpha_ksk, basebit, t, 99, key_to=b0)
+            hr = tfhe_amd.HipReencryptor(ctx, tfhe_amd.ProxyReencryptionKey(key, basebit, t))
+            want = np.array([oracle.reencrypt(p.n, basebit, t, x, key) for x in cts[:5]])
+            for ks_form in (3, 0):
+                for B in (5, 65):
+                    with ctx.options(ks_form=ks_form):
+                        got = hr.reencrypt(cts[:B])
+                        seen[_record_key(pname, f"reencrypt(basebit {basebit}, t {t})", {"ks_form": ks_form}, B)] = \
+                            ctx.last_kernels()
+                    assert np.array_equal(got[:5], want), (basebit, t, ks_form, B)
+            hr.close()
+    finally:
+        ctx.close()
+    return seen
+
+
+@pytest.mark.parametrize("pname", ["80", "128", "uint4"])
+def test_last_kernels_match_parent_record(oracle, pname):
+    """Which kernel runs, and the name last_kernels() reports for it, for every form
+    option, key-switch shape and batch-size branch of the launchers, equal to
+    tests/golden/last_kernels.json byte for byte.  The record was taken from the
+    library as it was before the launchers became table-driven (hand-written
+    dispatch chains, names typed next to each launch), with this matrix: bench.py
+    and the profile records match these strings, so a launcher change keeps them."""
+    import json
+    with open(os.path.join(GOLDEN, "last_kernels.json")) as f:
+        record = {key: v for key, v in json.load(f).items() if key.startswith(pname + "|")}
+    seen = _observed_last_kernels(oracle, pname)
+    assert sorted(seen) == sorted(record)
+    for key in sorted(seen):
+        assert seen[key] == record[key], key

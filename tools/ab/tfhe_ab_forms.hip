@@ -3,9 +3,10 @@
 // (VERDICT r04 item 3).  tools/ab_forms.sh links this unit into an A/B library
 // (tools/bin/lib_ab.so, compiled with TFHE_AB_BUILD: tfhe_gpu_create refuses
 // it unless TFHE_ALLOW_AB_BUILD=1), where TFHE_OPT_BR_FORM 6 (duo), 7
-// (split-transform latency form) and 8 (round 4's whole form at L = 3, whose
+// (split-transform latency form), 8 (round 4's whole form at L = 3, whose
 // loader waves only issue DMAs: the reference point of the round-5 loader
-// assist) reach these kernels through the product launcher's weak hook
+// assist) and 30 (the product unit's latency form with row counters) reach
+// these kernels through the product launcher's weak hook
 // ab_launch_blind_rotate.  Measurements: DESIGN.md §4.2 (wide2: 109.4-109.8 vs
 // 99.9 ms per 16-bit adder), §4.3d (duo: 7.93-8.05 vs 6.12-6.18 ms per 1,024
 // gates), §4.1b (assist).  The development switches below (TFHE_KO_*,
@@ -885,70 +886,32 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_wide2(
     }
 }
 
-hipError_t ab_launch_wide_rc(const KParams &P, const DevTables &T, const uint8_t *ops, const uint32_t *in_a,
-                             const uint32_t *in_b, const uint32_t *idx, const uint32_t *testvec, const double2 *bk2,
-                             uint32_t *out, int out_mode, size_t B, hipStream_t s, const char **used);  // tfhe_kernels.hip
-hipError_t ab_launch_assist_dev(int var, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
-                                const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                const uint32_t *testvec, const double2 *bk2, uint32_t *out, int out_mode, size_t B,
-                                const char **used);  // tfhe_ab_assist_dev.hip
+hipError_t ab_launch_wide_rc(const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s,
+                             const char **used);  // tfhe_kernels.hip
 
-// TFHE_OPT_BR_FORM 6 / 7 / 8 (and 9 + VAR: tfhe_ab_assist_dev.hip) from the product launcher
-// (launch_blind_rotate_form).
-hipError_t ab_launch_blind_rotate(int br_form, const KParams &P, const DevTables &T, const uint8_t *ops,
-                                  const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                  const uint32_t *testvec, const double2 *bk2, uint32_t *out, int out_mode, size_t B,
-                                  hipStream_t s, bool fused, const char **used) {
+// TFHE_OPT_BR_FORM 6 / 7 / 8 / 30 from the product launcher (launch_br_form).
+hipError_t ab_launch_blind_rotate(int br_form, const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s,
+                                  bool fused, const char **used) {
     const bool small = std::ldexp(2.0 * P.L * 1024.0, P.bgbit - 1 + 31) < std::ldexp(1.0, 49);
+    BrEntry k{nullptr, ""};
+    BrGeometry g = br_geometry('w', b.B);
     if (br_form == 30) {  // the latency form with row counters (tfhe_kernels.hip, RC = 1)
         if (!(P.L == 3 && small && fused)) return hipErrorInvalidValue;
-        return ab_launch_wide_rc(P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B, s, used);
+        return ab_launch_wide_rc(P, T, b, s, used);
     }
     if (br_form == 6) {  // duo: two computing waves per item
-        const dim3 grid((unsigned)((B + BD_GATES - 1) / BD_GATES)), block(64 * BD_WAVES);
-        if (P.L == 3 && small && fused) {
-            hipLaunchKernelGGL((k_blind_rotate_duo<3, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_duo<3,true,true> (duo form, fused)";
-        } else if (P.L == 1 && small && fused) {
-            hipLaunchKernelGGL((k_blind_rotate_duo<1, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_duo<1,true,true> (duo form, fused)";
-        } else if (P.L == 1 && !small) {
-            hipLaunchKernelGGL((k_blind_rotate_duo<1, false, false>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_duo<1,false,false> (duo form)";
-        } else {
-            return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        g = {dim3((unsigned)((b.B + BD_GATES - 1) / BD_GATES)), dim3(64 * BD_WAVES)};
+        if (P.L == 3 && small && fused) k = {k_blind_rotate_duo<3, true, true>, "k_blind_rotate_duo<3,true,true> (duo form, fused)"};
+        else if (P.L == 1 && small && fused) k = {k_blind_rotate_duo<1, true, true>, "k_blind_rotate_duo<1,true,true> (duo form, fused)"};
+        else if (P.L == 1 && !small) k = {k_blind_rotate_duo<1, false, false>, "k_blind_rotate_duo<1,false,false> (duo form)"};
+    } else if (br_form == 8 && P.L == 3 && small && fused) {  // round 4's whole form at L = 3 (loader waves issue DMAs only)
+        k = {k_blind_rotate<3, true, true>, "k_blind_rotate<3,true,true> (whole form without loader assist, fused)"};
+    } else if (br_form == 7 && P.L == 3 && small) {  // latency form with split transforms
+        g = br_geometry('W', b.B);
+        if (fused) k = {k_blind_rotate_wide2<3, true, true>, "k_blind_rotate_wide2<3,true,true> (latency form, split transforms, fused)"};
+        else k = {k_blind_rotate_wide2<3, true, false>, "k_blind_rotate_wide2<3,true,false> (latency form, split transforms)"};
     }
-    if (br_form == 8 && P.L == 3 && small && fused) {  // round 4's whole form at L = 3 (loader waves issue DMAs only)
-        const dim3 grid((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), block(64 * BR_WAVES * 2);
-        hipLaunchKernelGGL((k_blind_rotate<3, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx, testvec, bk2,
-                           out, out_mode, B);
-        if (used) *used = "k_blind_rotate<3,true,true> (whole form without loader assist, fused)";
-        return hipGetLastError();
-    }
-    if (br_form >= 9 && P.L == 3 && small && fused) {  // development copies of the assist form
-        const dim3 grid((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), block(64 * BR_WAVES * 2);
-        return ab_launch_assist_dev(br_form - 9, grid, block, s, P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode,
-                                    B, used);
-    }
-    if (br_form == 7 && P.L == 3 && small) {  // latency form with split transforms
-        const dim3 grid((unsigned)B), block(64 * BW_WAVES);
-        if (fused) {
-            hipLaunchKernelGGL((k_blind_rotate_wide2<3, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_wide2<3,true,true> (latency form, split transforms, fused)";
-        } else {
-            hipLaunchKernelGGL((k_blind_rotate_wide2<3, true, false>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_wide2<3,true,false> (latency form, split transforms)";
-        }
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
+    return launch_br(k, g, P, T, b, s, used);
 }
 
 }  // namespace tfhe

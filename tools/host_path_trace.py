@@ -51,9 +51,10 @@ def report(d):
     rows.sort(key=lambda x: x[1])
     api.sort(key=lambda x: x[1])
     # the last 8 blind-rotation launches and what lies around them
-    br = [r for r in rows if "k_blind_rotate<3, true, true, true, true>" in r[0] or "k_blind_rotate<3,true,true,true,true>" in r[0]]
+    # (the default whole form at L = 3; else any form but the margin guard's recompute, k_blind_rotate<L, true, false>)
+    br = [r for r in rows if "k_blind_rotate_assist<true>" in r[0]]
     if not br:
-        br = [r for r in rows if "k_blind_rotate" in r[0] and "false, true>" not in r[0]]
+        br = [r for r in rows if "k_blind_rotate" in r[0] and "true, false>" not in r[0] and "true,false>" not in r[0]]
     for k in br[-3:]:
         lo, hi = k[1] - 600_000, k[2] + 400_000
         print("---- call around blind rotation at", k[1])

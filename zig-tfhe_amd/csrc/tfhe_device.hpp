@@ -18,7 +18,7 @@
 //    multiply-adds (fmad below, __builtin_fma) in the reference's operation
 //    order, with a margin guard on every rounding: an item that rounds a fused
 //    value 1/4 or more off its integer is recomputed in the reference trees
-//    (torus_from_f64_guarded, launch_br_recompute), so both give the
+//    (torus_from_f64_guarded, the recompute of launch_blind_rotate), so both give the
 //    reference's integers.
 // The key switch (k_key_switch_gemm, the default form) is integer-exact: a
 // one-hot int8 GEMM on the matrix cores.
@@ -512,7 +512,7 @@ DEV uint32_t torus_from_f64(double v) {
 }
 
 // Same result in 8 VALU ops when |v| < 2^51 is guaranteed by the parameter
-// set (|ExtProd| <= 2L * N * Bg/2 * 2^31; 2^47.6 at L=3, Bg=2^6): trunc,
+// set (|ExtProd| <= 2L * N * Bg/2 * 2^31; 2^48.6 at L=3, Bg=2^6): trunc,
 // then t + 1.5*2^52 is exact and its low mantissa word is t mod 2^32.
 DEV uint32_t torus_from_f64_small(double v) {
     const double t = trunc(v);

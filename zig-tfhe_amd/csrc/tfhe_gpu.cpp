@@ -187,8 +187,9 @@ bool params_ok(const tfhe_params *p, std::string &why) {
     if (p->n == 0 || p->n > 1024) { why = "n must be in [1, 1024]"; return false; }
     if (p->L < 1 || p->L > 3) { why = "L must be 1, 2 or 3"; return false; }
     if (p->bgbit < 1 || p->bgbit * p->L > 32) { why = "bgbit*L must be <= 32"; return false; }
-    // key-switch kernels are instantiated for basebit 2 with t in [7, 9]
-    // (128/80-bit) and basebit 3..8 with t in [2, 4] (Uint sets)
+    // the select form takes basebit 2 with t in [7, 9] (128/80-bit), the gather form
+    // basebit 3..8 with t in [2, 4] (Uint sets); the shapes with faster forms are
+    // listed once, in KS_SHAPES (tfhe_kernels.hip)
     const bool ks_sel = p->basebit == 2 && p->iks_t >= 7 && p->iks_t <= 9;
     const bool ks_gather = p->basebit >= 3 && p->basebit <= 8 && p->iks_t >= 2 && p->iks_t <= 4;
     if (!(ks_sel || ks_gather) || p->basebit * p->iks_t >= 31) {
@@ -260,15 +261,13 @@ enum RunKind : int {
     RUN_NO_KEYSWITCH = 2,  // sampleExtractIndex2, n+1 words (vanilla.zig:58-69)
 };
 
-// The gemm key switch's buffers for a batch of B (TFHE_OPT_KS_FORM = 2, or 3 from
-// KS_GEMM_MIN_ITEMS items): the
-// MFMA-layout KSK, rebuilt on the stream after a key change, and the partial
-// sums.  G stays empty for the other forms (launch_key_switch ignores it).
+// The gemm key switch's buffers for a batch of B where it is the form to run
+// (ks_use_gemm): the MFMA-layout KSK, rebuilt on the stream after a key change,
+// and the partial sums.  G stays empty for the other forms (launch_key_switch
+// ignores it).
 int ks_gemm_args(tfhe_gpu_ctx *c, size_t B, KsGemm &G) {
     G = KsGemm();
-    const bool want = c->opts.ks_form == 2 ||
-                      (c->opts.ks_form == 3 && B >= KS_GEMM_MIN_ITEMS && ks_gemm_auto(c->K.iks_t, c->K.basebit));
-    if (!want || !ks_gemm_supported(c->K)) return TFHE_OK;
+    if (!ks_use_gemm(c->opts, c->K.iks_t, c->K.basebit, B, nullptr)) return TFHE_OK;
     if (!c->d_ksk_gemm) {
         hipError_t e = hipMalloc((void **)&c->d_ksk_gemm, ks_gemm_bytes(c->K, 1024, c->K.iks_t, c->K.basebit));
         if (e != hipSuccess) return fail(c, TFHE_ERR_OOM, "hipMalloc(ksk gemm layout)");
@@ -284,6 +283,16 @@ int ks_gemm_args(tfhe_gpu_ctx *c, size_t B, KsGemm &G) {
     return TFHE_OK;
 }
 
+// Near-tie flags (KParams::tie_flags) for B items.  The flags are all zero between
+// launches, so only a new buffer is zeroed (on the context stream).
+int ensure_tie_flags(tfhe_gpu_ctx *c, size_t B) {
+    if (c->s_ties.bytes >= B) return TFHE_OK;
+    int rc = ensure(c, c->s_ties, B);
+    if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(c->s_ties.p, 0, c->s_ties.bytes, c->stream));
+    return TFHE_OK;
+}
+
 // Blind rotation (+ key switch for RUN_BOOTSTRAP) over device buffers, async.
 int run_bootstrap_dev(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, const uint32_t *b,
                       const uint32_t *testvec_dev, uint32_t *out, size_t B, int kind,
@@ -293,12 +302,8 @@ int run_bootstrap_dev(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, co
     if (!c->has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
     if (B == 0) return TFHE_OK;
     int rc = ensure(c, c->s_lv1, B * 1025 * sizeof(uint32_t));
+    if (!rc) rc = ensure_tie_flags(c, B);
     if (rc) return rc;
-    if (c->s_ties.bytes < B) {  // the flags are all zero between launches: a new buffer starts zeroed
-        rc = ensure(c, c->s_ties, B);
-        if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(c->s_ties.p, 0, c->s_ties.bytes, c->stream));
-    }
     KParams K = c->K;
     K.tie_flags = (uint8_t *)c->s_ties.p;
     uint32_t *lv1 = key_switch ? (uint32_t *)c->s_lv1.p : out;
@@ -313,8 +318,8 @@ int run_bootstrap_dev(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, co
         c->ev_used += 3;
         HIPCHK(c, hipEventRecord(ev[0], c->stream));
     }
-    HIPCHK(c, launch_blind_rotate(K, tables(c), ops, a, b, idx, testvec_dev ? testvec_dev : c->d_testvec, c->d_bk,
-                                  lv1, out_mode, B, c->stream, c->opts, &c->last_br));
+    const BrBatch batch{ops, a, b, idx, testvec_dev ? testvec_dev : c->d_testvec, c->d_bk, lv1, out_mode, B};
+    HIPCHK(c, launch_blind_rotate(K, tables(c), batch, c->stream, c->opts, &c->last_br));
     c->bootstraps += B;
     if (ev[1]) HIPCHK(c, hipEventRecord(ev[1], c->stream));
     c->last_ks = "";
@@ -1049,12 +1054,8 @@ int pipelined_bootstrap(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, 
     if (!rc && b) rc = ensure(c, c->s_b, B * wb);
     if (!rc) rc = ensure(c, c->s_out, B * wb);
     if (!rc) rc = ensure(c, c->s_lv1, B * 1025 * sizeof(uint32_t));
+    if (!rc) rc = ensure_tie_flags(c, B);
     if (rc) return rc;
-    if (c->s_ties.bytes < B) {
-        rc = ensure(c, c->s_ties, B);
-        if (rc) return rc;
-        HIPCHK(c, hipMemsetAsync(c->s_ties.p, 0, c->s_ties.bytes, c->stream));
-    }
     if (!c->pipe_ev) HIPCHK(c, hipEventCreateWithFlags(&c->pipe_ev, hipEventDisableTiming));
     for (hipStream_t &p : c->pipe)
         if (!p) HIPCHK(c, hipStreamCreateWithFlags(&p, hipStreamNonBlocking));
@@ -1105,9 +1106,9 @@ int pipelined_bootstrap(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, 
                 return;
             KParams K = c->K;
             K.tie_flags = (uint8_t *)c->s_ties.p + k0;
-            if (!chk(launch_blind_rotate(K, tables(c), ops ? d_ops + k0 : nullptr, d_a + k0 * w, b ? d_b + k0 * w : nullptr,
-                                         nullptr, tv_dev ? tv_dev : c->d_testvec, c->d_bk, d_lv1 + k0 * 1025, BR_OUT_LV1,
-                                         n, st, o, s == 0 && k == 0 ? &c->last_br : nullptr),
+            const BrBatch batch{ops ? d_ops + k0 : nullptr, d_a + k0 * w, b ? d_b + k0 * w : nullptr, nullptr,
+                                tv_dev ? tv_dev : c->d_testvec, c->d_bk, d_lv1 + k0 * 1025, BR_OUT_LV1, n};
+            if (!chk(launch_blind_rotate(K, tables(c), batch, st, o, s == 0 && k == 0 ? &c->last_br : nullptr),
                      "blind rotation") ||
                 !chk(launch_key_switch(c->K, d_lv1 + k0 * 1025, c->d_ksk, d_out + k0 * w, n, st, c->opts,
                                        s == 0 && k == 0 ? &c->last_ks : nullptr, &Gs[s]),
@@ -1141,87 +1142,49 @@ bool use_pipeline(const tfhe_gpu_ctx *c, size_t B) {
 
 extern "C" {
 
-static int bootstrap_batch_one(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t *out, size_t B) {
-    if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
-    if (use_pipeline(c, B)) return pipelined_bootstrap(c, nullptr, in, nullptr, nullptr, out, B);
-    const size_t w = tlwe0_words(c);
-    int rc = h2d(c, c->s_a, in, B * w * 4);
-    if (!rc) rc = ensure(c, c->s_out, B * w * 4);
-    if (!rc) rc = run_bootstrap_dev(c, nullptr, (const uint32_t *)c->s_a.p, nullptr, nullptr, (uint32_t *)c->s_out.p, B, RUN_BOOTSTRAP);
-    if (!rc) rc = d2h_sync(c, out, c->s_out.p, B * w * 4);
-    return rc;
+// One host-buffer batch through the blind rotation: what the bootstrap, gate,
+// blind-rotate and LUT entry points differ in.
+struct HostBatch {
+    const uint8_t *ops;       // NULL unless gate
+    const uint32_t *a, *b;    // b NULL unless gate
+    const uint32_t *testvec;  // host test vector, or NULL: the key's
+    uint32_t *out;
+    int kind;                 // RunKind
+    bool gate;                // a gate batch: ops and b are arguments too
+    bool needs_key;           // refuse a context without a cloud key before any upload
+    bool may_pipeline;        // large batches may take pipelined_bootstrap
+};
+static bool host_batch_args_ok(const HostBatch &d, size_t B) {
+    return B == 0 || (d.a && d.out && (!d.gate || (d.ops && d.b)));
+}
+static size_t host_batch_out_words(const tfhe_gpu_ctx *c, const HostBatch &d) {
+    return d.kind == RUN_TRLWE ? 2 * (size_t)c->P.N : tlwe0_words(c);
 }
 
-static int bootstrap_without_key_switch_batch_one(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t *out, size_t B) {
-    if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+static int host_batch_one(tfhe_gpu_ctx *c, const HostBatch &d, size_t B) {
+    if (!c || !host_batch_args_ok(d, B)) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
+    if (d.gate)
+        for (size_t i = 0; i < B; i++)
+            if (d.ops[i] > TFHE_GATE_ORYN && d.ops[i] != TFHE_GATE_COPY) return fail(c, TFHE_ERR_INVALID, "bad gate op");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t w = tlwe0_words(c);
-    int rc = h2d(c, c->s_a, in, B * w * 4);
-    if (!rc) rc = ensure(c, c->s_out, B * w * 4);
-    if (!rc) rc = run_bootstrap_dev(c, nullptr, (const uint32_t *)c->s_a.p, nullptr, nullptr, (uint32_t *)c->s_out.p, B, RUN_NO_KEYSWITCH);
-    if (!rc) rc = d2h_sync(c, out, c->s_out.p, B * w * 4);
-    return rc;
-}
-
-static int gate_batch_one(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, const uint32_t *b, uint32_t *out,
-                        size_t B) {
-    if (!c || (B && (!ops || !a || !b || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    for (size_t i = 0; i < B; i++)
-        if (ops[i] > TFHE_GATE_ORYN && ops[i] != TFHE_GATE_COPY) return fail(c, TFHE_ERR_INVALID, "bad gate op");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
-    if (use_pipeline(c, B)) return pipelined_bootstrap(c, ops, a, b, nullptr, out, B);
-    const size_t w = tlwe0_words(c);
-    int rc = h2d(c, c->s_ops, ops, B);
-    if (!rc) rc = h2d(c, c->s_a, a, B * w * 4);
-    if (!rc) rc = h2d(c, c->s_b, b, B * w * 4);
-    if (!rc) rc = ensure(c, c->s_out, B * w * 4);
-    if (!rc)
-        rc = run_bootstrap_dev(c, (const uint8_t *)c->s_ops.p, (const uint32_t *)c->s_a.p, (const uint32_t *)c->s_b.p,
-                               nullptr, (uint32_t *)c->s_out.p, B, RUN_BOOTSTRAP);
-    if (!rc) rc = d2h_sync(c, out, c->s_out.p, B * w * 4);
-    return rc;
-}
-
-static int blind_rotate_batch_one(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvec, uint32_t *trlwe_out,
-                                size_t B) {
-    if (!c || (B && (!in || !trlwe_out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t w = tlwe0_words(c);
-    int rc = h2d(c, c->s_a, in, B * w * 4);
+    if (d.needs_key && !c->has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t in_bytes = B * tlwe0_words(c) * 4, out_bytes = B * host_batch_out_words(c, d) * 4;
     const uint32_t *tv = nullptr;
-    if (!rc && testvec) {
-        rc = h2d(c, c->s_tv, testvec, 2 * c->P.N * 4);
+    int rc = TFHE_OK;
+    if (d.testvec) {
+        if ((rc = h2d(c, c->s_tv, d.testvec, 2 * c->P.N * 4))) return rc;
         tv = (const uint32_t *)c->s_tv.p;
     }
-    if (!rc) rc = ensure(c, c->s_out, B * 2 * c->P.N * 4);
-    if (!rc) rc = run_bootstrap_dev(c, nullptr, (const uint32_t *)c->s_a.p, nullptr, tv, (uint32_t *)c->s_out.p, B, RUN_TRLWE);
-    if (!rc) rc = d2h_sync(c, trlwe_out, c->s_out.p, B * 2 * c->P.N * 4);
-    return rc;
-}
-
-static int bootstrap_lut_batch_one(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvec, uint32_t *out,
-                                 size_t B) {
-    if (!c || !testvec || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
-    const size_t w = tlwe0_words(c);
-    int rc = h2d(c, c->s_tv, testvec, 2 * c->P.N * 4);
-    if (rc) return rc;
-    if (use_pipeline(c, B)) return pipelined_bootstrap(c, nullptr, in, nullptr, (const uint32_t *)c->s_tv.p, out, B);
-    rc = h2d(c, c->s_a, in, B * w * 4);
-    if (!rc) rc = ensure(c, c->s_out, B * w * 4);
+    if (d.may_pipeline && use_pipeline(c, B)) return pipelined_bootstrap(c, d.ops, d.a, d.b, tv, d.out, B);
+    if (d.gate) rc = h2d(c, c->s_ops, d.ops, B);
+    if (!rc) rc = h2d(c, c->s_a, d.a, in_bytes);
+    if (!rc && d.gate) rc = h2d(c, c->s_b, d.b, in_bytes);
+    if (!rc) rc = ensure(c, c->s_out, out_bytes);
     if (!rc)
-        rc = run_bootstrap_dev(c, nullptr, (const uint32_t *)c->s_a.p, nullptr, (const uint32_t *)c->s_tv.p,
-                               (uint32_t *)c->s_out.p, B, RUN_BOOTSTRAP);
-    if (!rc) rc = d2h_sync(c, out, c->s_out.p, B * w * 4);
+        rc = run_bootstrap_dev(c, d.gate ? (const uint8_t *)c->s_ops.p : nullptr, (const uint32_t *)c->s_a.p,
+                               d.gate ? (const uint32_t *)c->s_b.p : nullptr, tv, (uint32_t *)c->s_out.p, B, d.kind);
+    if (!rc) rc = d2h_sync(c, d.out, c->s_out.p, out_bytes);
     return rc;
 }
 
@@ -1859,8 +1822,10 @@ bool option_ok(const tfhe_gpu_ctx *c, int key, int64_t v, std::string &why) {
     switch (key) {
     case TFHE_OPT_BR_FORM:
         // 2 split, 4 pair: removed in round 4; 6 duo, 7 split-transform latency
-        // form, 8 the whole form without loader assist: A/B libraries only (tools/ab/); 5 octo: L = 1 only
-        ok = v == 0 || v == 1 || v == 3 || (v == 5 && c->P.L == 1) || (v >= 6 && v <= 40 && ab_forms_linked());
+        // form, 8 the whole form without loader assist, 30 the latency form with row
+        // counters: A/B libraries only (tools/ab/); 5 octo: L = 1 only
+        ok = v == 0 || v == 1 || v == 3 || (v == 5 && c->P.L == 1) ||
+             ((v == 6 || v == 7 || v == 8 || v == 30) && ab_forms_linked());
         if (!ok && v == 5) why = "TFHE_OPT_BR_FORM 5 (octo form) exists at L = 1 only";
         if (!ok && v >= 6 && v <= 8) why = "TFHE_OPT_BR_FORM " + std::to_string(v) + ": an A/B-only form, not in the product library (tools/ab/)";
         break;
@@ -2137,6 +2102,12 @@ int run_sharded(tfhe_gpu_ctx *c, size_t B, F f) {
     for (size_t d = 1; d < D; d++)
         if (rc[d]) return fail(c, rc[d], "device " + std::to_string(c->shards[d]->device) + ": " + c->shards[d]->err);
     return rc[0];
+}
+
+// A shard's part of a per-item host array of `words` words per item (NULL stays NULL).
+template <class T>
+T *shard_items(T *p, size_t first, size_t words) {
+    return p ? p + first * words : nullptr;
 }
 
 struct Dsu {
@@ -2501,52 +2472,53 @@ int tfhe_gpu_device_bootstraps(const tfhe_gpu_ctx *c, uint64_t *counts, int max_
     return D;
 }
 
-int tfhe_gpu_bootstrap_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t *out, size_t B) {
-    if (!is_multi(c)) return bootstrap_batch_one(c, in, out, B);
-    if (B && (!in || !out)) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const size_t w = tlwe0_words(c);
+// host_batch_one on the context's one device, or on every shard's slice of the batch.
+static int host_batch(tfhe_gpu_ctx *c, const HostBatch &d, size_t B) {
+    if (!is_multi(c)) return host_batch_one(c, d, B);
+    if (!host_batch_args_ok(d, B)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    const size_t w = tlwe0_words(c), wo = host_batch_out_words(c, d);
     return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return bootstrap_batch_one(s, in + b0 * w, out + b0 * w, n);
+        HostBatch p = d;
+        p.ops = shard_items(d.ops, b0, 1);
+        p.a = shard_items(d.a, b0, w);
+        p.b = shard_items(d.b, b0, w);
+        p.out = shard_items(d.out, b0, wo);
+        return host_batch_one(s, p, n);
     });
 }
 
+int tfhe_gpu_bootstrap_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t *out, size_t B) {
+    const HostBatch d{nullptr, in, nullptr, nullptr, out, RUN_BOOTSTRAP, /*gate*/ false,
+                      /*needs_key*/ true, /*may_pipeline*/ true};
+    return host_batch(c, d, B);
+}
+
 int tfhe_gpu_bootstrap_without_key_switch_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t *out, size_t B) {
-    if (!is_multi(c)) return bootstrap_without_key_switch_batch_one(c, in, out, B);
-    if (B && (!in || !out)) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const size_t w = tlwe0_words(c);
-    return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return bootstrap_without_key_switch_batch_one(s, in + b0 * w, out + b0 * w, n);
-    });
+    const HostBatch d{nullptr, in, nullptr, nullptr, out, RUN_NO_KEYSWITCH, /*gate*/ false,
+                      /*needs_key*/ false, /*may_pipeline*/ false};
+    return host_batch(c, d, B);
 }
 
 int tfhe_gpu_gate_batch(tfhe_gpu_ctx *c, const uint8_t *ops, const uint32_t *a, const uint32_t *b, uint32_t *out,
                         size_t B) {
-    if (!is_multi(c)) return gate_batch_one(c, ops, a, b, out, B);
-    if (B && (!ops || !a || !b || !out)) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const size_t w = tlwe0_words(c);
-    return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return gate_batch_one(s, ops + b0, a + b0 * w, b + b0 * w, out + b0 * w, n);
-    });
+    const HostBatch d{ops, a, b, nullptr, out, RUN_BOOTSTRAP, /*gate*/ true,
+                      /*needs_key*/ true, /*may_pipeline*/ true};
+    return host_batch(c, d, B);
 }
 
 int tfhe_gpu_blind_rotate_batch(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvec, uint32_t *trlwe_out,
                                 size_t B) {
-    if (!is_multi(c)) return blind_rotate_batch_one(c, in, testvec, trlwe_out, B);
-    if (B && (!in || !trlwe_out)) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const size_t w = tlwe0_words(c), wo = 2 * (size_t)c->P.N;
-    return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return blind_rotate_batch_one(s, in + b0 * w, testvec, trlwe_out + b0 * wo, n);
-    });
+    const HostBatch d{nullptr, in, nullptr, testvec, trlwe_out, RUN_TRLWE, /*gate*/ false,
+                      /*needs_key*/ false, /*may_pipeline*/ false};
+    return host_batch(c, d, B);
 }
 
 int tfhe_gpu_bootstrap_lut_batch(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvec, uint32_t *out,
                                  size_t B) {
-    if (!is_multi(c)) return bootstrap_lut_batch_one(c, in, testvec, out, B);
-    if (!testvec || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const size_t w = tlwe0_words(c);
-    return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return bootstrap_lut_batch_one(s, in + b0 * w, testvec, out + b0 * w, n);
-    });
+    if (!testvec) return fail(c, TFHE_ERR_INVALID, "null argument");
+    const HostBatch d{nullptr, in, nullptr, testvec, out, RUN_BOOTSTRAP, /*gate*/ false,
+                      /*needs_key*/ true, /*may_pipeline*/ true};
+    return host_batch(c, d, B);
 }
 
 int tfhe_gpu_key_switch_batch(tfhe_gpu_ctx *c, const uint32_t *in_lv1, uint32_t *out_lv0, size_t B) {
@@ -2554,7 +2526,7 @@ int tfhe_gpu_key_switch_batch(tfhe_gpu_ctx *c, const uint32_t *in_lv1, uint32_t 
     if (B && (!in_lv1 || !out_lv0)) return fail(c, TFHE_ERR_INVALID, "null argument");
     const size_t w = tlwe0_words(c), wi = (size_t)c->P.N + 1;
     return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
-        return key_switch_batch_one(s, in_lv1 + b0 * wi, out_lv0 + b0 * w, n);
+        return key_switch_batch_one(s, shard_items(in_lv1, b0, wi), shard_items(out_lv0, b0, w), n);
     });
 }
 
@@ -2584,7 +2556,7 @@ int tfhe_gpu_reencrypt_batch(tfhe_gpu_ctx *c, const tfhe_gpu_reenc_key *k, const
     return run_sharded(c, B, [&](tfhe_gpu_ctx *s, size_t b0, size_t n) {
         size_t d = 0;
         while (c->shards[d] != s) d++;
-        return reencrypt_batch_one(s, d ? k->peers[d - 1] : k, in + b0 * w, out + b0 * w, n);
+        return reencrypt_batch_one(s, d ? k->peers[d - 1] : k, shard_items(in, b0, w), shard_items(out, b0, w), n);
     });
 }
 

@@ -77,7 +77,8 @@ struct DevTables {
 // for A/B runs and parity tests.  `used` (may be NULL) receives the name of
 // the kernel a launcher ran.
 struct LaunchOpts {
-    int br_form = 0;     // 0 auto, 1 whole, 3 latency (wide), 5 octo (L = 1); 6 duo, 7 wide2 (A/B libraries only)
+    int br_form = 0;     // 0 auto, 1 whole, 3 latency (wide), 5 octo (L = 1); 6 duo, 7 wide2, 8 whole without
+                         // loader assist, 30 latency with row counters (A/B libraries only)
     int ks_form = 3;     // 0 lanes, 1 select / gather, 2 one-hot GEMM on the matrix cores (basebit 2), 3 auto
     int ks_narrow = 0;   // basebit 2: 1 forces the 32-word x 4-wave blocks
     int ks_groups = 0;   // basebit >= 5: item groups per block (0 auto = 4; 1, 2, 4, 8)
@@ -101,22 +102,46 @@ inline bool fused_allowed(const LaunchOpts &O) {
 #define TFHE_AB_BUILD 1
 #endif
 bool kernels_ab_build();  // tfhe_kernels.hip: this unit was compiled as an A/B build
-// The A/B-only blind-rotation forms (TFHE_OPT_BR_FORM 6, 7) are linked in
+// The A/B-only blind-rotation forms (TFHE_OPT_BR_FORM 6, 7, 8, 30) are linked in
 // (tools/ab/tfhe_ab_forms.hip), i.e. this is an A/B library.
 bool ab_forms_linked();
 
 // ---- launchers (tfhe_kernels.hip); all asynchronous on `s` --------------
-// idx: NULL, or B pairs (a, b) of ciphertext indices into in_a / in_b (circuit gather)
-// The default whole-form kernels (k_blind_rotate<L, true, true, true, true>), built in their
-// own unit with the max-memory-clause scheduler (tfhe_kernels_whole.hip).
-hipError_t launch_whole_default(int L, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
-                                const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                const uint32_t *testvec, const double2 *bk2, uint32_t *out, int out_mode, size_t B);
-hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const uint8_t *ops,
-                               const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                               const uint32_t *testvec, const double *bkd, uint32_t *out,
-                               int out_mode, size_t B, hipStream_t s, const LaunchOpts &O = LaunchOpts(),
-                               const char **used = nullptr);
+// One batch of blind rotations, as the launchers pass it on (device pointers).
+struct BrBatch {
+    const uint8_t *ops = nullptr;   // gate op per item, or NULL (plain bootstrap)
+    const uint32_t *in_a = nullptr;
+    const uint32_t *in_b = nullptr;  // second gate input, or NULL
+    const uint32_t *idx = nullptr;   // NULL, or B pairs (a, b) of ciphertext indices into in_a / in_b (circuit gather)
+    const uint32_t *testvec = nullptr;
+    const double *bk = nullptr;  // device-layout bootstrapping key (launch_bk_permute)
+    uint32_t *out = nullptr;
+    int out_mode = BR_OUT_LV1;
+    size_t B = 0;
+};
+// The signature every blind-rotation kernel shares, and a kernel with the name
+// last_kernels() reports for it.
+using BrKernel = void (*)(KParams, DevTables, const uint8_t *, const uint32_t *, const uint32_t *, const uint32_t *,
+                          const uint32_t *, const double2 *, uint32_t *, int, size_t);
+struct BrEntry {
+    BrKernel fn;
+    const char *name;
+};
+// The default whole-form kernels (fused arithmetic; L = 3: k_blind_rotate_assist), built in
+// their own unit with the max-memory-clause scheduler (tfhe_kernels_whole.hip).
+BrEntry whole_default_kernel(int L);
+// Grid and block of a form ('w' whole, 'W' latency, 'o' octo) over B items, and the one
+// launch of a blind-rotation kernel: hipErrorInvalidValue for an entry without a kernel.
+struct BrGeometry {
+    dim3 grid, block;
+};
+BrGeometry br_geometry(char form, size_t B);
+hipError_t launch_br(const BrEntry &k, const BrGeometry &g, const KParams &P, const DevTables &T, const BrBatch &b,
+                     hipStream_t s, const char **used);
+// The batch through the measured-fastest plan (or the form TFHE_OPT_BR_FORM forces), then the
+// margin guard's recompute where the fused arithmetic ran.
+hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s,
+                               const LaunchOpts &O = LaunchOpts(), const char **used = nullptr);
 // CUs of the current device (256 when it cannot be queried) and
 // launch_blind_rotate's modelled time for B items on `cus` CUs, in whole-form
 // rounds of 4 x cus items (the circuit scheduler's level packing)
@@ -133,13 +158,13 @@ struct KsGemm {
     uint32_t *part = nullptr;
 };
 // n_in: input coefficients (1024 for the identity key switch, n for a proxy
-// re-encryption key); t levels of basebit 2 (t 7..9) or 5 (t 2, 3)
+// re-encryption key); (t, basebit) a shape with the GEMM form (ks_gemm_supported)
 size_t ks_gemm_bytes(const KParams &P, int n_in, int t, int basebit);
 size_t ks_gemm_part_bytes(const KParams &P, size_t B, int n_in, int basebit);
-bool ks_gemm_supported(const KParams &P);
 bool ks_gemm_supported(int t, int basebit);
-bool ks_gemm_auto(int t, int basebit);
-extern size_t KS_GEMM_MIN_ITEMS;
+// This call takes the GEMM form: the shape has it, its buffers are there (G may be
+// NULL: the question before they are built) and TFHE_OPT_KS_FORM asks for it (2) or is auto (3).
+bool ks_use_gemm(const LaunchOpts &O, int t, int basebit, size_t B, const KsGemm *G);
 constexpr size_t KS_GEMM_INPUT_SLACK = 16;  // bytes past the last input row the gemm form may read
 hipError_t launch_ksk_to_gemm(const KParams &P, const uint32_t *ksk, uint32_t *kg, int n_in, int t, int basebit,
                               hipStream_t s);

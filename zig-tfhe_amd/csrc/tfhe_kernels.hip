@@ -16,7 +16,7 @@
 //    multiply-adds (fmad below, __builtin_fma) in the reference's operation
 //    order, with a margin guard on every rounding: an item that rounds a fused
 //    value 1/4 or more off its integer is recomputed in the reference trees
-//    (torus_from_f64_guarded, launch_br_recompute), so both give the
+//    (torus_from_f64_guarded, the recompute of launch_blind_rotate), so both give the
 //    reference's integers.
 // The key switch (k_key_switch_gemm, the default form) is integer-exact: a
 // one-hot int8 GEMM on the matrix cores.
@@ -37,6 +37,8 @@
 // kernels and every launcher; the device building blocks are in
 // tfhe_device.hpp, the default whole-form kernels in tfhe_kernels_whole.hip.
 #include <algorithm>
+#include <string>
+#include <type_traits>
 
 #include "tfhe_device.hpp"
 
@@ -1346,9 +1348,6 @@ hipError_t launch_tlwe_gather(const KParams &P, const uint32_t *src, const uint3
     return hipGetLastError();
 }
 
-// The pair form: fused (exact-integer regime) for any L, the reference's trees
-// only for L = 1 (where its regrouped sum is the reference's order).
-
 // |external product| <= 2L * N * Bg/2 * 2^31 below 2^49: the SMALL conversions
 // and the fused arithmetic's guarded conversion hold (the L=3 / Bg=2^6 sets:
 // 2^48.6; UINT4: 2^63, never)
@@ -1361,10 +1360,7 @@ static bool small_products(const KParams &P) {
 // tools/ab/tfhe_ab_forms.hip, which an A/B library links in (tools/ab_forms.sh)
 // and which then defines this hook.  In the product it stays unresolved (null).
 __attribute__((weak)) hipError_t ab_launch_blind_rotate(int br_form, const KParams &P, const DevTables &T,
-                                                        const uint8_t *ops, const uint32_t *in_a,
-                                                        const uint32_t *in_b, const uint32_t *idx,
-                                                        const uint32_t *testvec, const double2 *bk2, uint32_t *out,
-                                                        int out_mode, size_t B, hipStream_t s, bool fused,
+                                                        const BrBatch &b, hipStream_t s, bool fused,
                                                         const char **used);
 bool ab_forms_linked() { return ab_launch_blind_rotate != nullptr; }
 #ifdef TFHE_AB_BUILD
@@ -1373,106 +1369,75 @@ bool kernels_ab_build() { return true; }
 bool kernels_ab_build() { return false; }
 #endif
 
-// form: 'w' whole (default kernels: launch_whole_default), 'W' latency (one
-// item per 8-wave workgroup), 'o' octo (L = 1: 8 items per workgroup), 'a' the
-// A/B forms (TFHE_OPT_BR_FORM 6-8, A/B libraries only).
-static hipError_t launch_blind_rotate_form(const KParams &P, const DevTables &T, const uint8_t *ops,
-                                           const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                           const uint32_t *testvec, const double *bkd, uint32_t *out, int out_mode,
-                                           size_t B, hipStream_t s, char form, const LaunchOpts &O,
-                                           const char **used) {
-    if (B == 0) return hipSuccess;
-    const double2 *bk2 = reinterpret_cast<const double2 *>(bkd);
-    const bool small = small_products(P);
-    // fused arithmetic in the exact-integer regime (SMALL) unless the
-    // reference expression trees are requested (TFHE_OPT_ARITH)
-    const bool fused = small && fused_allowed(O);
-    if (form == 'a') {  // an A/B form (TFHE_OPT_BR_FORM >= 6)
-        if (!ab_launch_blind_rotate) return hipErrorInvalidValue;
-        return ab_launch_blind_rotate(O.br_form, P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B, s, fused,
-                                      used);
+// The product's blind-rotation kernels, each with the name last_kernels() reports
+// for it.  form: 'w' whole (4 items + 4 loader waves per 512-thread workgroup),
+// 'W' latency (one item per 8-wave workgroup), 'o' octo (L = 1: 8 items per
+// workgroup, two gate waves per SIMD).  fused: the fused
+// arithmetic of the exact-integer regime, so only with small; the fused whole
+// form is the default kernels' unit's (whole_default_kernel).  {nullptr, ""}:
+// no such instantiation.
+#define BR_ENTRY(K_, L_, S_, F_, WHAT_) BrEntry{K_<L_, S_, F_>, #K_ "<" #L_ "," #S_ "," #F_ "> (" WHAT_ ")"}
+#define BR_TREES(K_, L_, WHAT_) BR_ENTRY(K_, L_, false, false, WHAT_), BR_ENTRY(K_, L_, true, false, WHAT_)
+#define BR_ALL(K_, L_, WHAT_) BR_TREES(K_, L_, WHAT_), BR_ENTRY(K_, L_, true, true, WHAT_ ", fused")
+static BrEntry br_kernel(char form, int L, bool small, bool fused) {
+    static const BrEntry none{nullptr, ""};
+    static const BrEntry whole[3][2] = {{BR_TREES(k_blind_rotate, 1, "whole form")},
+                                        {BR_TREES(k_blind_rotate, 2, "whole form")},
+                                        {BR_TREES(k_blind_rotate, 3, "whole form")}};
+    static const BrEntry wide[3][3] = {{BR_ALL(k_blind_rotate_wide, 1, "latency form")},
+                                       {BR_ALL(k_blind_rotate_wide, 2, "latency form")},
+                                       {BR_ALL(k_blind_rotate_wide, 3, "latency form")}};
+    static const BrEntry octo[3] = {BR_ALL(k_blind_rotate_octo, 1, "octo form")};
+    if (L < 1 || L > 3 || (fused && !small)) return none;
+    const int arith = (small ? 1 : 0) + (fused ? 1 : 0);
+    switch (form) {
+    case 'w': return fused ? whole_default_kernel(L) : whole[L - 1][arith];
+    case 'W': return wide[L - 1][arith];
+    case 'o': return L == 1 ? octo[arith] : none;
+    default: return none;
     }
-    if (form == 'o') {  // octo form: 8 items per workgroup, two gate waves per SIMD; L = 1
-        if (P.L != 1) return hipErrorInvalidValue;
-        const dim3 grid((unsigned)((B + BO_GATES - 1) / BO_GATES)), block(64 * BO_GATES);
-        if (fused) {
-            hipLaunchKernelGGL((k_blind_rotate_octo<1, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_octo<1,true,true> (octo form, fused)";
-        } else if (small) {
-            hipLaunchKernelGGL((k_blind_rotate_octo<1, true, false>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_octo<1,true,false> (octo form)";
-        } else {
-            hipLaunchKernelGGL((k_blind_rotate_octo<1, false, false>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,
-                               testvec, bk2, out, out_mode, B);
-            if (used) *used = "k_blind_rotate_octo<1,false,false> (octo form)";
-        }
-        return hipGetLastError();
+}
+#undef BR_ALL
+#undef BR_TREES
+#undef BR_ENTRY
+
+BrGeometry br_geometry(char form, size_t B) {
+    switch (form) {
+    case 'o': return {dim3((unsigned)((B + BO_GATES - 1) / BO_GATES)), dim3(64 * BO_GATES)};
+    case 'W': return {dim3((unsigned)B), dim3(64 * BW_WAVES)};
+    default: return {dim3((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES * 2)};
     }
-    if (form == 'W') {  // latency form: one item per 8-wave workgroup
-        const dim3 grid((unsigned)B), block(64 * BW_WAVES);
-#define BW_LAUNCH(L_, S_)                                                                                         \
-    do {                                                                                                          \
-        if (fused) {                                                                                              \
-            hipLaunchKernelGGL((k_blind_rotate_wide<L_, S_, S_>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,  \
-                               testvec, bk2, out, out_mode, B);                                                   \
-            if (used) *used = "k_blind_rotate_wide<" #L_ "," #S_ ",true> (latency form, fused)";                  \
-        } else {                                                                                                  \
-            hipLaunchKernelGGL((k_blind_rotate_wide<L_, S_, false>), grid, block, 0, s, P, T, ops, in_a, in_b,    \
-                               idx, testvec, bk2, out, out_mode, B);                                              \
-            if (used) *used = "k_blind_rotate_wide<" #L_ "," #S_ ",false> (latency form)";                        \
-        }                                                                                                         \
-    } while (0)
-        switch (P.L) {
-        case 1: if (small) BW_LAUNCH(1, true); else BW_LAUNCH(1, false); break;
-        case 2: if (small) BW_LAUNCH(2, true); else BW_LAUNCH(2, false); break;
-        case 3: if (small) BW_LAUNCH(3, true); else BW_LAUNCH(3, false); break;
-        default: return hipErrorInvalidValue;
-        }
-#undef BW_LAUNCH
-        return hipGetLastError();
-    }
-    // whole form: 4 items + 4 loader waves per 512-thread workgroup
-    const dim3 grid((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), block(64 * BR_WAVES * 2);
-    if (fused) {  // the default kernels, in their own unit (fused implies SMALL)
-        const hipError_t e = launch_whole_default(P.L, grid, block, s, P, T, ops, in_a, in_b, idx, testvec, bk2, out,
-                                                  out_mode, B);
-        if (used) {
-            static const char *names[4] = {"", "k_blind_rotate<1,true,true> (whole form, fused)",
-                                           "k_blind_rotate<2,true,true> (whole form, fused)",
-                                           "k_blind_rotate_assist<true> (whole form, loader waves own polynomial b, fused)"};
-            *used = P.L >= 1 && P.L <= 3 ? names[P.L] : "";
-        }
-        return e;
-    }
-#define BR_LAUNCH(L_, S_)                                                                                         \
-    do {                                                                                                          \
-        hipLaunchKernelGGL((k_blind_rotate<L_, S_, false>), grid, block, 0, s, P, T, ops, in_a, in_b, idx,        \
-                           testvec, bk2, out, out_mode, B);                                                       \
-        if (used) *used = "k_blind_rotate<" #L_ "," #S_ ",false> (whole form)";                                   \
-    } while (0)
-    switch (P.L) {
-    case 1: if (small) BR_LAUNCH(1, true); else BR_LAUNCH(1, false); break;
-    case 2: if (small) BR_LAUNCH(2, true); else BR_LAUNCH(2, false); break;
-    case 3: if (small) BR_LAUNCH(3, true); else BR_LAUNCH(3, false); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef BR_LAUNCH
+}
+
+hipError_t launch_br(const BrEntry &k, const BrGeometry &g, const KParams &P, const DevTables &T, const BrBatch &b,
+                     hipStream_t s, const char **used) {
+    if (!k.fn) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k.fn, g.grid, g.block, 0, s, P, T, b.ops, b.in_a, b.in_b, b.idx, b.testvec,
+                       reinterpret_cast<const double2 *>(b.bk), b.out, b.out_mode, b.B);
+    if (used) *used = k.name;
     return hipGetLastError();
+}
+
+// One form for the whole batch; 'a': the A/B forms (TFHE_OPT_BR_FORM 6-8 and 30, A/B
+// libraries only).  Fused arithmetic in the exact-integer regime (SMALL) unless
+// the reference expression trees are requested (TFHE_OPT_ARITH).
+static hipError_t launch_br_form(const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s, char form,
+                                 const LaunchOpts &O, const char **used) {
+    const bool small = small_products(P), fused = small && fused_allowed(O);
+    if (form == 'a')
+        return ab_launch_blind_rotate ? ab_launch_blind_rotate(O.br_form, P, T, b, s, fused, used) : hipErrorInvalidValue;
+    return launch_br(br_kernel(form, P.L, small, fused), br_geometry(form, b.B), P, T, b, s, used);
 }
 
 #ifdef TFHE_AB_BUILD
 // A/B builds only (tools/ab/tfhe_ab_forms.hip, TFHE_OPT_BR_FORM 30): the latency form with row
 // counters (RC = 1) at L = 3, fused.
-hipError_t ab_launch_wide_rc(const KParams &P, const DevTables &T, const uint8_t *ops, const uint32_t *in_a,
-                             const uint32_t *in_b, const uint32_t *idx, const uint32_t *testvec, const double2 *bk2,
-                             uint32_t *out, int out_mode, size_t B, hipStream_t s, const char **used) {
+hipError_t ab_launch_wide_rc(const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s,
+                             const char **used) {
     if (P.L != 3) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_blind_rotate_wide<3, true, true, 1>), dim3((unsigned)B), dim3(64 * BW_WAVES), 0, s, P, T,
-                       ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B);
-    if (used) *used = "k_blind_rotate_wide<3,true,true,RC> (latency form, row counters, fused)";
-    return hipGetLastError();
+    return launch_br({k_blind_rotate_wide<3, true, true, 1>,
+                      "k_blind_rotate_wide<3,true,true,RC> (latency form, row counters, fused)"},
+                     br_geometry('W', b.B), P, T, b, s, used);
 }
 #endif
 
@@ -1538,81 +1503,133 @@ double blind_rotate_cost(size_t B, size_t cus, int L) {
     return c;
 }
 
-// Items [start, start + count) of a batch through one form: their ops / idx
-// entries / inputs / outputs / near-tie flags.
-static hipError_t launch_blind_rotate_range(const KParams &P, const DevTables &T, const uint8_t *ops,
-                                            const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                            const uint32_t *testvec, const double *bkd, uint32_t *out, int out_mode,
-                                            size_t start, size_t count, hipStream_t s, char form, const LaunchOpts &O,
-                                            const char **used) {
+// Items [start, start + count) of a batch: their ops / idx entries / inputs /
+// outputs (their near-tie flags are KParams': the caller's to shift).
+static BrBatch slice(const BrBatch &b, const KParams &P, size_t start, size_t count) {
     const size_t in_words = (size_t)P.n + 1;
-    const size_t out_words = out_mode == BR_OUT_LV1 ? (size_t)P.N + 1 : out_mode == BR_OUT_TRLWE ? 2 * (size_t)P.N : in_words;
-    KParams Q = P;
-    if (Q.tie_flags) Q.tie_flags += start;
-    return launch_blind_rotate_form(Q, T, ops ? ops + start : nullptr, idx ? in_a : in_a + start * in_words,
-                                    idx ? in_b : (in_b ? in_b + start * in_words : nullptr),
-                                    idx ? idx + 2 * start : nullptr, testvec, bkd, out + start * out_words, out_mode,
-                                    count, s, form, O, used);
+    const size_t out_words = b.out_mode == BR_OUT_LV1 ? (size_t)P.N + 1 : b.out_mode == BR_OUT_TRLWE ? 2 * (size_t)P.N : in_words;
+    BrBatch r = b;
+    if (b.ops) r.ops = b.ops + start;
+    if (b.idx) {
+        r.idx = b.idx + 2 * start;
+    } else {
+        r.in_a = b.in_a + start * in_words;
+        if (b.in_b) r.in_b = b.in_b + start * in_words;
+    }
+    r.out = b.out + start * out_words;
+    r.B = count;
+    return r;
 }
 
-static hipError_t launch_blind_rotate_forms(const KParams &P, const DevTables &T, const uint8_t *ops,
-                                            const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                            const uint32_t *testvec, const double *bkd, uint32_t *out, int out_mode,
-                                            size_t B, hipStream_t s, const LaunchOpts &O, const char **used) {
-    if (O.br_form) {  // forced form (TFHE_OPT_BR_FORM): the whole batch in one launch
-        const char f = O.br_form == 3 ? 'W' : O.br_form == 5 ? 'o' : O.br_form >= 6 ? 'a' : 'w';  // 6-8: A/B forms
-        return launch_blind_rotate_form(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B, s, f, O, used);
-    }
-    const size_t round = BR_WAVES * device_cus(), tail = B % round;
-    switch (blind_rotate_plan(B, device_cus(), P.L, nullptr)) {
-    case PLAN_NONE: return hipSuccess;
-    case PLAN_WIDE:
-        return launch_blind_rotate_form(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B, s, 'W', O, used);
-    case PLAN_OCTO:
-        return launch_blind_rotate_form(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B, s, 'o', O, used);
-    case PLAN_WHOLE_TAIL: {
-        hipError_t e = launch_blind_rotate_range(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, 0, B - tail,
-                                                 s, 'w', O, used);
-        if (e != hipSuccess) return e;
-        return launch_blind_rotate_range(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B - tail, tail, s,
-                                         'W', O, nullptr);
-    }
-    default:
-        return launch_blind_rotate_form(P, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B, s, 'w', O, used);
-    }
-}
-
-// The margin guard's recompute: the whole form in the
-// reference's expression trees over the same B items, whose workgroups return
-// at once unless one of their 4 items was flagged by the fused launch.
-static hipError_t launch_br_recompute(const KParams &P, const DevTables &T, const uint8_t *ops, const uint32_t *in_a,
-                                      const uint32_t *in_b, const uint32_t *idx, const uint32_t *testvec,
-                                      const double2 *bk2, uint32_t *out, int out_mode, size_t B, hipStream_t s) {
-    KParams Q = P;
-    Q.fallback = 1;
-    const dim3 grid((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), block(64 * BR_WAVES * 2);
-    switch (P.L) {
-    case 1: hipLaunchKernelGGL((k_blind_rotate<1, true, false>), grid, block, 0, s, Q, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    case 2: hipLaunchKernelGGL((k_blind_rotate<2, true, false>), grid, block, 0, s, Q, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    case 3: hipLaunchKernelGGL((k_blind_rotate<3, true, false>), grid, block, 0, s, Q, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const uint8_t *ops,
-                               const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                               const uint32_t *testvec, const double *bkd, uint32_t *out, int out_mode, size_t B,
-                               hipStream_t s, const LaunchOpts &O, const char **used) {
-    if (B == 0) return hipSuccess;
+hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBatch &b, hipStream_t s,
+                               const LaunchOpts &O, const char **used) {
+    if (b.B == 0) return hipSuccess;
     KParams Q = P;
     Q.fallback = 0;
     const bool fused = small_products(P) && fused_allowed(O);
     if (!fused) Q.tie_flags = nullptr;
-    hipError_t e = launch_blind_rotate_forms(Q, T, ops, in_a, in_b, idx, testvec, bkd, out, out_mode, B, s, O, used);
+    hipError_t e;
+    if (O.br_form) {  // forced form (TFHE_OPT_BR_FORM): the whole batch in one launch
+        const char f = O.br_form == 3 ? 'W' : O.br_form == 5 ? 'o' : O.br_form >= 6 ? 'a' : 'w';  // 6-8, 30: A/B forms
+        e = launch_br_form(Q, T, b, s, f, O, used);
+    } else {
+        switch (blind_rotate_plan(b.B, device_cus(), P.L, nullptr)) {
+        case PLAN_WIDE: e = launch_br_form(Q, T, b, s, 'W', O, used); break;
+        case PLAN_OCTO: e = launch_br_form(Q, T, b, s, 'o', O, used); break;
+        case PLAN_WHOLE_TAIL: {
+            const size_t full = b.B - b.B % (BR_WAVES * device_cus());
+            e = launch_br_form(Q, T, slice(b, P, 0, full), s, 'w', O, used);
+            if (e != hipSuccess) return e;
+            KParams Qt = Q;
+            if (Qt.tie_flags) Qt.tie_flags += full;
+            e = launch_br_form(Qt, T, slice(b, P, full, b.B - full), s, 'W', O, nullptr);
+            break;
+        }
+        default: e = launch_br_form(Q, T, b, s, 'w', O, used); break;
+        }
+    }
     if (e != hipSuccess || !fused || !Q.tie_flags) return e;
-    return launch_br_recompute(Q, T, ops, in_a, in_b, idx, testvec, reinterpret_cast<const double2 *>(bkd), out,
-                               out_mode, B, s);
+    // The margin guard's recompute: the whole form in the
+    // reference's expression trees over the same B items, whose workgroups return
+    // at once unless one of their 4 items was flagged by the fused launch.
+    Q.fallback = 1;
+    return launch_br(br_kernel('w', P.L, true, false), br_geometry('w', b.B), Q, T, b, s, nullptr);
+}
+
+// The key-switch shapes (t levels of basebit bits) with instantiated kernels, and
+// the forms each has.  Everything below that asks "is there a kernel for (t,
+// basebit)" or launches one goes through ks_with_shape over this list.
+enum KsForm : unsigned {
+    KS_LANES = 1,    // k_key_switch_lanes<t, basebit>: every listed shape
+    KS_WIDE = 2,     // the 44-word x 8-wave lane blocks
+    KS_GROUPED = 4,  // k_key_switch_ring and the lane form with 2 / 4 item groups per block
+    KS_GROUPS8 = 8,  // the lane form with 8 item groups per block
+    KS_GEMM = 16,    // k_key_switch_gemm (one-hot GEMM on the matrix cores)
+    KS_SEL = 32,     // k_key_switch_sel<t>
+    KS_GATHER = 64,  // k_key_switch_gather<t>, for any basebit >= 3
+};
+struct KsShape {
+    int t, basebit;
+    unsigned forms;
+};
+constexpr KsShape KS_SHAPES[] = {
+    {9, 2, KS_LANES | KS_WIDE | KS_GEMM | KS_SEL},
+    {8, 2, KS_LANES | KS_WIDE | KS_GEMM | KS_SEL},
+    {7, 2, KS_LANES | KS_WIDE | KS_GEMM | KS_SEL},
+    {4, 3, KS_LANES | KS_GATHER},
+    {3, 4, KS_LANES | KS_GATHER},
+    {4, 4, KS_LANES | KS_GATHER},
+    {3, 5, KS_LANES | KS_GROUPED | KS_GROUPS8 | KS_GEMM | KS_GATHER},
+    {2, 5, KS_LANES | KS_GROUPED | KS_GEMM | KS_GATHER},
+};
+constexpr int KS_ANY_BASEBIT = -1;
+
+// f(integral_constant t, integral_constant basebit) for the first listed shape
+// that has FORM and matches the run-time (t, basebit); false when there is none.
+// f is instantiated for the shapes with FORM only.
+template <unsigned FORM, size_t I = 0, class F>
+static bool ks_with_shape(int t, int basebit, F &&f) {
+    if constexpr (I < sizeof(KS_SHAPES) / sizeof(KS_SHAPES[0])) {
+        constexpr KsShape S = KS_SHAPES[I];
+        if constexpr ((S.forms & FORM) != 0) {
+            if (S.t == t && (S.basebit == basebit || basebit == KS_ANY_BASEBIT)) {
+                f(std::integral_constant<int, S.t>(), std::integral_constant<int, S.basebit>());
+                return true;
+            }
+        }
+        return ks_with_shape<FORM, I + 1>(t, basebit, f);
+    }
+    return false;
+}
+bool reencrypt_supported(int t, int basebit) {
+    return ks_with_shape<KS_LANES>(t, basebit, [](auto, auto) {});
+}
+bool ks_gemm_supported(int t, int basebit) {
+    return ks_with_shape<KS_GEMM>(t, basebit, [](auto, auto) {});
+}
+
+// TFHE_OPT_KS_FORM = 3 (auto) takes the GEMM wherever it applies and for any batch
+// size.  Basebit 2: faster from 64 items up (0.050 vs 0.218 ms at 64, 0.35 vs
+// 0.94 ms at 4,096; profiles/r03k_ks_gemm.txt), and a batch of one still fills
+// 242 workgroups (22 tiles x 11 K splits).  Basebit 5 (UINT4, 4,096 items): 0.90
+// ms against the ring form's 1.24 ms (profiles/r03m_ks_gemm_uint4.txt).
+bool ks_use_gemm(const LaunchOpts &O, int t, int basebit, size_t B, const KsGemm *G) {
+    if (B == 0 || (G && !(G->kg && G->part))) return false;
+    return (O.ks_form == 2 || O.ks_form == 3) && ks_gemm_supported(t, basebit);
+}
+
+// The name last_kernels() reports for a key-switch instantiation, from its own
+// template arguments.
+enum KsKernel { KK_LANES, KK_RING, KK_GEMM };
+template <KsKernel K, int... V>
+static const char *ks_name() {
+    static const std::string name = [] {
+        std::string r = K == KK_RING ? "k_key_switch_ring<" : K == KK_GEMM ? "k_key_switch_gemm<" : "k_key_switch_lanes<";
+        ((r += std::to_string(V) + ','), ...);
+        r.back() = '>';
+        return K == KK_GEMM ? r + " + k_ks_gemm_reduce" : r;
+    }();
+    return name.c_str();
 }
 
 // lane-form key switch over an input of n_in coefficients (+ b); false if
@@ -1620,6 +1637,15 @@ hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const uint8
 static bool launch_ks_lanes(const KParams &P, int t_, int basebit, const uint32_t *in, int n_in, int in_stride,
                             const uint32_t *key, uint32_t *out, size_t B, hipStream_t s, const LaunchOpts &O,
                             const char **used) {
+    // k_key_switch_lanes<T, BB, CH, WV, GW> on (g, b)
+    auto lanes = [&](dim3 g, dim3 b, auto T, auto BB, auto CH, auto WV, auto GW) {
+        hipLaunchKernelGGL((k_key_switch_lanes<T(), BB(), CH(), WV(), GW()>), g, b, 0, s, P, in, key, out, B, n_in,
+                           in_stride);
+        if (used) *used = ks_name<KK_LANES, T(), BB(), CH(), WV(), GW()>();
+    };
+    using std::integral_constant;
+    const integral_constant<int, KL_CHUNK> chunk;
+    const integral_constant<int, KL_WAVES> waves;
     const unsigned groups = (unsigned)((B + 63) / 64);
     dim3 grid((unsigned)((P.ks_stride + KL_CHUNK - 1) / KL_CHUNK), groups), block(64 * KL_WAVES);
     // basebit 2 (128/80-bit): the 44-word x 8-wave blocks when they spread the
@@ -1628,90 +1654,40 @@ static bool launch_ks_lanes(const KParams &P, int t_, int basebit, const uint32_
     const unsigned wide_chunks = (unsigned)((P.ks_stride + KL_CHUNK_WIDE - 1) / KL_CHUNK_WIDE);
     const size_t rounds = (grid.x * (size_t)groups + 255) / 256, rounds_w = (wide_chunks * (size_t)groups + 255) / 256;
     const bool wide = basebit == 2 && !O.ks_narrow && rounds_w * (KL_CHUNK_WIDE / 4) < rounds * (KL_CHUNK / 4);
-    if (wide) {
-        dim3 gw(wide_chunks, groups), bw(64 * KL_WAVES_WIDE);
-#define KS_WIDE(T_)                                                                                                     \
-    do {                                                                                                                \
-        hipLaunchKernelGGL((k_key_switch_lanes<T_, 2, KL_CHUNK_WIDE, KL_WAVES_WIDE>), gw, bw, 0, s, P, in, key, out, B, \
-                           n_in, in_stride);                                                                            \
-        if (used) *used = "k_key_switch_lanes<" #T_ ",2,44,8,1>";                                                       \
-    } while (0)
-        if (t_ == 9) KS_WIDE(9);
-        else if (t_ == 8) KS_WIDE(8);
-        else if (t_ == 7) KS_WIDE(7);
-        else return false;
-#undef KS_WIDE
-        return true;
-    }
+    if (wide)
+        return ks_with_shape<KS_WIDE>(t_, basebit, [&](auto T, auto BB) {
+            lanes(dim3(wide_chunks, groups), dim3(64 * KL_WAVES_WIDE), T, BB, integral_constant<int, KL_CHUNK_WIDE>(),
+                  integral_constant<int, KL_WAVES_WIDE>(), integral_constant<int, 1>());
+        });
     // UINT4 (basebit 5): the 323 MB KSK streams from HBM once per item group, so
     // 4 groups per block share each chunk through L2, and (default) one ring of
     // 4 buffers per block keeps 3 coefficients in flight (k_key_switch_ring).
     // LaunchOpts::ks_groups forces the lane form with 1, 2, 4 or 8 groups.
-    if (!O.ks_groups && basebit == 5 && B > 64 && (t_ == 3 || t_ == 2)) {
-        dim3 gr(grid.x, (unsigned)((B + 255) / 256)), br(256);
-        if (t_ == 3) hipLaunchKernelGGL((k_key_switch_ring<3, 5, KL_CHUNK, 4, KS_RING_DEPTH>), gr, br, 0, s, P, in, key, out, B, n_in, in_stride);
-        else hipLaunchKernelGGL((k_key_switch_ring<2, 5, KL_CHUNK, 4, KS_RING_DEPTH>), gr, br, 0, s, P, in, key, out, B, n_in, in_stride);
-        if (used) *used = t_ == 3 ? "k_key_switch_ring<3,5,32,4,4>" : "k_key_switch_ring<2,5,32,4,4>";
+    if (!O.ks_groups && basebit == 5 && B > 64 &&
+        ks_with_shape<KS_GROUPED>(t_, basebit, [&](auto T, auto BB) {
+            hipLaunchKernelGGL((k_key_switch_ring<T(), BB(), KL_CHUNK, 4, KS_RING_DEPTH>), dim3(grid.x, (unsigned)((B + 255) / 256)),
+                               dim3(256), 0, s, P, in, key, out, B, n_in, in_stride);
+            if (used) *used = ks_name<KK_RING, T(), BB(), KL_CHUNK, 4, KS_RING_DEPTH>();
+        }))
         return true;
-    }
     const int gw = O.ks_groups ? O.ks_groups : (basebit >= 5 ? 4 : 1);
-    if (gw == 8 && basebit == 5 && t_ == 3 && B > 64) {  // 16-word chunks: 8 rings fit the LDS
-        dim3 g8((unsigned)((P.ks_stride + 15) / 16), (unsigned)((B + 511) / 512)), b8(512);
-        hipLaunchKernelGGL((k_key_switch_lanes<3, 5, 16, 8, 8>), g8, b8, 0, s, P, in, key, out, B, n_in, in_stride);
-        if (used) *used = "k_key_switch_lanes<3,5,16,8,8>";
+    if (gw == 8 && basebit == 5 && B > 64 &&  // 16-word chunks: 8 rings fit the LDS
+        ks_with_shape<KS_GROUPS8>(t_, basebit, [&](auto T, auto BB) {
+            lanes(dim3((unsigned)((P.ks_stride + 15) / 16), (unsigned)((B + 511) / 512)), dim3(512), T, BB,
+                  integral_constant<int, 16>(), integral_constant<int, 8>(), integral_constant<int, 8>());
+        }))
         return true;
-    }
-    if (gw == 4 && basebit == 5 && B > 64) {
-        dim3 g4(grid.x, (unsigned)((B + 255) / 256)), b4(256);
-        if (t_ == 3) hipLaunchKernelGGL((k_key_switch_lanes<3, 5, KL_CHUNK, 4, 4>), g4, b4, 0, s, P, in, key, out, B, n_in, in_stride);
-        else if (t_ == 2) hipLaunchKernelGGL((k_key_switch_lanes<2, 5, KL_CHUNK, 4, 4>), g4, b4, 0, s, P, in, key, out, B, n_in, in_stride);
-        else return false;
-        if (used) *used = t_ == 3 ? "k_key_switch_lanes<3,5,32,4,4>" : "k_key_switch_lanes<2,5,32,4,4>";
-        return true;
-    }
-    if (gw == 2 && basebit == 5 && B > 64) {
-        dim3 g2(grid.x, (unsigned)((B + 127) / 128)), b2(256);
-        if (t_ == 3) hipLaunchKernelGGL((k_key_switch_lanes<3, 5, KL_CHUNK, 4, 2>), g2, b2, 0, s, P, in, key, out, B, n_in, in_stride);
-        else if (t_ == 2) hipLaunchKernelGGL((k_key_switch_lanes<2, 5, KL_CHUNK, 4, 2>), g2, b2, 0, s, P, in, key, out, B, n_in, in_stride);
-        else return false;
-        if (used) *used = t_ == 3 ? "k_key_switch_lanes<3,5,32,4,2>" : "k_key_switch_lanes<2,5,32,4,2>";
-        return true;
-    }
-#define KS_LANES(T_, BB_)                                                                                     \
-    do {                                                                                                      \
-        hipLaunchKernelGGL((k_key_switch_lanes<T_, BB_>), grid, block, 0, s, P, in, key, out, B, n_in, in_stride); \
-        if (used) *used = "k_key_switch_lanes<" #T_ "," #BB_ ",32,4,1>";                                      \
-    } while (0)
-    if (basebit == 2 && t_ == 9) KS_LANES(9, 2);
-    else if (basebit == 2 && t_ == 8) KS_LANES(8, 2);
-    else if (basebit == 2 && t_ == 7) KS_LANES(7, 2);
-    else if (basebit == 3 && t_ == 4) KS_LANES(4, 3);
-    else if (basebit == 4 && t_ == 3) KS_LANES(3, 4);
-    else if (basebit == 4 && t_ == 4) KS_LANES(4, 4);
-    else if (basebit == 5 && t_ == 3) KS_LANES(3, 5);
-    else if (basebit == 5 && t_ == 2) KS_LANES(2, 5);
-    else return false;
-#undef KS_LANES
-    return true;
-}
-
-static hipError_t launch_ks_gemm(const KParams &P, int t, int basebit, int n_in, int in_stride, const uint32_t *in,
-                                 const KsGemm &G, uint32_t *out, size_t B, hipStream_t s, const char **used);
-
-hipError_t launch_reencrypt(const KParams &P, int t_, int basebit, const uint32_t *in, const uint32_t *key,
-                            uint32_t *out, size_t B, hipStream_t s, const LaunchOpts &O, const char **used,
-                            const KsGemm *KG) {
-    if (B == 0) return hipSuccess;
-    if (KG && KG->kg && KG->part && ks_gemm_supported(t_, basebit) &&
-        (O.ks_form == 2 || (O.ks_form == 3 && ks_gemm_auto(t_, basebit))))
-        return launch_ks_gemm(P, t_, basebit, P.n, P.n + 1, in, *KG, out, B, s, used);
-    if (!launch_ks_lanes(P, t_, basebit, in, P.n, P.n + 1, key, out, B, s, O, used)) return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-bool reencrypt_supported(int t_, int basebit) {
-    return (basebit == 2 && t_ >= 7 && t_ <= 9) || (basebit == 3 && t_ == 4) || (basebit == 4 && (t_ == 3 || t_ == 4)) ||
-           (basebit == 5 && (t_ == 2 || t_ == 3));
+    if (gw == 4 && basebit == 5 && B > 64)
+        return ks_with_shape<KS_GROUPED>(t_, basebit, [&](auto T, auto BB) {
+            lanes(dim3(grid.x, (unsigned)((B + 255) / 256)), dim3(256), T, BB, chunk, waves, integral_constant<int, 4>());
+        });
+    if (gw == 2 && basebit == 5 && B > 64)
+        return ks_with_shape<KS_GROUPED>(t_, basebit, [&](auto T, auto BB) {
+            lanes(dim3(grid.x, (unsigned)((B + 127) / 128)), dim3(256), T, BB, chunk, waves, integral_constant<int, 2>());
+        });
+    return ks_with_shape<KS_LANES>(t_, basebit, [&](auto T, auto BB) {
+        lanes(grid, block, T, BB, chunk, waves, integral_constant<int, 1>());
+    });
 }
 
 // K splits of the gemm form: enough workgroups for one per CU.
@@ -1736,38 +1712,27 @@ static hipError_t launch_ks_gemm(const KParams &P, int t, int basebit, int n_in,
     const int splits = (nib + per - 1) / per;
     dim3 grid((unsigned)((P.n + 1 + 31) / 32), (unsigned)((B + KG_ITEMS - 1) / KG_ITEMS), (unsigned)splits),
         block(64 * KG_WAVES);
-#define KG_LAUNCH(T_, BB_)                                                                                       \
-    do {                                                                                                         \
-        hipLaunchKernelGGL((k_key_switch_gemm<T_, BB_>), grid, block, 0, s, P, in, G.kg, G.part, B, per, n_in, \
-                           in_stride);                                                                           \
-        if (used) *used = "k_key_switch_gemm<" #T_ "," #BB_ "> + k_ks_gemm_reduce";                              \
-    } while (0)
-    if (basebit == 2 && t == 9) KG_LAUNCH(9, 2);
-    else if (basebit == 2 && t == 8) KG_LAUNCH(8, 2);
-    else if (basebit == 2 && t == 7) KG_LAUNCH(7, 2);
-    else if (basebit == 5 && t == 3) KG_LAUNCH(3, 5);
-    else if (basebit == 5 && t == 2) KG_LAUNCH(2, 5);
-    else return hipErrorInvalidValue;
-#undef KG_LAUNCH
+    if (!ks_with_shape<KS_GEMM>(t, basebit, [&](auto T, auto BB) {
+            hipLaunchKernelGGL((k_key_switch_gemm<T(), BB()>), grid, block, 0, s, P, in, G.kg, G.part, B, per, n_in,
+                               in_stride);
+            if (used) *used = ks_name<KK_GEMM, T(), BB()>();
+        }))
+        return hipErrorInvalidValue;
     const size_t total = B * (size_t)(P.n + 1);
     hipLaunchKernelGGL(k_ks_gemm_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P, in, G.part, out, B,
                        splits, n_in, in_stride, t, basebit);
     return hipGetLastError();
 }
 
-bool ks_gemm_supported(int t, int basebit) {
-    return (basebit == 2 && t >= 7 && t <= 9) || (basebit == 5 && (t == 2 || t == 3));
+hipError_t launch_reencrypt(const KParams &P, int t_, int basebit, const uint32_t *in, const uint32_t *key,
+                            uint32_t *out, size_t B, hipStream_t s, const LaunchOpts &O, const char **used,
+                            const KsGemm *KG) {
+    if (B == 0) return hipSuccess;
+    if (KG && ks_use_gemm(O, t_, basebit, B, KG))
+        return launch_ks_gemm(P, t_, basebit, P.n, P.n + 1, in, *KG, out, B, s, used);
+    if (!launch_ks_lanes(P, t_, basebit, in, P.n, P.n + 1, key, out, B, s, O, used)) return hipErrorInvalidValue;
+    return hipGetLastError();
 }
-bool ks_gemm_supported(const KParams &P) { return ks_gemm_supported(P.iks_t, P.basebit); }
-// Batches from this size take the GEMM under TFHE_OPT_KS_FORM = 3: it is the
-// faster form from 64 items up (0.050 vs 0.218 ms at 64, 0.090 vs 0.239 ms at
-// 1,024, 0.35 vs 0.94 ms at 4,096; profiles/r03k_ks_gemm.txt), and a batch of
-// one still fills 242 workgroups (22 tiles x 11 K splits).
-size_t KS_GEMM_MIN_ITEMS = 1;
-// TFHE_OPT_KS_FORM = 3 takes the GEMM wherever it applies: at basebit 5 too
-// (UINT4, 4,096 items: 0.90 ms against the ring form's 1.24 ms, config 5
-// 182.5 k -> 186.0 k/s; profiles/r03m_ks_gemm_uint4.txt)
-bool ks_gemm_auto(int t, int basebit) { return ks_gemm_supported(t, basebit); }
 
 hipError_t launch_ksk_to_gemm(const KParams &P, const uint32_t *ksk, uint32_t *kg, int n_in, int t, int basebit,
                               hipStream_t s) {
@@ -1780,45 +1745,33 @@ hipError_t launch_ksk_to_gemm(const KParams &P, const uint32_t *ksk, uint32_t *k
 hipError_t launch_key_switch(const KParams &P, const uint32_t *lv1, const uint32_t *ksk, uint32_t *out,
                              size_t B, hipStream_t s, const LaunchOpts &O, const char **used, const KsGemm *KG) {
     if (B == 0) return hipSuccess;
-    // kernel form (TFHE_OPT_KS_FORM): 3 auto (default) = the one-hot GEMM for
-    // basebit 2 from KS_GEMM_MIN_ITEMS items, else lanes; 2 the GEMM wherever it
-    // applies; 0 lanes; 1 the select / gather forms
-    const bool gemm_ok = KG && KG->kg && KG->part && ks_gemm_supported(P);
-    if (gemm_ok && (O.ks_form == 2 || (O.ks_form == 3 && B >= KS_GEMM_MIN_ITEMS && ks_gemm_auto(P.iks_t, P.basebit))))
+    // kernel form (TFHE_OPT_KS_FORM): 3 auto (default) and 2 = the one-hot GEMM
+    // wherever it applies (ks_use_gemm), else lanes; 0 lanes; 1 the select /
+    // gather forms
+    if (KG && ks_use_gemm(O, P.iks_t, P.basebit, B, KG))
         return launch_ks_gemm(P, P.iks_t, P.basebit, 1024, 1025, lv1, *KG, out, B, s, used);
     if (O.ks_form != 1 && launch_ks_lanes(P, P.iks_t, P.basebit, lv1, 1024, 1025, ksk, out, B, s, O, used))
         return hipGetLastError();
     // items per block: TFHE_OPT_KS_SEL_ITEMS in {8, 16, 32} (default 8)
-    const int G = (O.ks_sel_items == 16 || O.ks_sel_items == 32) ? O.ks_sel_items : 8;
     if (used) *used = P.basebit == 2 ? "k_key_switch_sel" : "k_key_switch_gather";
-    dim3 grid((unsigned)((P.n + 1 + 255) / 256), (unsigned)((B + G - 1) / G)), block(256);
-#define KS_SEL(T_, G_) hipLaunchKernelGGL((k_key_switch_sel<T_, G_>), grid, block, 0, s, P, lv1, ksk, out, B)
-#define KS_GATHER(T_, G_) hipLaunchKernelGGL((k_key_switch_gather<T_, G_>), grid, block, 0, s, P, lv1, ksk, out, B)
-#define KS_G(KIND, T_)                  \
-    do {                                \
-        if (G == 16) KIND(T_, 16);      \
-        else if (G == 32) KIND(T_, 32); \
-        else KIND(T_, 8);               \
-    } while (0)
-    if (P.basebit == 2) {
-        switch (P.iks_t) {
-        case 7: KS_G(KS_SEL, 7); break;
-        case 8: KS_G(KS_SEL, 8); break;
-        case 9: KS_G(KS_SEL, 9); break;
-        default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (P.iks_t) {
-        case 2: KS_G(KS_GATHER, 2); break;
-        case 3: KS_G(KS_GATHER, 3); break;
-        case 4: KS_G(KS_GATHER, 4); break;
-        default: return hipErrorInvalidValue;
-        }
-    }
-#undef KS_SEL
-#undef KS_GATHER
-#undef KS_G
-    return hipGetLastError();
+    auto with_items = [&](auto f) {
+        if (O.ks_sel_items == 16) f(std::integral_constant<int, 16>());
+        else if (O.ks_sel_items == 32) f(std::integral_constant<int, 32>());
+        else f(std::integral_constant<int, 8>());
+    };
+    auto launch = [&](auto kernel, int G) {
+        dim3 grid((unsigned)((P.n + 1 + 255) / 256), (unsigned)((B + G - 1) / G)), block(256);
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, P, lv1, ksk, out, B);
+    };
+    const bool found =
+        P.basebit == 2
+            ? ks_with_shape<KS_SEL>(P.iks_t, 2, [&](auto T, auto) {
+                  with_items([&](auto G) { launch(k_key_switch_sel<T(), G()>, G()); });
+              })
+            : ks_with_shape<KS_GATHER>(P.iks_t, KS_ANY_BASEBIT, [&](auto T, auto) {
+                  with_items([&](auto G) { launch(k_key_switch_gather<T(), G()>, G()); });
+              });
+    return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_ksk_zero_k0(const KParams &P, uint32_t *ksk, hipStream_t s) {

@@ -348,16 +348,13 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     }
 }
 
-hipError_t launch_whole_default(int L, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
-                                const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b, const uint32_t *idx,
-                                const uint32_t *testvec, const double2 *bk2, uint32_t *out, int out_mode, size_t B) {
-    switch (L) {
-    case 1: hipLaunchKernelGGL((k_blind_rotate<1, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    case 2: hipLaunchKernelGGL((k_blind_rotate<2, true, true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    case 3: hipLaunchKernelGGL((k_blind_rotate_assist<true>), grid, block, 0, s, P, T, ops, in_a, in_b, idx, testvec, bk2, out, out_mode, B); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+BrEntry whole_default_kernel(int L) {
+    static const BrEntry kernels[3] = {
+        {k_blind_rotate<1, true, true>, "k_blind_rotate<1,true,true> (whole form, fused)"},
+        {k_blind_rotate<2, true, true>, "k_blind_rotate<2,true,true> (whole form, fused)"},
+        {k_blind_rotate_assist<true>, "k_blind_rotate_assist<true> (whole form, loader waves own polynomial b, fused)"},
+    };
+    return L >= 1 && L <= 3 ? kernels[L - 1] : BrEntry{nullptr, ""};
 }
 
 }  // namespace tfhe
