@@ -96,6 +96,33 @@ def test_circuit_mixed_gates_with_mux(oracle):
 
 
 @pytest.mark.gpu
+def test_circuit_not_of_not(oracle):
+    """NOTs of NOTs, of an input and of a gate: all of one level, where one gather
+    launch evaluates the level's NOTs, so none of them may read a slot that launch
+    writes.  Every wire bit-exact vs the reference's gate-by-gate evaluation."""
+    from conftest import get_keys
+    k = get_keys(oracle, "80")
+    ctx = tfhe_amd.Context("80", 0)
+    ctx.load_cloud_key(k.ck.offset, k.ck.testvec, k.ck.bk, k.ck.ksk)
+    sk = tfhe_amd.SecretKey(ctx.params, k.k0, k.k1)
+    c = Circuit()
+    a, b = c.input(), c.input()
+    n1 = c.not_(a)
+    n2 = c.not_(n1)
+    n3 = c.not_(n2)
+    g = c.and_(n2, b)
+    n4 = c.not_(g)
+    n5 = c.not_(n4)
+    c.output(n1, n2, n3, g, n4, n5)
+    inputs = sk.encrypt_bool(np.array([1, 1], np.uint8), seed0=900)
+    got, depth = c.run(ctx, inputs)
+    assert depth == 1
+    assert sk.decrypt_bool(got).tolist() == [False, True, False, True, False, True]
+    assert np.array_equal(got, oracle_eval(oracle, k, c, inputs))
+    ctx.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["adder128", "wide80"])
 def test_circuit_device_resident(oracle, shape):
     """tfhe_gpu_circuit_eval_dev (inputs and outputs in HBM, async on the context

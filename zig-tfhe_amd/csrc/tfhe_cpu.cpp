@@ -1,0 +1,553 @@
+// tfhe_cpu.cpp — the GPU-free half of the C ABI (include/tfhe_gpu.h): the tfhe_*
+// functions that take no context, and the circuit planner tfhe_gpu.cpp evaluates.
+// Plain C++17, no HIP: cpp/test_cpu.cpp runs it stand-alone, under the host sanitizers too.
+#include "tfhe_cpu.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <numeric>
+
+#include "host_math.hpp"
+
+namespace tfhe {
+
+bool params_ok(const tfhe_params *p, std::string &why) {
+    if (!p) { why = "params is NULL"; return false; }
+    if (p->N != 1024 || p->nbit != 10) { why = "only N=1024 (nbit=10) is supported"; return false; }
+    if (p->n == 0 || p->n > 1024) { why = "n must be in [1, 1024]"; return false; }
+    if (p->L < 1 || p->L > 3) { why = "L must be 1, 2 or 3"; return false; }
+    if (p->bgbit < 1 || p->bgbit * p->L > 32) { why = "bgbit*L must be <= 32"; return false; }
+    // the select form takes basebit 2 with t in [7, 9] (128/80-bit), the gather form
+    // basebit 3..8 with t in [2, 4] (Uint sets); the shapes with faster forms are
+    // listed once, in KS_SHAPES (tfhe_kernels.hip)
+    const bool ks_sel = p->basebit == 2 && p->iks_t >= 7 && p->iks_t <= 9;
+    const bool ks_gather = p->basebit >= 3 && p->basebit <= 8 && p->iks_t >= 2 && p->iks_t <= 4;
+    if (!(ks_sel || ks_gather) || p->basebit * p->iks_t >= 31) {
+        why = "unsupported key-switch base/levels";
+        return false;
+    }
+    return true;
+}
+
+size_t bk_rows(const tfhe_params &p) { return (size_t)p.n * 2 * p.L; }
+size_t ksk_rows(const tfhe_params &p) { return (size_t)p.N * p.iks_t * (1u << p.basebit); }
+size_t ksk_words(const tfhe_params &p) { return ksk_rows(p) * (p.n + 1); }
+
+// genDecompositionOffset (key.zig:121-131)
+uint32_t decomposition_offset(const tfhe_params &p) {
+    uint32_t offset = 0;
+    for (uint32_t l = 0; l < p.L; l++) offset += ((1u << p.bgbit) / 2) * (1u << (32 - (l + 1) * p.bgbit));
+    return offset;
+}
+
+// TLWELv0.encryptF64 (tlwe.zig:34-49) with DefaultPrng(seed).
+void tlwe_encrypt(uint32_t n, double mu, double alpha, const uint32_t *key, uint64_t seed, uint32_t *out) {
+    host::Rng r(seed);
+    uint32_t inner = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t x = r.u32();
+        inner += key[i] * x;
+        out[i] = x;
+    }
+    host::NormalDist nd(0.0, alpha);
+    uint32_t mu_t = host::f64_to_torus(mu);
+    out[n] = inner + host::gaussian_torus(mu_t, nd, r);
+}
+
+// ---- Circuit evaluation with a level scheduler -------------
+// Round packing.  A bootstrapped gate whose consumers all sit at least two
+// levels later, and that feeds no NOT, can run one level later without
+// changing the depth.  Levels are visited in ascending order; each moves to
+// the next level the number of such gates that minimises the modelled
+// blind-rotation time of the two levels (blind_rotate_cost: whole rounds of
+// 4 x #CUs gates, a ragged tail in the latency form).  Example: a level of
+// 10,256 gates hands 16 of them to the next level instead of running a
+// 16-gate tail.  Moved gates may move again from their new level.
+// TFHE_OPT_CIRCUIT_PACK = 0 turns packing off (A/B runs and tests).
+static void pack_levels(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                        const uint32_t *in_b, size_t cus, CostModel model, std::vector<uint32_t> &level,
+                        std::vector<std::vector<uint32_t>> &bs) {
+    const size_t W = n_inputs + n_gates;
+    const uint32_t max_level = (uint32_t)bs.size() - 1;
+    // earliest level among each wire's bootstrapped consumers; NOT consumers pin it
+    constexpr uint32_t PINNED = 0, FREE = 0xFFFFFFFFu;
+    // (kept from the ASAP levels: moving a gate later only raises its inputs'
+    // true first use, so the values stay safe)
+    std::vector<uint32_t> first_use(W, FREE);
+    for (size_t g = 0; g < n_gates; g++) {
+        const bool two = ops[g] <= TFHE_GATE_ORYN;
+        for (int k = 0; k < (two ? 2 : 1); k++) {
+            const uint32_t src = k ? in_b[g] : in_a[g];
+            if (ops[g] == TFHE_GATE_NOT) first_use[src] = PINNED;
+            else if (first_use[src] != PINNED) first_use[src] = std::min(first_use[src], level[n_inputs + g]);
+        }
+    }
+    const size_t R = 4 * cus;
+    const size_t J = (512 + cus - 1) / cus + 1;  // tail breakpoints per round (multiples of #CUs)
+    auto cost = [&](size_t b) { return model(b, cus); };
+    std::vector<uint32_t> cand;
+    for (uint32_t lv = 1; lv < max_level; lv++) {
+        cand.clear();
+        for (uint32_t g : bs[lv]) {
+            const uint32_t u = first_use[n_inputs + g];
+            if (u != PINNED && (u == FREE || u >= lv + 2)) cand.push_back(g);
+        }
+        if (cand.empty()) continue;
+        const size_t c0 = bs[lv].size(), c1 = bs[lv + 1].size(), k = cand.size();
+        // blind_rotate_cost(c0 - d) only drops where c0 - d reaches a breakpoint
+        // m*R + j*#CUs, so those d (and d = 0) are the only candidates
+        size_t best_d = 0;
+        double best = cost(c0) + cost(c1);
+        for (size_t m = (c0 - k) / R; m <= c0 / R; m++)
+            for (size_t j = 0; j <= J; j++) {
+                const size_t bp = m * R + j * cus;
+                if (bp > c0 || bp + k < c0) continue;
+                const size_t d = c0 - bp;
+                const double cd = cost(bp) + cost(c1 + d);
+                if (cd < best - 1e-9 || (cd < best + 1e-9 && d < best_d)) {
+                    best = cd;
+                    best_d = d;
+                }
+            }
+        if (best_d == 0) continue;
+        // move the last best_d candidates (those of the latest gates); their
+        // consumers are at lv + 2 or later, their inputs only gain slack
+        for (size_t x = k - best_d; x < k; x++) {
+            level[n_inputs + cand[x]] = lv + 1;
+            bs[lv + 1].push_back(cand[x]);
+        }
+        std::vector<uint32_t> keep;
+        keep.reserve(c0 - best_d);
+        for (uint32_t g : bs[lv])
+            if (level[n_inputs + g] == lv) keep.push_back(g);
+        bs[lv].swap(keep);
+    }
+}
+
+// Wire w < n_inputs is input w; gate g drives wire n_inputs + g.  A
+// bootstrapped gate is ready one level after the later of its inputs; a NOT
+// (negation) is ready with its input.  Fills level[] (per wire), the depth and
+// the bootstrapped / NOT gates of every level (packed unless `pack` is false);
+// returns nullptr, or the reason the graph is invalid.
+const char *schedule_levels(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                            const uint32_t *in_b, bool pack, size_t cus, CostModel cost, std::vector<uint32_t> &level,
+                            uint32_t &max_level, std::vector<std::vector<uint32_t>> &bs,
+                            std::vector<std::vector<uint32_t>> &nots) {
+    level.assign(n_inputs + n_gates, 0);
+    max_level = 0;
+    for (size_t g = 0; g < n_gates; g++) {
+        const size_t w = n_inputs + g;
+        const int op = ops[g];
+        const bool bootstrapped = op <= TFHE_GATE_ORYN || op == TFHE_GATE_COPY;
+        if (!bootstrapped && op != TFHE_GATE_NOT) return "unknown gate op";
+        if (in_a[g] >= w) return "gate input a is not an earlier wire";
+        const bool two = op <= TFHE_GATE_ORYN;
+        if (two && in_b[g] >= w) return "gate input b is not an earlier wire";
+        uint32_t r = level[in_a[g]];
+        if (two) r = std::max(r, level[in_b[g]]);
+        level[w] = bootstrapped ? r + 1 : r;
+        max_level = std::max(max_level, level[w]);
+    }
+    // groups in evaluation order: NOT(0), BS(1), NOT(1), ..., BS(max), NOT(max)
+    bs.assign(max_level + 1, {});
+    nots.assign(max_level + 1, {});
+    for (size_t g = 0; g < n_gates; g++) {
+        const uint32_t lv = level[n_inputs + g];
+        (ops[g] == TFHE_GATE_NOT ? nots[lv] : bs[lv]).push_back((uint32_t)g);
+    }
+    if (pack && max_level > 1) pack_levels(n_inputs, n_gates, ops, in_a, in_b, cus, cost, level, bs);
+    return nullptr;
+}
+
+const char *plan_circuit(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                         const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires, bool pack, size_t cus,
+                         CostModel cost, CircuitPlan &pl) {
+    const size_t W = n_inputs + n_gates;
+    if (W > 0xFFFFFFFFull) return "too many wires";
+    std::vector<uint32_t> ready;
+    if (const char *why = schedule_levels(n_inputs, n_gates, ops, in_a, in_b, pack, cus, cost, ready, pl.max_level,
+                                          pl.bs, pl.nots))
+        return why;
+    for (size_t o = 0; o < n_outputs; o++)
+        if (out_wires[o] >= W) return "output wire out of range";
+    // A NOT of a NOT is in its input's group, which one gather launch evaluates: it may not read a
+    // slot that launch writes.  It equals its input's input, so it shares that wire's slot and
+    // leaves the group (pl.nots); every gather index is then below its group's first slot.
+    std::vector<uint32_t> same_as(W);
+    std::iota(same_as.begin(), same_as.end(), 0u);
+    for (size_t g = 0; g < n_gates; g++)
+        if (ops[g] == TFHE_GATE_NOT && in_a[g] >= n_inputs && ops[in_a[g] - n_inputs] == TFHE_GATE_NOT)
+            same_as[n_inputs + g] = same_as[in_a[in_a[g] - n_inputs]];
+    for (std::vector<uint32_t> &group : pl.nots)
+        group.erase(std::remove_if(group.begin(), group.end(),
+                                   [&](uint32_t g) { return same_as[n_inputs + g] != n_inputs + g; }),
+                    group.end());
+    std::vector<uint32_t> slot(W);
+    for (size_t w = 0; w < n_inputs; w++) slot[w] = (uint32_t)w;
+    uint32_t next = (uint32_t)n_inputs;
+    for (uint32_t lv = 0; lv <= pl.max_level; lv++) {
+        for (uint32_t g : pl.bs[lv]) slot[n_inputs + g] = next++;
+        for (uint32_t g : pl.nots[lv]) slot[n_inputs + g] = next++;
+    }
+    for (size_t w = n_inputs; w < W; w++) slot[w] = slot[same_as[w]];
+    pl.idx.clear();
+    pl.cops.clear();
+    pl.idx.reserve(2 * n_gates + n_outputs);
+    for (uint32_t lv = 0; lv <= pl.max_level; lv++) {
+        for (uint32_t g : pl.bs[lv]) {
+            const bool two = ops[g] <= TFHE_GATE_ORYN;
+            pl.idx.push_back(slot[in_a[g]]);
+            pl.idx.push_back(two ? slot[in_b[g]] : slot[in_a[g]]);
+            pl.cops.push_back(ops[g]);
+        }
+        for (uint32_t g : pl.nots[lv]) pl.idx.push_back(slot[in_a[g]]);
+    }
+    for (size_t o = 0; o < n_outputs; o++) pl.idx.push_back(slot[out_wires[o]]);
+    return nullptr;
+}
+
+// The graph's validation without a plan (before a partition): nullptr, or plan_circuit's
+// reason for a graph of at most 2^32 - 1 wires.
+const char *check_circuit(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                          const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires) {
+    std::vector<uint32_t> level;
+    std::vector<std::vector<uint32_t>> bs, nots;
+    uint32_t ml = 0;
+    if (const char *why = schedule_levels(n_inputs, n_gates, ops, in_a, in_b, false, 256, nullptr, level, ml, bs, nots))
+        return why;
+    for (size_t o = 0; o < n_outputs; o++)
+        if (out_wires[o] >= n_inputs + n_gates) return "output wire out of range";
+    return nullptr;
+}
+
+namespace {
+struct Dsu {
+    std::vector<uint32_t> p;
+    explicit Dsu(size_t n) : p(n) { std::iota(p.begin(), p.end(), 0u); }
+    uint32_t find(uint32_t x) {
+        while (p[x] != x) x = p[x] = p[p[x]];
+        return x;
+    }
+    void unite(uint32_t a, uint32_t b) { p[find(a)] = find(b); }
+};
+}  // namespace
+
+// Device of every gate (dev_of_gate[g] < D) for circuit_eval_multi: the
+// connected components of the gate DAG under gate-to-gate wires (primary
+// inputs do not join gates: they are replicated), largest first (by
+// bootstrapped gates) onto the least-loaded device.
+void partition_gates(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b,
+                     size_t D, std::vector<uint32_t> &dev_of_gate) {
+    Dsu dsu(std::max<size_t>(n_gates, 1));
+    auto join = [&](size_t g, uint32_t w) {
+        if (w >= n_inputs) dsu.unite((uint32_t)g, (uint32_t)(w - n_inputs));
+    };
+    for (size_t g = 0; g < n_gates; g++) {
+        join(g, in_a[g]);
+        if (ops[g] <= TFHE_GATE_ORYN) join(g, in_b[g]);
+    }
+    std::vector<uint64_t> weight(n_gates, 0);
+    for (size_t g = 0; g < n_gates; g++)
+        if (ops[g] != TFHE_GATE_NOT) weight[dsu.find((uint32_t)g)]++;
+    std::vector<uint32_t> roots;
+    for (size_t g = 0; g < n_gates; g++)
+        if (dsu.find((uint32_t)g) == g) roots.push_back((uint32_t)g);
+    std::stable_sort(roots.begin(), roots.end(), [&](uint32_t a, uint32_t b) { return weight[a] > weight[b]; });
+    std::vector<uint32_t> dev_of_root(n_gates, 0);
+    std::vector<uint64_t> load(D, 0);
+    for (uint32_t r : roots) {
+        const size_t d = std::min_element(load.begin(), load.end()) - load.begin();
+        dev_of_root[r] = (uint32_t)d;
+        load[d] += weight[r];
+    }
+    dev_of_gate.resize(n_gates);
+    for (size_t g = 0; g < n_gates; g++) dev_of_gate[g] = dev_of_root[dsu.find((uint32_t)g)];
+}
+
+}  // namespace tfhe
+
+using namespace tfhe;
+
+namespace {
+
+uint32_t tlwe_phase(uint32_t n, const uint32_t *ct, const uint32_t *key) {
+    uint32_t inner = 0;
+    for (uint32_t i = 0; i < n; i++) inner += ct[i] * key[i];
+    return ct[n] - inner;
+}
+
+// PublicKeyLv0.encryptF64 (proxy_reenc.zig:83-113): plaintext on b, each
+// encryption of zero kept with probability 1/2 and added or subtracted with
+// probability 1/2 (two booleans, the second only when kept), then fresh noise.
+void pk_encrypt(uint32_t n, const uint32_t *pk, size_t pk_size, double plaintext, double alpha, uint64_t seed,
+                uint32_t *out) {
+    host::Rng r(seed);
+    std::fill(out, out + n + 1, 0u);
+    out[n] = host::f64_to_torus(plaintext);
+    for (size_t e = 0; e < pk_size; e++) {
+        if (!r.boolean()) continue;
+        const uint32_t *enc = pk + e * (n + 1);
+        if (r.boolean())
+            for (uint32_t x = 0; x <= n; x++) out[x] += enc[x];
+        else
+            for (uint32_t x = 0; x <= n; x++) out[x] -= enc[x];
+    }
+    host::NormalDist nd(0.0, alpha);
+    out[n] += host::gaussian_torus(0u, nd, r);
+}
+
+// ProxyReencryptionKey.new{Symmetric,Asymmetric}WithParams (proxy_reenc.zig:
+// 150-256): entry (i, j, k != 0) encrypts k * key_from[i] / 2^((j+1)*basebit)
+// under the target; the c-th encryption in (i, j, k) order uses seed0 + c.
+template <class Enc>
+void reenc_key_gen(uint32_t n, const uint32_t *key_from, uint32_t basebit, uint32_t t, uint64_t seed0,
+                   uint32_t *out, Enc enc) {
+    const uint32_t base = 1u << basebit;
+    std::fill(out, out + (size_t)n * t * base * (n + 1), 0u);
+    uint64_t c = 0;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t j = 0; j < t; j++)
+            for (uint32_t k = 1; k < base; k++) {
+                const double p = ((double)k * (double)key_from[i]) / (double)(1u << ((j + 1) * basebit));
+                enc(p, seed0 + c++, out + ((size_t)base * t * i + (size_t)base * j + k) * (n + 1));
+            }
+}
+
+// ---- Cloud-key files (include/tfhe_gpu.h) ---------------
+struct KeyFileHeader {
+    char magic[8];
+    uint32_t version, n, N, L, bgbit, basebit, iks_t, offset;
+    uint64_t bsk_len, ksk_len, checksum;
+};
+static_assert(sizeof(KeyFileHeader) == 64, "key file header is 64 bytes");
+constexpr char KEY_MAGIC[8] = {'Z', 'T', 'F', 'H', 'E', 'C', 'K', '1'};
+
+// FNV-1a-64 over 8-byte little-endian words; a section's last < 8 bytes one by one
+struct Fnv64 {
+    uint64_t h = 0xcbf29ce484222325ull;
+    void add(const void *p, size_t bytes) {
+        const unsigned char *b = static_cast<const unsigned char *>(p);
+        size_t k = 0;
+        for (; k + 8 <= bytes; k += 8) {
+            uint64_t w;
+            std::memcpy(&w, b + k, 8);
+            h = (h ^ w) * 0x100000001b3ull;
+        }
+        for (; k < bytes; k++) h = (h ^ b[k]) * 0x100000001b3ull;
+    }
+};
+
+uint64_t key_checksum(const tfhe_params *p, const uint32_t *tv_a, const uint32_t *tv_b, const double *bsk,
+                      size_t bsk_len, const uint32_t *ksk, size_t ksk_len) {
+    Fnv64 f;
+    f.add(tv_a, p->N * sizeof(uint32_t));
+    f.add(tv_b, p->N * sizeof(uint32_t));
+    f.add(bsk, bsk_len * sizeof(double));
+    f.add(ksk, ksk_len * sizeof(uint32_t));
+    return f.h;
+}
+
+bool key_shape_ok(const tfhe_params *p, size_t bsk_len, size_t ksk_len) {
+    std::string why;
+    return params_ok(p, why) && bsk_len == bk_rows(*p) * 2 * p->N && ksk_len == ksk_words(*p);
+}
+
+// generateLookupTableFullAssign (lut/generator.zig:155-191): message x's range
+// [divRound(xN, m), divRound((x+1)N, m)) of the raw table holds values[x]; the
+// table is rotated by divRound(N, 2m), its last divRound(N, 2m) entries negated,
+// and stored as the b polynomial (a = 0).  divRound(a, b) = (a + b/2) / b
+// (generator.zig:253-255).  Any m >= 1, as the reference (m > N leaves ranges empty).
+void lut_from_values(size_t N, size_t m, const uint32_t *values, uint32_t *tv) {
+    std::vector<uint32_t> raw(N, 0u);
+    auto div_round = [](size_t a, size_t b) { return (a + b / 2) / b; };
+    for (size_t x = 0; x < m; x++) {
+        const size_t s = div_round(x * N, m), e = div_round((x + 1) * N, m);
+        for (size_t i = s; i < e; i++) raw[i] = values[x];
+    }
+    const size_t off = div_round(N, 2 * m);
+    for (size_t i = 0; i < N; i++) tv[N + i] = raw[(i + off) % N];
+    for (size_t i = N - off; i < N; i++) tv[N + i] = ~tv[N + i] + 1u;
+    for (size_t i = 0; i < N; i++) tv[i] = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tfhe_cloud_key_write(const char *path, const tfhe_params *p, uint32_t offset, const uint32_t *tv_a,
+                         const uint32_t *tv_b, const double *bsk, size_t bsk_len, const uint32_t *ksk,
+                         size_t ksk_len) {
+    if (!path || !tv_a || !tv_b || !bsk || !ksk || !key_shape_ok(p, bsk_len, ksk_len)) return TFHE_ERR_INVALID;
+    KeyFileHeader h{};
+    std::memcpy(h.magic, KEY_MAGIC, 8);
+    h.version = 1;
+    h.n = p->n, h.N = p->N, h.L = p->L, h.bgbit = p->bgbit, h.basebit = p->basebit, h.iks_t = p->iks_t;
+    h.offset = offset;
+    h.bsk_len = bsk_len;
+    h.ksk_len = ksk_len;
+    h.checksum = key_checksum(p, tv_a, tv_b, bsk, bsk_len, ksk, ksk_len);
+    FILE *fp = std::fopen(path, "wb");
+    if (!fp) return TFHE_ERR_IO;
+    bool ok = std::fwrite(&h, sizeof h, 1, fp) == 1 && std::fwrite(tv_a, 4, p->N, fp) == p->N &&
+              std::fwrite(tv_b, 4, p->N, fp) == p->N && std::fwrite(bsk, 8, bsk_len, fp) == bsk_len &&
+              std::fwrite(ksk, 4, ksk_len, fp) == ksk_len;
+    ok = std::fclose(fp) == 0 && ok;
+    return ok ? TFHE_OK : TFHE_ERR_IO;
+}
+
+int tfhe_cloud_key_read(const char *path, const tfhe_params *p, uint32_t *offset, uint32_t *tv_a, uint32_t *tv_b,
+                        double *bsk, size_t bsk_len, uint32_t *ksk, size_t ksk_len) {
+    if (!path || !offset || !tv_a || !tv_b || !bsk || !ksk || !key_shape_ok(p, bsk_len, ksk_len))
+        return TFHE_ERR_INVALID;
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return TFHE_ERR_IO;
+    KeyFileHeader h{};
+    int rc = TFHE_OK;
+    if (std::fread(&h, sizeof h, 1, fp) != 1)
+        rc = TFHE_ERR_IO;
+    else if (std::memcmp(h.magic, KEY_MAGIC, 8) != 0 || h.version != 1)
+        rc = TFHE_ERR_INVALID;  // not a key file of this format
+    else if (h.n != p->n || h.N != p->N || h.L != p->L || h.bgbit != p->bgbit || h.basebit != p->basebit ||
+             h.iks_t != p->iks_t || h.bsk_len != bsk_len || h.ksk_len != ksk_len)
+        rc = TFHE_ERR_INVALID;  // another parameter set
+    else if (std::fread(tv_a, 4, p->N, fp) != p->N || std::fread(tv_b, 4, p->N, fp) != p->N ||
+             std::fread(bsk, 8, bsk_len, fp) != bsk_len || std::fread(ksk, 4, ksk_len, fp) != ksk_len)
+        rc = TFHE_ERR_IO;  // truncated
+    std::fclose(fp);
+    if (rc) return rc;
+    if (key_checksum(p, tv_a, tv_b, bsk, bsk_len, ksk, ksk_len) != h.checksum) return TFHE_ERR_INVALID;
+    *offset = h.offset;
+    return TFHE_OK;
+}
+
+int tfhe_secret_key_new(const tfhe_params *p, uint64_t seed, uint32_t *key_lv0, uint32_t *key_lv1) {
+    if (!p || !key_lv0 || !key_lv1) return TFHE_ERR_INVALID;
+    host::Rng r(seed);  // SecretKey.new (key.zig:41-57)
+    for (uint32_t i = 0; i < p->n; i++) key_lv0[i] = r.boolean() ? 1u : 0u;
+    for (uint32_t i = 0; i < p->N; i++) key_lv1[i] = r.boolean() ? 1u : 0u;
+    return TFHE_OK;
+}
+
+int tfhe_public_key_gen(const tfhe_params *p, const uint32_t *key, size_t size, double alpha, uint64_t seed0,
+                        uint32_t *pk) {
+    if (!p || !key || (size && !pk)) return TFHE_ERR_INVALID;
+    for (size_t e = 0; e < size; e++) tlwe_encrypt(p->n, 0.0, alpha, key, seed0 + e, pk + e * (p->n + 1));
+    return TFHE_OK;
+}
+
+int tfhe_public_key_encrypt_bool_batch(const tfhe_params *p, const uint32_t *pk, size_t pk_size, const uint8_t *bits,
+                                       double alpha, uint64_t seed0, uint32_t *out, size_t B) {
+    if (!p || (pk_size && !pk) || (B && (!bits || !out))) return TFHE_ERR_INVALID;
+    for (size_t i = 0; i < B; i++)
+        pk_encrypt(p->n, pk, pk_size, bits[i] ? 0.125 : -0.125, alpha, seed0 + i, out + i * (p->n + 1));
+    return TFHE_OK;
+}
+
+int tfhe_reenc_key_gen_symmetric(const tfhe_params *p, const uint32_t *key_from, const uint32_t *key_to, double alpha,
+                                 uint32_t basebit, uint32_t t, uint64_t seed0, uint32_t *out) {
+    if (!p || !key_from || !key_to || !out || basebit < 1 || basebit > 8 || t < 1) return TFHE_ERR_INVALID;
+    reenc_key_gen(p->n, key_from, basebit, t, seed0, out, [&](double v, uint64_t seed, uint32_t *o) {
+        tlwe_encrypt(p->n, v, alpha, key_to, seed, o);
+    });
+    return TFHE_OK;
+}
+
+int tfhe_reenc_key_gen_asymmetric(const tfhe_params *p, const uint32_t *key_from, const uint32_t *pk, size_t pk_size,
+                                  double alpha, uint32_t basebit, uint32_t t, uint64_t seed0, uint32_t *out) {
+    if (!p || !key_from || !out || (pk_size && !pk) || basebit < 1 || basebit > 8 || t < 1) return TFHE_ERR_INVALID;
+    reenc_key_gen(p->n, key_from, basebit, t, seed0, out, [&](double v, uint64_t seed, uint32_t *o) {
+        pk_encrypt(p->n, pk, pk_size, v, alpha, seed, o);
+    });
+    return TFHE_OK;
+}
+
+int tfhe_circuit_partition(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                           const uint32_t *in_b, int num_devices, uint32_t *device_of_gate) {
+    if ((n_gates && (!ops || !in_a || !in_b || !device_of_gate)) || num_devices < 1) return TFHE_ERR_INVALID;
+    if (n_inputs + n_gates > 0xFFFFFFFFull) return TFHE_ERR_INVALID;
+    if (check_circuit(n_inputs, n_gates, ops, in_a, in_b, 0, nullptr)) return TFHE_ERR_INVALID;
+    std::vector<uint32_t> dev;
+    partition_gates(n_inputs, n_gates, ops, in_a, in_b, (size_t)num_devices, dev);
+    std::copy(dev.begin(), dev.end(), device_of_gate);
+    return TFHE_OK;
+}
+
+// ---- host-side TLWELv0 helpers ------------------------------------------
+int tfhe_encrypt_bool_batch(const tfhe_params *p, const uint32_t *key, const uint8_t *bits, uint64_t seed0,
+                            uint32_t *out, size_t B) {
+    if (!p || !key || (B && (!bits || !out))) return TFHE_ERR_INVALID;
+    for (size_t i = 0; i < B; i++)
+        tlwe_encrypt(p->n, bits[i] ? 0.125 : -0.125, p->alpha_lv0, key, seed0 + i, out + i * (p->n + 1));
+    return TFHE_OK;
+}
+
+int tfhe_decrypt_bool_batch(const tfhe_params *p, const uint32_t *key, const uint32_t *ct, uint8_t *bits, size_t B) {
+    if (!p || !key || (B && (!bits || !ct))) return TFHE_ERR_INVALID;
+    for (size_t i = 0; i < B; i++) bits[i] = (int32_t)tlwe_phase(p->n, ct + i * (p->n + 1), key) >= 0;
+    return TFHE_OK;
+}
+
+int tfhe_encrypt_lwe_message_batch(const tfhe_params *p, const uint32_t *key, const uint32_t *msgs, uint32_t m,
+                                   uint64_t seed0, uint32_t *out, size_t B) {
+    if (!p || !key || m == 0 || (B && (!msgs || !out))) return TFHE_ERR_INVALID;
+    const double scale = 1.0 / (2.0 * (double)m);
+    for (size_t i = 0; i < B; i++)
+        tlwe_encrypt(p->n, (double)(msgs[i] % m) * scale, p->alpha_lv0, key, seed0 + i, out + i * (p->n + 1));
+    return TFHE_OK;
+}
+
+int tfhe_decrypt_lwe_message_batch(const tfhe_params *p, const uint32_t *key, const uint32_t *ct, uint32_t m,
+                                   uint32_t *msgs, size_t B) {
+    if (!p || !key || m == 0 || (B && (!msgs || !ct))) return TFHE_ERR_INVALID;
+    const double scale = 1.0 / (2.0 * (double)m);
+    for (size_t i = 0; i < B; i++) {
+        double f = (double)tlwe_phase(p->n, ct + i * (p->n + 1), key) / 4294967296.0;
+        msgs[i] = (uint32_t)((uint64_t)(f / scale + 0.5) % m);
+    }
+    return TFHE_OK;
+}
+
+int tfhe_lut_generate_scaled(const tfhe_params *p, uint32_t m, double scale, const uint32_t *f_table, uint32_t *tv) {
+    if (!p || !f_table || !tv || m == 0 || m > TFHE_LUT_MAX_M) return TFHE_ERR_INVALID;
+    try {
+        std::vector<uint32_t> enc(m);
+        for (uint32_t x = 0; x < m; x++)  // Encoder.encode (encoder.zig:66-74): (f(x) mod m) * scale -> torus
+            enc[x] = host::f64_to_torus((double)(f_table[x] % m) * scale);
+        lut_from_values(p->N, m, enc.data(), tv);
+    } catch (const std::bad_alloc &) {  // never through the C ABI (std::terminate)
+        return TFHE_ERR_OOM;
+    }
+    return TFHE_OK;
+}
+
+int tfhe_lut_generate(const tfhe_params *p, uint32_t m, const uint32_t *f_table, uint32_t *tv) {
+    if (!p || m == 0 || m > TFHE_LUT_MAX_M) return TFHE_ERR_INVALID;
+    return tfhe_lut_generate_scaled(p, m, 1.0 / (2.0 * (double)m), f_table, tv);  // Encoder.new (encoder.zig:29-42)
+}
+
+int tfhe_lut_generate_full(const tfhe_params *p, uint32_t m, const uint32_t *values, uint32_t *tv) {
+    if (!p || !values || !tv || m == 0 || m > TFHE_LUT_MAX_M) return TFHE_ERR_INVALID;
+    try {
+        lut_from_values(p->N, m, values, tv);
+    } catch (const std::bad_alloc &) {
+        return TFHE_ERR_OOM;
+    }
+    return TFHE_OK;
+}
+
+int tfhe_fft_tables(uint32_t N, int source, double *twist_re, double *twist_im, double *stage_re, double *stage_im) {
+    if (N < 4 || (N & (N - 1)) || (source != TFHE_TWIDDLES_GLIBC && source != TFHE_TWIDDLES_FDLIBM))
+        return TFHE_ERR_INVALID;
+    std::vector<double> a, b;
+    host::twist_table(N, a, b, source);
+    if (twist_re) std::memcpy(twist_re, a.data(), a.size() * 8);
+    if (twist_im) std::memcpy(twist_im, b.data(), b.size() * 8);
+    host::stage_twiddles(N, false, a, b, source);
+    if (stage_re) std::memcpy(stage_re, a.data(), a.size() * 8);
+    if (stage_im) std::memcpy(stage_im, b.data(), b.size() * 8);
+    return TFHE_OK;
+}
+
+}  // extern "C"

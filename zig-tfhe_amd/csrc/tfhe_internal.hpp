@@ -65,7 +65,7 @@ enum BrOut : int {
     BR_OUT_LV0_EXTRACT2 = 2,
 };
 
-// Device constant tables uploaded once per context (host_tables in tfhe_gpu.cpp).
+// Device constant tables uploaded once per context (build_tables in tfhe_gpu.cpp).
 struct DevTables {
     const C2 *twist;  // N/2 twisting factors exp(i*pi*k/N)        fft.zig:92-106
     const C2 *tw;     // N/2-1 forward stage twiddles (recurrence)  fft.zig:590-616
