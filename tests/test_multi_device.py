@@ -86,6 +86,57 @@ def test_two_shards_every_batch_entry(oracle):
     multi.close()
 
 
+def test_two_shards_error_routing(oracle):
+    """A device's refusal reaches tfhe_gpu_last_error: as it is from the first device, behind
+    "device <id>: " from another one.  B = 4 over [0, 0] puts items 0-1 on the first slot and
+    2-3 on the second; a bad op code is refused host-side before any upload of its slot, and
+    the context goes on working after each refusal."""
+    single, k = loaded(oracle, "80")
+    multi, _ = loaded(oracle, "80", devices=[0, 0])
+    g = rng(76)
+    ops = g.integers(0, 10, 4).astype(np.uint8)
+    A, Bc = u32rand(g, 4, k.p.n + 1), u32rand(g, 4, k.p.n + 1)
+    want = single.gate_batch(ops, A, Bc)
+    for item, prefixed in ((3, True), (0, False)):
+        bad = ops.copy()
+        bad[item] = 200
+        with pytest.raises(tfhe_amd.TfheError) as e:
+            multi.gate_batch(bad, A, Bc)
+        assert e.value.status == tfhe_amd.ERR_INVALID
+        if prefixed:
+            assert "device 0: bad gate op" in str(e.value)
+        else:
+            assert "bad gate op" in str(e.value) and "device 0:" not in str(e.value)
+        assert np.array_equal(multi.gate_batch(ops, A, Bc), want)
+    single.close()
+    multi.close()
+
+
+def test_two_shards_reencryption_key():
+    """A re-encryption key holds one copy per device of the context that loaded it: over
+    [0, 0] an uneven batch (B = 3: two items and one) gives one device's words; another
+    context, over [0, 0, 0], refuses the key."""
+    single, multi = tfhe_amd.Context("80", 0), tfhe_amd.Context.multi("80", devices=[0, 0])
+    other = tfhe_amd.Context.multi("80", devices=[0, 0, 0])
+    alice, bob = tfhe_amd.secret_key_new(single.params, 21), tfhe_amd.secret_key_new(single.params, 22)
+    key = tfhe_amd.ProxyReencryptionKey.new_symmetric(alice, bob, 2000)
+    bits = np.array([1, 0, 1], np.uint8)
+    enc = alice.encrypt_bool(bits, seed0=9)
+    r1, r2 = tfhe_amd.HipReencryptor(single, key), tfhe_amd.HipReencryptor(multi, key)
+    out = r2.reencrypt(enc)
+    assert np.array_equal(out, r1.reencrypt(enc))
+    assert np.array_equal(bob.decrypt_bool(out), bits.astype(bool))
+    r2.ctx = other  # the key loaded on `multi`, handed to another context
+    with pytest.raises(tfhe_amd.TfheError) as e:
+        r2.reencrypt(enc)
+    assert e.value.status == tfhe_amd.ERR_INVALID and "key was not loaded on this context" in str(e.value)
+    r2.ctx = multi
+    r1.close()
+    r2.close()
+    for c in (single, multi, other):
+        c.close()
+
+
 def test_two_shards_keygen_broadcast(oracle):
     """Keygen on the first device, D2D broadcast to the second: every shard's
     result equals the oracle keygen's."""

@@ -14,10 +14,11 @@ $H -c -o $O/k.o zig-tfhe_amd/csrc/tfhe_kernels.hip &
 $H -mllvm -amdgpu-sched-strategy=max-memory-clause -c -o $O/w.o zig-tfhe_amd/csrc/tfhe_kernels_whole.hip &
 $H -mllvm -amdgpu-sched-strategy=max-memory-clause -c -o $O/ab.o tools/ab/tfhe_ab_forms.hip &
 $H -x hip -c -o $O/g.o zig-tfhe_amd/csrc/tfhe_gpu.cpp &
+$H -x hip -c -o $O/m.o zig-tfhe_amd/csrc/tfhe_multi.cpp &
 # the GPU-free half of the C ABI: the host compiler, as in the Makefile (no hipcc flags)
 g++ -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -Izig-tfhe_amd/csrc -DTFHE_AB_BUILD -c -o $O/c.o zig-tfhe_amd/csrc/tfhe_cpu.cpp &
 wait
 printf 'extern "C" const char *tfhe_gpu_build_id(void) { return "ab-%s"; }\n' "$(cat $O/k.o $O/w.o $O/ab.o | sha256sum | cut -c1-13)" > $O/id.cpp
 g++ -O2 -fPIC -c -o $O/id.o $O/id.cpp
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/bin/lib_ab${NAME:+_$NAME}.so $O/k.o $O/w.o $O/ab.o $O/g.o $O/c.o $O/id.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/bin/lib_ab${NAME:+_$NAME}.so $O/k.o $O/w.o $O/ab.o $O/g.o $O/m.o $O/c.o $O/id.o
 echo "tools/bin/lib_ab${NAME:+_$NAME}.so"

@@ -7,6 +7,7 @@
 
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -172,6 +173,152 @@ void test_partition() {
     std::printf("ok   partition (no wire crosses devices; D = 1, 2, 3, 8)\n");
 }
 
+// a circuit on plain booleans: every wire's value
+std::vector<bool> eval_bools(size_t n_in, const std::vector<uint8_t> &ops, const std::vector<uint32_t> &a,
+                             const std::vector<uint32_t> &b, const std::vector<bool> &in) {
+    std::vector<bool> w(in.begin(), in.begin() + n_in);
+    for (size_t g = 0; g < ops.size(); g++) {
+        const bool x = w[a[g]], y = ops[g] <= TFHE_GATE_ORYN ? (bool)w[b[g]] : false;
+        switch (ops[g]) {
+        case TFHE_GATE_NAND: w.push_back(!(x && y)); break;
+        case TFHE_GATE_OR: w.push_back(x || y); break;
+        case TFHE_GATE_AND: w.push_back(x && y); break;
+        case TFHE_GATE_XOR: w.push_back(x != y); break;
+        case TFHE_GATE_XNOR: w.push_back(x == y); break;
+        case TFHE_GATE_NOR: w.push_back(!(x || y)); break;
+        case TFHE_GATE_ANDNY: w.push_back(!x && y); break;
+        case TFHE_GATE_ANDYN: w.push_back(x && !y); break;
+        case TFHE_GATE_ORNY: w.push_back(!x || y); break;
+        case TFHE_GATE_ORYN: w.push_back(x || !y); break;
+        case TFHE_GATE_NOT: w.push_back(!x); break;
+        default: w.push_back(x); break;  // TFHE_GATE_COPY
+        }
+    }
+    return w;
+}
+
+// split_circuit of `d` under the placement `dev`: every sub-circuit is a valid circuit, every
+// output of the whole circuit comes from exactly one of them, and on plain booleans (all
+// assignments of up to 10 inputs, else 64 of them) the re-assembled outputs equal the whole's.
+void check_split(const char *what, const Dag &d, const std::vector<uint32_t> &dev, size_t D) {
+    const auto sub = tfhe::split_circuit(d.n_in, d.gates(), d.ops.data(), d.a.data(), d.b.data(), d.outs.size(),
+                                         d.outs.data(), dev, D);
+    expect(sub.size() == D, what, "one sub-circuit per device");
+    std::vector<int> covered(d.outs.size(), 0);
+    size_t gates = 0;
+    for (size_t k = 0; k < sub.size(); k++) {
+        const tfhe::SubCircuit &s = sub[k];
+        gates += s.ops.size();
+        expect(s.in_a.size() == s.ops.size() && s.in_b.size() == s.ops.size() && s.out_index.size() == s.out_wires.size(),
+               what, "sub-circuit array lengths");
+        expect(!tfhe::check_circuit(s.inputs.size(), s.ops.size(), s.ops.data(), s.in_a.data(), s.in_b.data(),
+                                    s.out_wires.size(), s.out_wires.data()),
+               what, "sub-circuit passes check_circuit");
+        for (uint32_t w : s.inputs) expect(w < d.n_in, what, "sub-circuit input is a primary input");
+        for (uint32_t o : s.out_index)
+            if (o < covered.size()) covered[o]++;
+            else expect(false, what, "out_index out of range");
+    }
+    expect(gates == d.gates(), what, "every gate on one device");
+    for (int c : covered) expect(c == 1, what, "every output from exactly one device");
+    const size_t cases = d.n_in <= 10 ? (size_t)1 << d.n_in : 64;
+    Lcg r{d.n_in * 977 + d.gates()};
+    for (size_t t = 0; t < cases; t++) {
+        std::vector<bool> in(d.n_in);
+        for (size_t i = 0; i < d.n_in; i++) in[i] = d.n_in <= 10 ? (t >> i) & 1 : r.next(2) != 0;
+        const std::vector<bool> whole = eval_bools(d.n_in, d.ops, d.a, d.b, in);
+        std::vector<int> got(d.outs.size(), -1);
+        for (const tfhe::SubCircuit &s : sub) {
+            std::vector<bool> sin(s.inputs.size());
+            for (size_t i = 0; i < s.inputs.size(); i++) sin[i] = in[s.inputs[i]];
+            const std::vector<bool> w = eval_bools(s.inputs.size(), s.ops, s.in_a, s.in_b, sin);
+            for (size_t k = 0; k < s.out_wires.size(); k++) got[s.out_index[k]] = w[s.out_wires[k]];
+        }
+        bool same = true;
+        for (size_t o = 0; o < d.outs.size(); o++) same = same && got[o] == (int)whole[d.outs[o]];
+        expect(same, what, "re-assembled outputs equal the whole circuit's");
+    }
+}
+
+void test_split_circuit() {
+    // inputs a0 a1 b0 b1 cin (0-4) and x0..x7 (5-12): a 2-bit ripple adder, then four independent gates
+    Dag d;
+    d.n_in = 13;
+    auto gate = [&](uint8_t op, uint32_t a, uint32_t b) {
+        d.ops.push_back(op);
+        d.a.push_back(a);
+        d.b.push_back(b);
+        return (uint32_t)(d.n_in + d.gates() - 1);
+    };
+    uint32_t carry = 4;
+    for (uint32_t i = 0; i < 2; i++) {  // full adder: s = a ^ b ^ c, c' = (a & b) | (c & (a ^ b))
+        const uint32_t x = gate(TFHE_GATE_XOR, i, 2 + i), s = gate(TFHE_GATE_XOR, x, carry);
+        const uint32_t g1 = gate(TFHE_GATE_AND, i, 2 + i), g2 = gate(TFHE_GATE_AND, carry, x);
+        carry = gate(TFHE_GATE_OR, g1, g2);
+        d.outs.push_back(s);
+    }
+    d.outs.push_back(carry);
+    d.outs.push_back(gate(TFHE_GATE_NAND, 5, 6));
+    d.outs.push_back(gate(TFHE_GATE_ORNY, 7, 8));
+    d.outs.push_back(gate(TFHE_GATE_ANDYN, 9, 10));
+    d.outs.push_back(gate(TFHE_GATE_COPY, 11, 12));
+    for (size_t D : {1, 2, 3}) {
+        std::vector<uint32_t> dev;
+        tfhe::partition_gates(d.n_in, d.gates(), d.ops.data(), d.a.data(), d.b.data(), D, dev);
+        check_split("split: adder + 4 gates", d, dev, D);
+        if (D == 3) {  // the adder (10 gates) whole on one device, the four gates on the other two
+            std::vector<size_t> n(D, 0);
+            for (uint32_t x : dev) n[x]++;
+            expect(n[dev[0]] == 10, "split: adder + 4 gates", "the adder stays whole");
+        }
+    }
+    // an output that is a primary input comes from device 0, which here has no gate; device 2 has none either
+    Dag e;
+    e.n_in = 3;
+    e.ops = {TFHE_GATE_AND, TFHE_GATE_XOR};
+    e.a = {0, 3};
+    e.b = {1, 1};
+    e.outs = {2, 4, 2, 0};
+    check_split("split: input as output", e, {1, 1}, 3);
+    const auto se = tfhe::split_circuit(e.n_in, 2, e.ops.data(), e.a.data(), e.b.data(), 4, e.outs.data(), {1, 1}, 3);
+    expect(se[0].ops.empty() && se[0].out_index == std::vector<uint32_t>({0, 2, 3}) &&
+               se[0].inputs == std::vector<uint32_t>({2, 0}) && se[0].out_wires == std::vector<uint32_t>({0, 0, 1}),
+           "split: input as output", "device 0 copies the primary inputs out");
+    expect(se[1].out_index == std::vector<uint32_t>({1}) && se[1].inputs == std::vector<uint32_t>({0, 1}),
+           "split: input as output", "device 1 has the gates and their inputs only");
+    expect(se[2].ops.empty() && se[2].inputs.empty() && se[2].out_wires.empty(), "split: input as output",
+           "a device without gates or outputs is empty");
+    // a NOT's in_b is ignored: here it names a gate of the other device and an input nobody reads
+    Dag f;
+    f.n_in = 3;
+    f.ops = {TFHE_GATE_AND, TFHE_GATE_NOT, TFHE_GATE_NOT, TFHE_GATE_OR};
+    f.a = {0, 1, 4, 5};
+    f.b = {1, 3, 2, 1};
+    f.outs = {3, 6};
+    check_split("split: NOT ignores in_b", f, {0, 1, 1, 1}, 2);
+    const auto sf = tfhe::split_circuit(f.n_in, 4, f.ops.data(), f.a.data(), f.b.data(), 2, f.outs.data(), {0, 1, 1, 1}, 2);
+    expect(sf[1].inputs == std::vector<uint32_t>({1}) && sf[1].in_b[0] == 0 && sf[1].in_b[1] == 0,
+           "split: NOT ignores in_b", "in_b of a NOT brings in no input and no wire");
+    std::printf("ok   split_circuit (adder + 4 gates over D = 1, 2, 3; input as output; empty device; NOT's in_b)\n");
+}
+
+void test_slice_of() {
+    for (size_t D : {1, 2, 8})
+        for (size_t B : {(size_t)0, (size_t)1, D - 1, D, D + 1, (size_t)1100}) {
+            const size_t per = (B + D - 1) / D;
+            size_t next = 0;
+            for (size_t d = 0; d < D; d++) {
+                const tfhe::Slice s = tfhe::slice_of(B, D, d);
+                expect(s.lo == next, "slice_of", "slices are contiguous and in device order");
+                expect(s.lo == std::min(B, d * per) && s.n == std::min(B, s.lo + per) - s.lo, "slice_of",
+                       "ceil(B/D) items per device");
+                next = s.lo + s.n;
+            }
+            expect(next == B, "slice_of", "the slices cover [0, B) exactly once");
+        }
+    std::printf("ok   slice_of (B in {0, 1, D-1, D, D+1, 1100}, D in {1, 2, 8})\n");
+}
+
 void test_key_file() {  // the smallest parameters params_ok takes
     tfhe_params p{1, 1024, 10, 1, 8, 3, 2, 0, 2.0e-5, 2.0e-8, 2.0e-5, 2.0e-8};
     const size_t bl = 4096, kl = 32768, bytes = 64 + 2 * 4096 + bl * 8 + kl * 4;
@@ -265,6 +412,8 @@ int main() {
     test_packing();
     test_rejections();
     test_partition();
+    test_split_circuit();
+    test_slice_of();
     test_key_file();
     test_lut();
     test_encrypt();

@@ -1,5 +1,6 @@
 // tfhe_cpu.cpp — the GPU-free half of the C ABI (include/tfhe_gpu.h): the tfhe_*
-// functions that take no context, and the circuit planner tfhe_gpu.cpp evaluates.
+// functions that take no context, and the circuit planner, partitioner and splitter
+// whose plans tfhe_gpu.cpp and tfhe_multi.cpp evaluate.
 // Plain C++17, no HIP: cpp/test_cpu.cpp runs it stand-alone, under the host sanitizers too.
 #include "tfhe_cpu.hpp"
 
@@ -264,6 +265,51 @@ void partition_gates(size_t n_inputs, size_t n_gates, const uint8_t *ops, const 
     }
     dev_of_gate.resize(n_gates);
     for (size_t g = 0; g < n_gates; g++) dev_of_gate[g] = dev_of_root[dsu.find((uint32_t)g)];
+}
+
+// The D sub-circuits of a placement (dev_of_gate: partition_gates' devices, no
+// gate-to-gate wire crossing them; the whole graph passed check_circuit).
+// Primary inputs are read-only, so each device gets its own copy of the ones
+// it reads.  Wires are renumbered: the device's inputs first (in the order it
+// first reads them), then its gates in the whole circuit's order.  An output
+// that is a primary input is copied out by device 0.
+std::vector<SubCircuit> split_circuit(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                                      const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
+                                      const std::vector<uint32_t> &dev_of_gate, size_t D) {
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    std::vector<SubCircuit> sub(D);
+    std::vector<std::vector<uint32_t>> input_id(D);  // per device: global input -> local id (or none)
+    auto wire_dev = [&](uint32_t w) { return w < n_inputs ? 0u : dev_of_gate[w - n_inputs]; };
+    auto use_input = [&](uint32_t d, uint32_t w) {
+        if (w >= n_inputs) return;
+        if (input_id[d].empty()) input_id[d].assign(n_inputs, NONE);
+        if (input_id[d][w] == NONE) {
+            input_id[d][w] = (uint32_t)sub[d].inputs.size();
+            sub[d].inputs.push_back(w);
+        }
+    };
+    for (size_t g = 0; g < n_gates; g++) {
+        use_input(dev_of_gate[g], in_a[g]);
+        if (ops[g] <= TFHE_GATE_ORYN) use_input(dev_of_gate[g], in_b[g]);
+    }
+    for (size_t o = 0; o < n_outputs; o++) use_input(wire_dev(out_wires[o]), out_wires[o]);
+    std::vector<uint32_t> local_gate(n_gates), gate_count(D, 0);
+    for (size_t g = 0; g < n_gates; g++) local_gate[g] = gate_count[dev_of_gate[g]]++;
+    auto id = [&](uint32_t d, uint32_t w) {
+        return w < n_inputs ? input_id[d][w] : (uint32_t)sub[d].inputs.size() + local_gate[w - n_inputs];
+    };
+    for (size_t g = 0; g < n_gates; g++) {
+        const uint32_t d = dev_of_gate[g];
+        sub[d].ops.push_back(ops[g]);
+        sub[d].in_a.push_back(id(d, in_a[g]));
+        sub[d].in_b.push_back(ops[g] <= TFHE_GATE_ORYN ? id(d, in_b[g]) : 0u);
+    }
+    for (size_t o = 0; o < n_outputs; o++) {
+        const uint32_t d = wire_dev(out_wires[o]);
+        sub[d].out_wires.push_back(id(d, out_wires[o]));
+        sub[d].out_index.push_back((uint32_t)o);
+    }
+    return sub;
 }
 
 }  // namespace tfhe

@@ -1,5 +1,5 @@
-// tfhe_cpu.hpp — what the GPU half of the C ABI (tfhe_gpu.cpp) calls in the
-// GPU-free half (tfhe_cpu.cpp: plain C++17, no HIP).  Not installed.
+// tfhe_cpu.hpp — what the GPU half of the C ABI (tfhe_gpu.cpp, tfhe_multi.cpp)
+// calls in the GPU-free half (tfhe_cpu.cpp: plain C++17, no HIP).  Not installed.
 #pragma once
 
 #include "tfhe_gpu.h"
@@ -47,5 +47,27 @@ const char *check_circuit(size_t n_inputs, size_t n_gates, const uint8_t *ops, c
                           const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires);
 void partition_gates(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b,
                      size_t D, std::vector<uint32_t> &dev_of_gate);
+
+// One device's part of a circuit placed by partition_gates: `inputs` are the
+// whole circuit's primary inputs it reads, in its own numbering; in_a / in_b /
+// out_wires use that numbering (inputs, then its gates); out_index[k] is the
+// whole circuit's output that its k-th output is.
+struct SubCircuit {
+    std::vector<uint32_t> inputs, in_a, in_b, out_wires, out_index;
+    std::vector<uint8_t> ops;
+};
+std::vector<SubCircuit> split_circuit(size_t n_inputs, size_t n_gates, const uint8_t *ops, const uint32_t *in_a,
+                                      const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
+                                      const std::vector<uint32_t> &dev_of_gate, size_t D);
+
+// Device d's contiguous slice of B items over D devices: ceil(B/D) each, the
+// last non-empty one ragged, the ones after it empty.
+struct Slice {
+    size_t lo, n;
+};
+inline Slice slice_of(size_t B, size_t D, size_t d) {
+    const size_t per = (B + D - 1) / D, lo = B < d * per ? B : d * per;
+    return {lo, (B < lo + per ? B : lo + per) - lo};
+}
 
 }  // namespace tfhe
