@@ -29,7 +29,10 @@
 extern "C" {
 #endif
 
-#define TFHE_GPU_ABI_VERSION 7  /* 7: tfhe_gpu_set_stream(NULL) = the null stream, tfhe_gpu_reset_stream;
+#define TFHE_GPU_ABI_VERSION 7  /* 7: tfhe_gpu_set_stream(NULL) = the null stream, tfhe_gpu_reset_stream; later
+                                   additions that change no existing entry keep the number: the leveled
+                                   entries (TRLWE / TRGSW encryption, selector sets, CMUX, table lookup,
+                                   sample extraction, tfhe_lookup_table_pack_bits) and TFHE_OPT_CMUX_FORM;
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -204,12 +207,18 @@ enum {
     TFHE_OPT_KEY_ROW_RMS_PPM = 16, /* read-only: the resident key's largest TRGSW row RMS / 2^31, in
                                      millionths (the admission's row-energy rule admits <= 650000;
                                      keygen'd keys ~600000; ABI 6) */
-    TFHE_OPT_HOST_STAGING = 17    /* host-buffer copies: 0 pageable hipMemcpyAsync from / to the caller's buffers
+    TFHE_OPT_HOST_STAGING = 17,   /* host-buffer copies: 0 pageable hipMemcpyAsync from / to the caller's buffers
                                      (default), 1 through per-device pinned staging (host memcpy + DMA).  Same
                                      words either way.  Measured: 8 concurrent shards'
                                      pageable copies 52.9 GB/s in total against 47.2 staged, and the one-card
                                      8-shard step 54.5 vs 56.6 ms, so staging is for hosts whose pageable
                                      copies serialise */
+    TFHE_OPT_CMUX_FORM = 18       /* table lookup's CMUX levels: 0 auto (default: the measured-faster form, which
+                                     is 2: 4.8 vs 9.6 ms per 1,024 lookups of a 256-entry table, DESIGN.md
+                                     §4.8), 1 one wavefront per CMUX, each reading its selector from L2, 2 where
+                                     a level has >= 4 pairs per query, workgroups of 4 CMUXes that stage their
+                                     shared selector's rows in LDS once.  Same words either way;
+                                     tfhe_gpu_last_kernels names what the last lookup ran */
 };
 enum { TFHE_STAGING_PAGEABLE = 0, TFHE_STAGING_PINNED = 1 };  /* TFHE_OPT_HOST_STAGING */
 /* TFHE_ARITH_AUTO (default): at the L=3 / Bg=2^6 sets the blind rotation
@@ -394,7 +403,58 @@ int tfhe_gpu_external_product_batch(tfhe_gpu_ctx *ctx, const double *trgsw_fft, 
 /* trgsw.identityKeySwitching (trgsw.zig:471-502): B TLWELv1 -> B TLWELv0. */
 int tfhe_gpu_key_switch_batch(tfhe_gpu_ctx *ctx, const uint32_t *in_lv1, uint32_t *out_lv0, size_t B);
 
+/* ---- Leveled operations: CMUX, TRGSW selectors, encrypted table lookup -----
+ * The leveled half of the reference (no bootstrap): a CMUX costs one external
+ * product where a gate costs n.  All of these run on the context's first
+ * device; CMUX, lookup and the encryptions need no cloud key and take the
+ * decomposition offset from the parameter set (key.zig:121-131).  They always
+ * run the reference's f64 expression trees (TFHE_OPT_ARITH does not apply: a
+ * caller's selector is not a keygen'd BK row).  TRLWELv1 = 2N words (a then b). */
+/* TRLWELv1.encryptF64 (trlwe.zig:30-64); item i uses DefaultPrng(seed0 + i); poly_mul on the device as keygen does. */
+int tfhe_gpu_trlwe_encrypt_batch(tfhe_gpu_ctx *ctx, const uint32_t *key_lv1, const double *mu /*B*N*/, double alpha,
+                                 uint64_t seed0, uint32_t *out /*B*2N*/, size_t B);
+/* TRLWELv1.decryptBool (trlwe.zig:85-98). */
+int tfhe_gpu_trlwe_decrypt_bool_batch(tfhe_gpu_ctx *ctx, const uint32_t *key_lv1, const uint32_t *ct,
+                                      uint8_t *bits /*B*N*/, size_t B);
+/* TRGSWLv1.encryptTorus + TRGSWLv1FFT.new (trgsw.zig:35-91); TRGSW s: a master DefaultPrng(seed0 + s) supplies
+ * its 2L row seeds in order.  out_fft: S*2L*2*N doubles in the reference layout (one BootstrappingKey entry each). */
+int tfhe_gpu_trgsw_encrypt_batch(tfhe_gpu_ctx *ctx, const uint32_t *key_lv1, const uint32_t *mu /*S*/, double alpha,
+                                 uint64_t seed0, double *out_fft, size_t S);
+/* S selectors (TRGSWLv1FFT, reference layout) resident on the device in the device layout of the
+ * bootstrapping key's rows.  S >= 1.  A set serves the context that loaded it. */
+typedef struct tfhe_gpu_trgsw_set tfhe_gpu_trgsw_set;
+int  tfhe_gpu_trgsw_set_load(tfhe_gpu_ctx *ctx, const double *trgsw_fft, size_t S, tfhe_gpu_trgsw_set **out);
+void tfhe_gpu_trgsw_set_destroy(tfhe_gpu_trgsw_set *set);
+/* trgsw.cmux (trgsw.zig:260-284): out[i] = cmux(in0[i], in1[i], set[sel[i]]) = ExtProd(set[sel[i]], in1[i] - in0[i])
+ * + in0[i], i.e. in1[i] where the selector encrypts 1.  sel is a HOST array in both variants; the _dev one takes
+ * the ciphertexts in HBM and is asynchronous on the context stream. */
+int tfhe_gpu_cmux_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *in0,
+                        const uint32_t *in1, uint32_t *out, size_t B);
+int tfhe_gpu_cmux_batch_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *sel,
+                            const uint32_t *in0_dev, const uint32_t *in1_dev, uint32_t *out_dev, size_t B);
+/* Table lookup by a CMUX tree (a chain of trgsw.cmux, trgsw.zig:260-284; "vertical packing"): table = 2^k
+ * TRLWELv1 shared by the Q queries; bit j of query q's address is set[addr[q*k + j]] (j = 0 the least significant:
+ * level j pairs entries 2i, 2i+1 of the previous level); out[q] = table[address_q], 2^k - 1 CMUXes per query, one
+ * launch per level.  1 <= k <= 12.  addr is a HOST array.  Queries run in chunks whose level buffers stay within
+ * a fixed 256 MB (+ half of it) of context scratch. */
+int tfhe_gpu_table_lookup_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                                const uint32_t *table, uint32_t *out_trlwe /*Q*2N*/, size_t Q);
+int tfhe_gpu_table_lookup_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                              const uint32_t *table_dev, uint32_t *out_dev, size_t Q);
+/* sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (host, each < N) of each of B TRLWELv1,
+ * TRLWE-major; key_switch != 0 adds identityKeySwitching (trgsw.zig:471-502; TFHE_ERR_NO_KEY without a cloud
+ * key): out = B*C*(N+1) or B*C*(n+1) words, ordinary TLWELv1 / TLWELv0 (gate inputs). */
+int tfhe_gpu_sample_extract_batch(tfhe_gpu_ctx *ctx, const uint32_t *trlwe, const uint32_t *coef, size_t C,
+                                  int key_switch, uint32_t *out, size_t B);
+int tfhe_gpu_sample_extract_dev(tfhe_gpu_ctx *ctx, const uint32_t *trlwe_dev, const uint32_t *coef, size_t C,
+                                int key_switch, uint32_t *out_dev, size_t B);
+
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
+/* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,
+ * key.zig:134-145): coefficient c < width = +1/8 if bit c of values[e] is set, else -1/8; coefficients >= width
+ * are 0.  width <= N (bits past 63 read as clear). */
+int tfhe_lookup_table_pack_bits(const tfhe_params *params, const uint64_t *values, size_t entries, uint32_t width,
+                                uint32_t *table /*entries*2N*/);
 /* SecretKey.new (key.zig:41-57) from DefaultPrng(seed): n lv0 bits, then N lv1 bits. */
 int tfhe_secret_key_new(const tfhe_params *params, uint64_t seed, uint32_t *key_lv0, uint32_t *key_lv1);
 /* TLWELv0.encryptBool (tlwe.zig:52-55 -> encryptF64 :34-49); item i uses

@@ -9,12 +9,16 @@
 //                        batchNand ... batchXnor — placeholders in the reference, implemented here)
 //   proxy_reenc.zig   -> tfhe::PublicKeyLv0, tfhe::ProxyReencryptionKey, tfhe::HipReencryptor
 //                        (reencryptTLWELv0 on the GPU)
+//   trlwe.zig         -> tfhe::TRLWELv1 (encryptF64 / encryptBool / decryptBool, sampleExtractIndex)
+//   trgsw.zig         -> tfhe::TRGSWLv1FFT::encryptTorus (encryptTorus + TRGSWLv1FFT.new), tfhe::cmux,
+//                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
 #pragma once
 
 #include <tfhe_gpu.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -239,6 +243,10 @@ class CloudKey {
               "CloudKey.generate", ck.ctx());
         return {std::move(sk), std::move(ck)};
     }
+    // CloudKey.newNoKsk (key.zig:80-89): no bootstrapping or key-switching key; what the leveled
+    // operations (cmux, TableLookup, the TRLWE / TRGSW encryptions) need, the decomposition offset,
+    // comes from the parameter set.
+    static CloudKey newNoKsk(const tfhe_params &p, int device = 0) { return CloudKey(p, device); }
     int numDevices() const { return tfhe_gpu_num_devices(ctx()); }
     void save(const std::string &path) const {
         check(tfhe_gpu_save_cloud_key(ctx(), path.c_str()), "CloudKey.save", ctx());
@@ -262,6 +270,120 @@ class CloudKey {
     }
     tfhe_params p_{};
     std::unique_ptr<tfhe_gpu_ctx, Del> ctx_;
+};
+
+// trlwe.zig:15-162.  Polynomial products run on the GPU of `ck`'s context (the reference passes an FFT plan).
+struct TRLWELv1 {
+    std::vector<Torus> p;  // a[N] then b[N]
+    TRLWELv1() : p(2 * 1024, 0u) {}
+    // encryptF64 (trlwe.zig:30-64) with DefaultPrng(seed)
+    static TRLWELv1 encryptF64(const std::vector<double> &mu, double alpha, const std::vector<Torus> &key_lv1,
+                               const CloudKey &ck, uint64_t seed) {
+        TRLWELv1 ct;
+        if (mu.size() != ck.params().N) throw Error(TFHE_ERR_INVALID, "TRLWELv1.encryptF64: N plaintext values");
+        check(tfhe_gpu_trlwe_encrypt_batch(ck.ctx(), key_lv1.data(), mu.data(), alpha, seed, ct.p.data(), 1),
+              "TRLWELv1.encryptF64", ck.ctx());
+        return ct;
+    }
+    // encryptBool (trlwe.zig:67-79): +-1/8 per coefficient
+    static TRLWELv1 encryptBool(const std::vector<bool> &bits, double alpha, const std::vector<Torus> &key_lv1,
+                                const CloudKey &ck, uint64_t seed) {
+        std::vector<double> mu(bits.size());
+        for (size_t i = 0; i < bits.size(); i++) mu[i] = bits[i] ? 0.125 : -0.125;
+        return encryptF64(mu, alpha, key_lv1, ck, seed);
+    }
+    std::vector<bool> decryptBool(const std::vector<Torus> &key_lv1, const CloudKey &ck) const {  // trlwe.zig:85-98
+        std::vector<uint8_t> v(ck.params().N);
+        check(tfhe_gpu_trlwe_decrypt_bool_batch(ck.ctx(), key_lv1.data(), p.data(), v.data(), 1), "TRLWELv1.decryptBool",
+              ck.ctx());
+        return std::vector<bool>(v.begin(), v.end());
+    }
+    // sampleExtractIndex (trlwe.zig:146-162): the TLWELv1 (N + 1 words) of coefficient k
+    std::vector<Torus> sampleExtractIndex(uint32_t k, const CloudKey &ck) const {
+        std::vector<Torus> out(ck.params().N + 1);
+        check(tfhe_gpu_sample_extract_batch(ck.ctx(), p.data(), &k, 1, 0, out.data(), 1), "sampleExtractIndex", ck.ctx());
+        return out;
+    }
+};
+
+// Selectors resident in HBM (tfhe_gpu_trgsw_set): S TRGSWLv1FFT in the reference layout, 2L*2*N doubles each.
+class TrgswSet {
+  public:
+    TrgswSet(const CloudKey &ck, const std::vector<double> &trgsw_fft, size_t S) : size_(S) {
+        tfhe_gpu_trgsw_set *h = nullptr;
+        const tfhe_params &p = ck.params();
+        if (trgsw_fft.size() != S * 2 * p.L * 2 * p.N) throw Error(TFHE_ERR_INVALID, "TrgswSet: S*2L*2*N doubles");
+        check(tfhe_gpu_trgsw_set_load(ck.ctx(), trgsw_fft.data(), S, &h), "trgsw_set_load", ck.ctx());
+        set_.reset(h, tfhe_gpu_trgsw_set_destroy);
+    }
+    const tfhe_gpu_trgsw_set *get() const { return set_.get(); }
+    size_t size() const { return size_; }
+
+  private:
+    std::shared_ptr<tfhe_gpu_trgsw_set> set_;
+    size_t size_ = 0;
+};
+
+// trgsw.zig:75-91: a TRGSW in the frequency domain; here also resident on the GPU as a set of one.
+struct TRGSWLv1FFT {
+    std::vector<double> fft;  // [2L][2][N], trgsw.zig:75-77
+    std::shared_ptr<TrgswSet> resident;
+    // TRGSWLv1.encryptTorus (trgsw.zig:35-71) + TRGSWLv1FFT.new (:81-91); DefaultPrng(seed) supplies the row seeds
+    static TRGSWLv1FFT encryptTorus(Torus mu, double alpha, const std::vector<Torus> &key_lv1, const CloudKey &ck,
+                                    uint64_t seed) {
+        TRGSWLv1FFT t;
+        const tfhe_params &p = ck.params();
+        t.fft.assign((size_t)2 * p.L * 2 * p.N, 0.0);
+        check(tfhe_gpu_trgsw_encrypt_batch(ck.ctx(), key_lv1.data(), &mu, alpha, seed, t.fft.data(), 1),
+              "TRGSWLv1.encryptTorus", ck.ctx());
+        t.resident = std::make_shared<TrgswSet>(ck, t.fft, 1);
+        return t;
+    }
+};
+
+// trgsw.cmux (trgsw.zig:260-284): if cond == 0 then in1 else in2.
+inline TRLWELv1 cmux(const TRLWELv1 &in1, const TRLWELv1 &in2, const TRGSWLv1FFT &cond, const CloudKey &ck) {
+    TRLWELv1 out;
+    const uint32_t sel = 0;
+    check(tfhe_gpu_cmux_batch(ck.ctx(), cond.resident->get(), &sel, in1.p.data(), in2.p.data(), out.p.data(), 1), "cmux",
+          ck.ctx());
+    return out;
+}
+
+// A table of 2^k TRLWELv1 addressed by k TRGSW-encrypted bits per query (tfhe_gpu_table_lookup_batch: a tree
+// of trgsw.cmux), and the extraction of its outputs' coefficients as gate inputs.
+struct TableLookup {
+    std::vector<Torus> table;  // 2^k x 2N
+    uint32_t k = 0;
+    // entry e = values[e]'s low `width` bits as +-1/8 coefficients of a trivial TRLWE (tfhe_lookup_table_pack_bits)
+    static TableLookup fromBits(const tfhe_params &p, const std::vector<uint64_t> &values, uint32_t width) {
+        TableLookup t;
+        while (((size_t)1 << t.k) < values.size()) t.k++;
+        if (values.size() != (size_t)1 << t.k || t.k < 1) throw Error(TFHE_ERR_INVALID, "TableLookup: 2^k entries, k >= 1");
+        t.table.assign(values.size() * 2 * p.N, 0u);
+        check(tfhe_lookup_table_pack_bits(&p, values.data(), values.size(), width, t.table.data()), "pack_bits");
+        return t;
+    }
+    // addr[q * k + j]: the selector of `set` that encrypts bit j (least significant first) of query q's address
+    std::vector<TRLWELv1> lookup(const CloudKey &ck, const TrgswSet &set, const std::vector<uint32_t> &addr) const {
+        const size_t Q = addr.size() / k, w = 2 * (size_t)ck.params().N;
+        std::vector<Torus> out(Q * w);
+        check(tfhe_gpu_table_lookup_batch(ck.ctx(), set.get(), addr.data(), k, table.data(), out.data(), Q), "table_lookup",
+              ck.ctx());
+        std::vector<TRLWELv1> r(Q);
+        for (size_t q = 0; q < Q; q++) std::copy(out.begin() + q * w, out.begin() + (q + 1) * w, r[q].p.begin());
+        return r;
+    }
+    // coefficients coef[] of one output as TLWELv0 (sampleExtractIndex + identityKeySwitching; needs the cloud key)
+    static std::vector<TLWELv0> extractBits(const CloudKey &ck, const TRLWELv1 &ct, const std::vector<uint32_t> &coef) {
+        const size_t w = ck.params().n + 1;
+        std::vector<Torus> out(coef.size() * w);
+        check(tfhe_gpu_sample_extract_batch(ck.ctx(), ct.p.data(), coef.data(), coef.size(), 1, out.data(), 1),
+              "sample_extract", ck.ctx());
+        std::vector<TLWELv0> r(coef.size(), TLWELv0(ck.params().n));
+        for (size_t c = 0; c < coef.size(); c++) std::copy(out.begin() + c * w, out.begin() + (c + 1) * w, r[c].p.begin());
+        return r;
+    }
 };
 
 // reencryptTLWELv0 (proxy_reenc.zig:267-306) on the GPU: the key is uploaded once to HBM; a

@@ -583,6 +583,23 @@ int tfhe_lut_generate_full(const tfhe_params *p, uint32_t m, const uint32_t *val
     return TFHE_OK;
 }
 
+// Table entries for tfhe_gpu_table_lookup_*: entry e as a trivial TRLWELv1 (a = 0) whose
+// coefficient c < width carries bit c of values[e] as +-1/8 (f64ToTorus(+-0.125), the gates'
+// plaintexts, gates.zig:48-121); bits past 63 read as clear.
+int tfhe_lookup_table_pack_bits(const tfhe_params *p, const uint64_t *values, size_t entries, uint32_t width,
+                                uint32_t *table) {
+    std::string why;
+    if (!params_ok(p, why) || (entries && (!values || !table)) || width > p->N) return TFHE_ERR_INVALID;
+    const size_t N = p->N;
+    const uint32_t plus = host::f64_to_torus(0.125), minus = host::f64_to_torus(-0.125);
+    for (size_t e = 0; e < entries; e++) {
+        uint32_t *t = table + e * 2 * N;
+        std::memset(t, 0, 2 * N * sizeof(uint32_t));
+        for (uint32_t c = 0; c < width; c++) t[N + c] = c < 64 && ((values[e] >> c) & 1u) ? plus : minus;
+    }
+    return TFHE_OK;
+}
+
 int tfhe_fft_tables(uint32_t N, int source, double *twist_re, double *twist_im, double *stage_re, double *stage_im) {
     if (N < 4 || (N & (N - 1)) || (source != TFHE_TWIDDLES_GLIBC && source != TFHE_TWIDDLES_FDLIBM))
         return TFHE_ERR_INVALID;

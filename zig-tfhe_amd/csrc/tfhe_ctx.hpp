@@ -157,6 +157,7 @@ struct Device {
     DevBuf s_wires, s_cidx, s_cops;  // circuit evaluator: wire table, gather indices, op codes
     DevBuf s_ties;                   // near-tie flags (KParams::tie_flags), one byte per item, zero between launches
     DevBuf s_kspart;                 // gemm key switch: the K splits' partial sums
+    DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
     DevPtr<uint32_t> d_ksk_gemm;     // gemm key switch: the MFMA-layout KSK (ks_gemm_bytes), built from d_ksk
     bool ksk_gemm_ok = false;        // d_ksk_gemm matches d_ksk
     Event level_ev;                  // level-split circuits: this device's slice of a level is computed
@@ -269,7 +270,11 @@ enum RunKind : int {
     RUN_NO_KEYSWITCH = 2,  // sampleExtractIndex2, n+1 words (vanilla.zig:58-69)
 };
 
-// ---- tfhe_gpu.cpp, for tfhe_multi.cpp ------------------------------------------
+// ---- tfhe_gpu.cpp, for tfhe_multi.cpp and tfhe_leveled.cpp -----------------------
+int ensure(Device &d, DevBuf &b, size_t bytes);                       // device scratch of at least `bytes`
+int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes);       // host -> `buf`, async on the device's stream
+DevTables tables(const Device &d);
+int ks_gemm_args(Device &d, size_t B, KsGemm &G);                     // the gemm key switch's buffers for B items
 int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint32_t *tv_b);
 int key_fingerprint(Device &d, uint64_t &bk, uint64_t &ksk);
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b, const uint32_t *testvec_dev,

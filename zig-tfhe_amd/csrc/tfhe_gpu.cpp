@@ -2,7 +2,8 @@
 // key residency, batch entry points and seeded key generation.  Host code;
 // all bootstrap arithmetic runs in tfhe_kernels.hip.  The functions that take
 // no context, and the circuit planner, are in tfhe_cpu.cpp (no HIP); what only
-// a context over several devices runs is in tfhe_multi.cpp.
+// a context over several devices runs is in tfhe_multi.cpp; the leveled entry
+// points (CMUX, selector sets, table lookup) are in tfhe_leveled.cpp.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -30,7 +31,7 @@ static int create_fail(int code, const std::string &msg) {
     return code;
 }
 
-static int ensure(Device &d, DevBuf &b, size_t bytes) {
+int ensure(Device &d, DevBuf &b, size_t bytes) {
     if (b.bytes >= bytes) return TFHE_OK;
     b.bytes = 0;
     size_t want = std::max<size_t>(bytes, 4096);
@@ -40,7 +41,7 @@ static int ensure(Device &d, DevBuf &b, size_t bytes) {
     return TFHE_OK;
 }
 
-static DevTables tables(const Device &d) {
+DevTables tables(const Device &d) {
     return DevTables{d.d_twist, d.d_tw, {d.twa[0], d.twa[1], d.twa[2], d.twa[3]}};
 }
 
@@ -83,7 +84,7 @@ int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint3
 // (ks_use_gemm): the MFMA-layout KSK, rebuilt on the stream after a key change,
 // and the partial sums.  G stays empty for the other forms (launch_key_switch
 // ignores it).
-static int ks_gemm_args(Device &d, size_t B, KsGemm &G) {
+int ks_gemm_args(Device &d, size_t B, KsGemm &G) {
     G = KsGemm();
     if (!ks_use_gemm(d.opts, d.K.iks_t, d.K.basebit, B, nullptr)) return TFHE_OK;
     if (!d.d_ksk_gemm) {
@@ -169,7 +170,7 @@ constexpr size_t STAGE_FLOOR = (size_t)1 << 20;  // the staging arenas start at 
 // pageable copies are faster).  The arena is reused from
 // offset 0 after every synchronisation of the stream (d2h_sync); when it is full the stream
 // is synchronised first, so no copy in flight ever reads overwritten bytes.
-static int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes) {
+int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes) {
     int rc = ensure(d, buf, bytes);
     if (rc) return rc;
     if (!staged(d) || !bytes) {
@@ -1188,6 +1189,7 @@ static bool option_ok(const Device &d, int key, int64_t v, std::string &why) {
     case TFHE_OPT_HOST_PIPELINE: ok = v == 0 || v == 1; break;
     case TFHE_OPT_CIRCUIT_SPLIT: ok = v >= 0 && v <= 2; break;
     case TFHE_OPT_HOST_STAGING: ok = v == TFHE_STAGING_PAGEABLE || v == TFHE_STAGING_PINNED; break;
+    case TFHE_OPT_CMUX_FORM: ok = v >= 0 && v <= 2; break;
     case TFHE_OPT_TWIDDLES:
         ok = v == TFHE_TWIDDLES_GLIBC || v == TFHE_TWIDDLES_FDLIBM;
         // tfhe_gpu_keygen transformed the resident BK with the current tables:
@@ -1221,6 +1223,7 @@ static int apply_option(Device &d, int key, int64_t v) {
     case TFHE_OPT_ARITH: o.arith_strict = v == TFHE_ARITH_REFERENCE ? 1 : v == TFHE_ARITH_FUSED_FORCED ? 2 : 0; break;
     case TFHE_OPT_BR_SPIN_CAP: d.K.spin_cap = (uint32_t)v; break;
     case TFHE_OPT_HOST_PIPELINE: d.pipeline = v; break;
+    case TFHE_OPT_CMUX_FORM: o.cmux_form = (int)v; break;
     case TFHE_OPT_HOST_STAGING:
         if (d.stage_used) HIPCHK(d, hipStreamSynchronize(d.stream));  // nothing in flight from the arena
         d.stage_used = 0;
@@ -1271,6 +1274,7 @@ int tfhe_gpu_get_option(const tfhe_gpu_ctx *c, int key, int64_t *v) {
     case TFHE_OPT_HOST_PIPELINE: *v = d.pipeline; break;
     case TFHE_OPT_CIRCUIT_SPLIT: *v = c->circuit_split; break;
     case TFHE_OPT_HOST_STAGING: *v = d.host_staging; break;
+    case TFHE_OPT_CMUX_FORM: *v = o.cmux_form; break;
     default: return TFHE_ERR_INVALID;
     }
     return TFHE_OK;

@@ -87,6 +87,8 @@ struct LaunchOpts {
                            // to the same integers (the L=3 / Bg=2^6 sets); 2: fused even on
                            // a key the admission check refused (margin-guard tests only)
     int key_fused_ok = 1;  // the resident BK passed the fused arithmetic's admission check
+    int cmux_form = 0;     // table lookup's CMUX levels: 1 one wave per item; 0 auto and 2: the workgroup form where
+                           // 4 consecutive items share a selector (levels with >= 4 pairs per query)
 };
 // The fused arithmetic runs unless the reference's trees are requested, and only on
 // an admitted key unless forced (TFHE_OPT_ARITH, LaunchOpts::key_fused_ok).
@@ -201,5 +203,28 @@ hipError_t launch_absmax(const double *p, size_t count, unsigned long long *out,
 hipError_t launch_row_energy_max(const double *bkd, size_t rows, unsigned long long *out, hipStream_t s);
 hipError_t launch_bk_unpermute(const KParams &P, const double *bkd, double *bk_ref, size_t rows,
                                hipStream_t s);
+
+// ---- launchers (tfhe_kernels_leveled.hip); asynchronous on `s` ----------
+// One batch of CMUXes (trgsw.zig:260-284), device pointers: item g computes
+// out[g] = cmux(src0[i0[g]], src1[i1[g]], selector sel[g]) on TRLWELv1 of 2N
+// words; selectors in device layout (launch_bk_permute), 2L * 2048 doubles each.
+// i0 / i1 may be NULL: item g reads slot g.  P.offset is the decomposition offset.
+struct CmuxBatch {
+    const double *sel_rows = nullptr;
+    const uint32_t *sel = nullptr;
+    const uint32_t *src0 = nullptr, *i0 = nullptr;
+    const uint32_t *src1 = nullptr, *i1 = nullptr;
+    uint32_t *out = nullptr;
+    size_t B = 0;
+};
+// shared: the workgroup form (k_cmux_shared), whose 4 items g0 .. g0 + 3 (g0 a multiple of 4) must
+// have sel[g0] as their selector; else one independent wavefront per item (k_cmux).
+constexpr size_t CMUX_SHARED_ITEMS = 4;
+hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b, bool shared, hipStream_t s,
+                       const char **used = nullptr);
+// sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (device, each < N) of each
+// of B TRLWELv1: B * C TLWELv1 of N + 1 words, TRLWE-major
+hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,
+                                 hipStream_t s);
 
 }  // namespace tfhe

@@ -1,0 +1,217 @@
+// tfhe_kernels_leveled.hip — the leveled half of zig-tfhe on the device: CMUX
+// against caller-supplied TRGSW selectors (trgsw.zig:260-284) and
+// sampleExtractIndex at any coefficient (trlwe.zig:146-162).  Its own unit: the
+// bootstrap kernels' objects (tfhe_kernels.o, tfhe_kernels_whole.o), which
+// tfhe_gpu_build_id() hashes, do not change with it.  Same flags as theirs
+// (-ffp-contract=off: every f64 multiply and add rounds separately).
+//
+// Arithmetic: the reference's expression trees (FU = false, SMALL = false)
+// whatever TFHE_OPT_ARITH says.  A caller's selector is not a keygen'd BK row,
+// so the fused arithmetic's admission regime says nothing
+// about it; the near-tie counter and flags are not touched.
+#include "tfhe_device.hpp"
+
+namespace tfhe {
+
+// Waves (items) per workgroup of k_cmux.  Each wave exchanges its transforms
+// through a private 16 KB LDS buffer (wave_sync only, no workgroup barrier).
+// Registers, not LDS, set the occupancy (make resource-usage): at L = 3 the
+// kernel takes 256 VGPRs + 68 AGPRs without scratch, i.e. one wave per SIMD,
+// and capping it at 256 registers for two (__launch_bounds__(256, 2)) spills
+// 272 bytes per lane.  So one workgroup of 4 waves fills a CU (64 KB of its
+// 160 KB LDS); a wider workgroup could not be resident and would idle more
+// waves in a ragged tail.
+constexpr int CMUX_WAVES = 4;
+
+// out[g] = ExtProd(sel_rows[sel[g]], in1 - in0) + in0 with in0 = src0[i0[g]],
+// in1 = src1[i1[g]] (i0 / i1 NULL: g itself), one wavefront per item; lane t
+// owns coefficients t + 64m as in k_external_product.  tmp = in1 - in0 + offset
+// stays in registers, and the accumulators start from in0, so inverse_and_add's
+// `acc += ExtProd` is the CMUX add (tmp2 + in1 of trgsw.zig:277-281; wrapping
+// u32 adds commute).  Waves past B (the last workgroup's tail) return before
+// they read or write anything; nothing below is a workgroup barrier.
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_cmux(KParams P, DevTables TT,
+                                                          const double2 *__restrict__ sel_rows,
+                                                          const uint32_t *__restrict__ sel,
+                                                          const uint32_t *__restrict__ src0,
+                                                          const uint32_t *__restrict__ i0,
+                                                          const uint32_t *__restrict__ src1,
+                                                          const uint32_t *__restrict__ i1, uint32_t *__restrict__ out,
+                                                          size_t B) {
+    __shared__ C2 s_x[CMUX_WAVES][2 * 512];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), t = threadIdx.x & 63;
+    const size_t g = (size_t)blockIdx.x * CMUX_WAVES + w;
+    if (g >= B) return;
+    const uint32_t *x0 = src0 + (size_t)(i0 ? i0[g] : g) * 2048;
+    const uint32_t *x1 = src1 + (size_t)(i1 ? i1[g] : g) * 2048;
+    const double2 *row = sel_rows + (size_t)sel[g] * (2 * L * 1024);
+    RegTw T;
+    T.init(TT.tw, t);
+    C2 twl[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+    uint32_t tA[16], tB[16], accA[16], accB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        accA[m] = x0[t + 64 * m];
+        accB[m] = x0[1024 + t + 64 * m];
+        tA[m] = x1[t + 64 * m] - accA[m] + P.offset;
+        tB[m] = x1[1024 + t + 64 * m] - accB[m] + P.offset;
+    }
+    C2 fa[8], fb[8];
+    ext_pairs_global<L>(tA, tB, row, P.bgbit, T, twl, s_x[w], t, fa, fb);
+    uint32_t near = NEAR_NONE;
+    inverse_and_add<false, 1>(fa, fb, s_x[w], T, twl, t, accA, accB, near);
+    uint32_t *o = out + g * 2048;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        o[t + 64 * m] = accA[m];
+        o[1024 + t + 64 * m] = accB[m];
+    }
+}
+
+// Workgroup form for items that share their selector: the 4 waves' items
+// g0 .. g0 + 3 (g0 = 4 * blockIdx.x) all use selector sel[g0] (the launcher's
+// contract: the tree levels with at least 4 pairs per query).  The per-wave form
+// reads each item's 2L rows (96 KB at L = 3) from L2, about four times the
+// item's ciphertext traffic (3 x 8 KB); here the 256 threads stage every row
+// pair (32 KB) in LDS once and all four waves run the LDS MAC of the blind
+// rotation (mac_pair_lds) on it.  No DMA and no slot counters: each thread reads
+// its 8 x 16 B of a pair into registers, runs the pair's forward transforms,
+// meets a workgroup barrier (all waves are through the previous pair's MAC),
+// stores its piece into LDS, and a second barrier opens the MAC.  fmaInFd1024 accumulates from 0.0 here as in
+// the blind rotation (0.0 + x == x).  There is no ragged tail: launch_cmux
+// refuses a B that is not a multiple of 4 (a wave that left early would miss
+// the barriers; one kept in by a flag until a late return made hipcc spill
+// 2.6 KB per lane at L = 3).
+constexpr int CS_LDS_BK = 2048 * 16;
+template <int L, int RP = 0>
+DEV void ext_pairs_shared(const uint32_t *tA, const uint32_t *tB, const double2 *__restrict__ row,
+                          int bgbit, const RegTw &T, const C2 *twl, C2 *xb, int t, int tid, double2 *s_bk, C2 *fa,
+                          C2 *fb) {
+    if constexpr (RP < L) {
+        // This thread's 8 x 16 B of the pair, read before the forward transforms so that they hide
+        // the L2 latency (4.81 against 6.88 ms per 1,024 lookups without, profiles/
+        // lookup_ab_shared_prefetch.txt).  The address goes through an opaque asm: hipcc otherwise
+        // hoists all L pairs' loads to the top of the kernel and spills.  Plain doubles: an array
+        // of double2 is not split into registers here but promoted to LDS, 64 KB of it.
+        const double2 *src = row + (size_t)RP * 2048 + tid;
+        asm volatile("" : "+v"(src)::"memory");
+        double prx[8], pry[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const double2 v = src[256 * k];
+            prx[k] = v.x;
+            pry[k] = v.y;
+        }
+        C2 d[2][8];
+        forward_pair<L, RP, 1>(tA, tB, bgbit, T, twl, xb, t, d);
+        if (RP > 0) __syncthreads();  // every wave is through the previous pair's MAC
+#pragma unroll
+        for (int k = 0; k < 8; k++) s_bk[256 * k + tid] = make_double2(prx[k], pry[k]);
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        mac_pair_lds<false>(fa, fb, d[0], d[1], s_bk, t);
+        __builtin_amdgcn_sched_barrier(0);
+        ext_pairs_shared<L, RP + 1>(tA, tB, row, bgbit, T, twl, xb, t, tid, s_bk, fa, fb);
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_cmux_shared(KParams P, DevTables TT,
+                                                                 const double2 *__restrict__ sel_rows,
+                                                                 const uint32_t *__restrict__ sel,
+                                                                 const uint32_t *__restrict__ src0,
+                                                                 const uint32_t *__restrict__ i0,
+                                                                 const uint32_t *__restrict__ src1,
+                                                                 const uint32_t *__restrict__ i1,
+                                                                 uint32_t *__restrict__ out, size_t B) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[CS_LDS_BK + CMUX_WAVES * 2 * 512 * 16];
+    double2 *s_bk = reinterpret_cast<double2 *>(smem);
+    const int tid = threadIdx.x, t = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    C2 *s_x = reinterpret_cast<C2 *>(smem + CS_LDS_BK) + w * 2 * 512;
+    const size_t g0 = (size_t)blockIdx.x * CMUX_WAVES, g = g0 + w;  // g < B: B is a multiple of 4 (launch_cmux)
+    const double2 *row = sel_rows + (size_t)sel[g0] * (2 * L * 1024);
+    RegTw T;
+    T.init(TT.tw, t);
+    C2 twl[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+    const uint32_t *x0 = src0 + (size_t)(i0 ? i0[g] : g) * 2048;
+    const uint32_t *x1 = src1 + (size_t)(i1 ? i1[g] : g) * 2048;
+    uint32_t tA[16], tB[16], accA[16], accB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        accA[m] = x0[t + 64 * m];
+        accB[m] = x0[1024 + t + 64 * m];
+        tA[m] = x1[t + 64 * m] - accA[m] + P.offset;
+        tB[m] = x1[1024 + t + 64 * m] - accB[m] + P.offset;
+    }
+    C2 fa[8], fb[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        fa[q] = c2(0.0, 0.0);
+        fb[q] = c2(0.0, 0.0);
+    }
+    ext_pairs_shared<L>(tA, tB, row, P.bgbit, T, twl, s_x, t, tid, s_bk, fa, fb);
+    uint32_t near = NEAR_NONE;
+    inverse_and_add<false, 1>(fa, fb, s_x, T, twl, t, accA, accB, near);
+    uint32_t *o = out + g * 2048;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        o[t + 64 * m] = accA[m];
+        o[1024 + t + 64 * m] = accB[m];
+    }
+}
+
+// sampleExtractIndex(trlwe, k) (trlwe.zig:146-162) for k < N = 1024: block
+// b * C + c extracts coefficient coef[c] of TRLWE b into TLWELv1 b * C + c
+// (1025 words): p[i] = a[k - i] (i <= k), -a[N + k - i] (i > k), p[N] = b[k].
+__global__ __launch_bounds__(256) void k_sample_extract(const uint32_t *__restrict__ trlwe,
+                                                        const uint32_t *__restrict__ coef, unsigned C,
+                                                        uint32_t *__restrict__ out) {
+    const uint32_t *x = trlwe + (size_t)(blockIdx.x / C) * 2048;
+    const uint32_t k = coef[blockIdx.x % C];
+    uint32_t *o = out + (size_t)blockIdx.x * 1025;
+    for (uint32_t i = threadIdx.x; i < 1024; i += 256) o[i] = i <= k ? x[k - i] : 0u - x[1024 + k - i];
+    if (threadIdx.x == 0) o[1024] = x[1024 + k];
+}
+
+template <int L>
+static const char *cmux_launch(bool shared, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
+                               const CmuxBatch &b) {
+    const double2 *rows = reinterpret_cast<const double2 *>(b.sel_rows);
+    if (shared) {
+        hipLaunchKernelGGL(k_cmux_shared<L>, grid, block, 0, s, P, T, rows, b.sel, b.src0, b.i0, b.src1, b.i1, b.out, b.B);
+        return L == 1 ? "k_cmux_shared<1>" : L == 2 ? "k_cmux_shared<2>" : "k_cmux_shared<3>";
+    }
+    hipLaunchKernelGGL(k_cmux<L>, grid, block, 0, s, P, T, rows, b.sel, b.src0, b.i0, b.src1, b.i1, b.out, b.B);
+    return L == 1 ? "k_cmux<1>" : L == 2 ? "k_cmux<2>" : "k_cmux<3>";
+}
+
+hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b, bool shared, hipStream_t s,
+                       const char **used) {
+    if (b.B == 0) return hipSuccess;
+    if (shared && b.B % CMUX_WAVES != 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((b.B + CMUX_WAVES - 1) / CMUX_WAVES)), block(64 * CMUX_WAVES);
+    const char *name = "";
+    switch (P.L) {
+    case 1: name = cmux_launch<1>(shared, grid, block, s, P, T, b); break;
+    case 2: name = cmux_launch<2>(shared, grid, block, s, P, T, b); break;
+    case 3: name = cmux_launch<3>(shared, grid, block, s, P, T, b); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (used) *used = name;
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,
+                                 hipStream_t s) {
+    if (B == 0 || C == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sample_extract, dim3((unsigned)(B * C)), dim3(256), 0, s, trlwe, coef, (unsigned)C, out_lv1);
+    return hipGetLastError();
+}
+
+}  // namespace tfhe

@@ -1,0 +1,366 @@
+// tfhe_leveled.cpp — the leveled half of the C ABI (include/tfhe_gpu.h):
+// TRLWE / TRGSW encryption, resident selector sets, CMUX, table lookup by a
+// CMUX tree and sample extraction at any coefficient.  Host code; the
+// arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
+// tfhe_kernels.hip.  Everything here runs on the context's first device and,
+// but for the key switch after an extraction, needs no cloud key.
+#include "tfhe_gpu.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "host_math.hpp"
+#include "tfhe_ctx.hpp"
+
+using namespace tfhe;
+
+// S TRGSWLv1FFT resident on one device, in the device layout of the
+// bootstrapping key's rows (launch_bk_permute).
+struct tfhe_gpu_trgsw_set {
+    const tfhe_gpu_ctx *ctx = nullptr;  // the context that loaded it (identity only, never dereferenced)
+    tfhe_params P{};
+    size_t S = 0;
+    DevPtr<double> rows;  // S * 2L * 2048 doubles
+};
+
+namespace tfhe {
+
+// Bytes of the larger of the table lookup's two ping-pong level buffers (the
+// other is half of it): a chunk of queries is as many as keep level 0's outputs,
+// 2^(k-1) TRLWELv1 of 8 KB per query, within it.  k = 12: 16 queries per chunk.
+constexpr size_t LOOKUP_SCRATCH_CAP = (size_t)256 << 20;
+constexpr uint32_t LOOKUP_MAX_K = 12;
+constexpr size_t TRLWE_BYTES = 2048 * sizeof(uint32_t);
+
+template <class F>
+static int on_device0(tfhe_gpu_ctx *c, F f) {
+    return lift(c, 0, f(c->dev[0]));
+}
+
+// The kernels' parameter block with the parameter set's own decomposition
+// offset (key.zig:121-131), whether or not a cloud key (which carries one) is loaded.
+static KParams leveled_params(const Device &d) {
+    KParams K = d.K;
+    K.offset = decomposition_offset(d.P);
+    return K;
+}
+
+// TRLWELv1.encryptF64 (trlwe.zig:30-64) of R rows, row r from DefaultPrng(seeds[r]):
+// a uniform, b = gaussianTorus(f64ToTorus(mu), alpha) + a * s, the products on the
+// device (k_poly_mul) as in tfhe_gpu_keygen.  mu: R * N values, or NULL for zeros.
+// rows receives R TRLWELv1 (a then b).
+static int trlwe_encrypt_rows(Device &d, const uint32_t *key_lv1, const std::vector<uint64_t> &seeds, const double *mu,
+                              double alpha, uint32_t *rows) {
+    const size_t N = d.P.N, R = seeds.size();
+    std::vector<uint32_t> a_only(R * N);
+    for (size_t row = 0; row < R; row++) {
+        host::Rng r(seeds[row]);
+        uint32_t *a = rows + row * 2 * N, *b = a + N;
+        for (size_t x = 0; x < N; x++) a[x] = r.u32();
+        host::NormalDist nd(0.0, alpha);
+        for (size_t x = 0; x < N; x++) b[x] = host::gaussian_torus(mu ? host::f64_to_torus(mu[row * N + x]) : 0u, nd, r);
+        std::memcpy(a_only.data() + row * N, a, N * sizeof(uint32_t));
+    }
+    int rc = h2d(d, d.s_b, key_lv1, N * sizeof(uint32_t));
+    if (!rc) rc = h2d(d, d.s_a, a_only.data(), a_only.size() * sizeof(uint32_t));
+    if (!rc) rc = ensure(d, d.s_out, R * N * sizeof(uint32_t));
+    if (rc) return rc;
+    HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 0,
+                              d.s_out.as<uint32_t>(), R, d.stream));
+    std::vector<uint32_t> as(R * N);
+    rc = d2h_sync(d, as.data(), d.s_out.p, as.size() * sizeof(uint32_t));
+    if (rc) return rc;
+    for (size_t row = 0; row < R; row++) {
+        uint32_t *b = rows + row * 2 * N + N;
+        for (size_t x = 0; x < N; x++) b[x] += as[row * N + x];
+    }
+    return TFHE_OK;
+}
+
+// The set belongs to this context and its parameter set.
+static const char *set_mismatch(const tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set) {
+    if (set->ctx != c) return "the selector set was loaded on another context";
+    if (std::memcmp(&set->P, &c->P, sizeof(tfhe_params)) != 0) return "the selector set was loaded for another parameter set";
+    return nullptr;
+}
+
+// in0 / in1 / out: B TRLWELv1 each, host (dev = false: staged, synchronous) or device.
+static int cmux_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *in0, const uint32_t *in1,
+                   uint32_t *out, size_t B, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    int rc = h2d(d, d.s_cidx, sel, B * sizeof(uint32_t));
+    if (!rc && !dev) rc = h2d(d, d.s_a, in0, B * TRLWE_BYTES);
+    if (!rc && !dev) rc = h2d(d, d.s_b, in1, B * TRLWE_BYTES);
+    if (!rc && !dev) rc = ensure(d, d.s_out, B * TRLWE_BYTES);
+    if (rc) return rc;
+    CmuxBatch b;
+    b.sel_rows = set.rows;
+    b.sel = d.s_cidx.as<const uint32_t>();
+    b.src0 = dev ? in0 : d.s_a.as<const uint32_t>();
+    b.src1 = dev ? in1 : d.s_b.as<const uint32_t>();
+    b.out = dev ? out : d.s_out.as<uint32_t>();
+    b.B = B;
+    d.last_ks = "";
+    HIPCHK(d, launch_cmux(leveled_params(d), tables(d), b, /*shared*/ false, d.stream, &d.last_br));
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * TRLWE_BYTES);
+}
+
+// The CMUX tree (vertical packing): level j pairs entries 2i, 2i + 1 of level j - 1
+// (level 0: of the table) under address bit j, one launch per level; levels ping-pong
+// between s_lk_a (level 0, 2, ...) and s_lk_b, the last one writes the outputs.
+// Queries go in chunks that keep s_lk_a within LOOKUP_SCRATCH_CAP.  The selector and
+// gather indices of all levels go up once, in one array:
+//   sel[j][q][i] = addr[q k + j]  (i < 2^(k-1-j) pairs of query q at level j), all Q queries;
+//   level 0 reads table entries 2i, 2i + 1 (the table is shared by the queries);
+//   level j > 0 reads slots 2g, 2g + 1 of the previous level's buffer for its item g.
+static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
+                           const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    const size_t entries = (size_t)1 << k, cnt0 = entries / 2, cnt1 = cnt0 / 2;
+    const size_t chunk = std::min(Q, std::max<size_t>(1, LOOKUP_SCRATCH_CAP / (cnt0 * TRLWE_BYTES)));
+    std::vector<size_t> sel_at(k);
+    size_t words = 0;
+    for (uint32_t j = 0; j < k; j++) {
+        sel_at[j] = words;
+        words += Q * (cnt0 >> j);
+    }
+    const size_t l0a_at = words, l0b_at = l0a_at + chunk * cnt0, even_at = l0b_at + chunk * cnt0,
+                 odd_at = even_at + chunk * cnt1;
+    std::vector<uint32_t> idx(odd_at + chunk * cnt1);
+    for (uint32_t j = 0; j < k; j++) {
+        const size_t cnt = cnt0 >> j;
+        uint32_t *s = idx.data() + sel_at[j];
+        for (size_t q = 0; q < Q; q++) std::fill(s + q * cnt, s + (q + 1) * cnt, addr[q * k + j]);
+    }
+    for (size_t g = 0; g < chunk * cnt0; g++) {
+        idx[l0a_at + g] = (uint32_t)(2 * (g % cnt0));
+        idx[l0b_at + g] = (uint32_t)(2 * (g % cnt0) + 1);
+    }
+    for (size_t g = 0; g < chunk * cnt1; g++) {
+        idx[even_at + g] = (uint32_t)(2 * g);
+        idx[odd_at + g] = (uint32_t)(2 * g + 1);
+    }
+    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): idx may go
+    int rc = h2d(d, d.s_lk_idx, idx.data(), idx.size() * sizeof(uint32_t));
+    if (!rc && k > 1) rc = ensure(d, d.s_lk_a, chunk * cnt0 * TRLWE_BYTES);
+    if (!rc && k > 2) rc = ensure(d, d.s_lk_b, chunk * cnt1 * TRLWE_BYTES);
+    if (!rc && !dev) rc = h2d(d, d.s_a, table, entries * TRLWE_BYTES);
+    if (!rc && !dev) rc = ensure(d, d.s_out, Q * TRLWE_BYTES);
+    if (rc) return rc;
+    const uint32_t *didx = d.s_lk_idx.as<const uint32_t>();
+    const uint32_t *tab = dev ? table : d.s_a.as<const uint32_t>();
+    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
+    const KParams K = leveled_params(d);
+    const DevTables T = tables(d);
+    d.last_br = d.last_ks = "";
+    for (size_t q0 = 0; q0 < Q; q0 += chunk) {
+        const size_t nq = std::min(chunk, Q - q0);
+        const uint32_t *prev = tab;
+        for (uint32_t j = 0; j < k; j++) {
+            const size_t cnt = cnt0 >> j;
+            CmuxBatch b;
+            b.sel_rows = set.rows;
+            b.sel = didx + sel_at[j] + q0 * cnt;
+            b.src0 = b.src1 = prev;
+            b.i0 = didx + (j ? even_at : l0a_at);
+            b.i1 = didx + (j ? odd_at : l0b_at);
+            b.out = j + 1 == k ? res + q0 * 2048 : (j & 1) ? d.s_lk_b.as<uint32_t>() : d.s_lk_a.as<uint32_t>();
+            b.B = nq * cnt;
+            // the workgroup form where 4 consecutive items share their selector (>= 4 pairs per
+            // query; cnt is a power of two) unless TFHE_OPT_CMUX_FORM = 1 forces the per-wave form:
+            // measured faster, 4.8 vs 9.6 ms at Q = 1024, k = 8
+            const bool shared = d.opts.cmux_form != 1 && cnt >= CMUX_SHARED_ITEMS;
+            const char *name = "";
+            HIPCHK(d, launch_cmux(K, T, b, shared, d.stream, &name));
+            // last_kernels: the first level's form, then the last level's if it differs
+            if (q0 == 0 && j == 0) d.last_br = name;
+            else if (q0 == 0 && j + 1 == k && name != d.last_br) d.last_ks = name;
+            prev = b.out;
+        }
+    }
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, Q * TRLWE_BYTES);
+}
+
+static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *coef, size_t C, bool key_switch,
+                             uint32_t *out, size_t B, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    if (key_switch && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t items = B * C, wo = key_switch ? tlwe0_words(d.P) : (size_t)d.P.N + 1;
+    if (items == 0) return TFHE_OK;
+    int rc = h2d(d, d.s_cidx, coef, C * sizeof(uint32_t));
+    if (!rc && !dev) rc = h2d(d, d.s_a, trlwe, B * TRLWE_BYTES);
+    if (!rc && !dev) rc = ensure(d, d.s_out, items * wo * 4);
+    if (!rc && key_switch) rc = ensure(d, d.s_lv1, items * 1025 * 4 + KS_GEMM_INPUT_SLACK);
+    if (rc) return rc;
+    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
+    uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : res;
+    HIPCHK(d, launch_sample_extract(dev ? trlwe : d.s_a.as<const uint32_t>(), d.s_cidx.as<const uint32_t>(), C, lv1, B,
+                                    d.stream));
+    if (key_switch) {
+        KsGemm G;
+        if ((rc = ks_gemm_args(d, items, G))) return rc;
+        HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, res, items, d.stream, d.opts, &d.last_ks, &G));
+    }
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, items * wo * 4);
+}
+
+}  // namespace tfhe
+
+extern "C" {
+
+int tfhe_gpu_trlwe_encrypt_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const double *mu, double alpha, uint64_t seed0,
+                                 uint32_t *out, size_t B) {
+    if (!c || !key_lv1 || (B && (!mu || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        HIPCHK(d, hipSetDevice(d.device));
+        std::vector<uint64_t> seeds(B);
+        for (size_t i = 0; i < B; i++) seeds[i] = seed0 + i;
+        return trlwe_encrypt_rows(d, key_lv1, seeds, mu, alpha, out);
+    });
+}
+
+int tfhe_gpu_trlwe_decrypt_bool_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const uint32_t *ct, uint8_t *bits,
+                                      size_t B) {
+    if (!c || !key_lv1 || (B && (!ct || !bits))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        HIPCHK(d, hipSetDevice(d.device));
+        const size_t N = d.P.N;
+        std::vector<uint32_t> a_only(B * N), as(B * N);
+        for (size_t i = 0; i < B; i++) std::memcpy(a_only.data() + i * N, ct + i * 2 * N, N * sizeof(uint32_t));
+        int rc = h2d(d, d.s_b, key_lv1, N * sizeof(uint32_t));
+        if (!rc) rc = h2d(d, d.s_a, a_only.data(), a_only.size() * sizeof(uint32_t));
+        if (!rc) rc = ensure(d, d.s_out, B * N * sizeof(uint32_t));
+        if (rc) return rc;
+        HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 0,
+                                  d.s_out.as<uint32_t>(), B, d.stream));
+        rc = d2h_sync(d, as.data(), d.s_out.p, as.size() * sizeof(uint32_t));
+        if (rc) return rc;
+        for (size_t i = 0; i < B; i++)
+            for (size_t x = 0; x < N; x++) bits[i * N + x] = (int32_t)(ct[i * 2 * N + N + x] - as[i * N + x]) >= 0;
+        return TFHE_OK;
+    });
+}
+
+int tfhe_gpu_trgsw_encrypt_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const uint32_t *mu, double alpha,
+                                 uint64_t seed0, double *out_fft, size_t S) {
+    if (!c || !key_lv1 || (S && (!mu || !out_fft))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (S == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        HIPCHK(d, hipSetDevice(d.device));
+        const size_t N = d.P.N, L = d.P.L, R = S * 2 * L;
+        std::vector<uint64_t> seeds(R);
+        for (size_t s = 0; s < S; s++) {
+            host::Rng master(seed0 + s);
+            for (size_t r = 0; r < 2 * L; r++) seeds[s * 2 * L + r] = master.next();
+        }
+        std::vector<uint32_t> rows(R * 2 * N);
+        int rc = trlwe_encrypt_rows(d, key_lv1, seeds, nullptr, alpha, rows.data());
+        if (rc) return rc;
+        for (size_t s = 0; s < S; s++)
+            for (size_t l = 0; l < L; l++) {  // the gadget: a[0] of row l, b[0] of row L + l (trgsw.zig:35-71)
+                const uint32_t h = host::f64_to_torus(std::ldexp(1.0, -(int)((l + 1) * d.P.bgbit)));
+                rows[(s * 2 * L + l) * 2 * N] += mu[s] * h;
+                rows[(s * 2 * L + L + l) * 2 * N + N] += mu[s] * h;
+            }
+        // TRGSWLv1FFT.new (trgsw.zig:81-91): ifft of every a and b polynomial
+        rc = h2d(d, d.s_a, rows.data(), rows.size() * sizeof(uint32_t));
+        if (!rc) rc = ensure(d, d.s_tmp, R * 2 * N * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(d, launch_fft_forward(tables(d), d.s_a.as<const uint32_t>(), d.s_tmp.as<double>(), R * 2, d.stream));
+        return d2h_sync(d, out_fft, d.s_tmp.p, R * 2 * N * sizeof(double));
+    });
+}
+
+int tfhe_gpu_trgsw_set_load(tfhe_gpu_ctx *c, const double *trgsw_fft, size_t S, tfhe_gpu_trgsw_set **out) {
+    if (out) *out = nullptr;
+    if (!c || !trgsw_fft || !out || S == 0 || S > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "null argument or empty set");
+    std::unique_ptr<tfhe_gpu_trgsw_set> set(new tfhe_gpu_trgsw_set);
+    set->ctx = c;
+    set->P = c->P;
+    set->S = S;
+    const int rc = on_device0(c, [&](Device &d) -> int {
+        HIPCHK(d, hipSetDevice(d.device));
+        const size_t rows = S * 2 * d.P.L, bytes = rows * 2048 * sizeof(double);
+        int rc = h2d(d, d.s_tmp, trgsw_fft, bytes);
+        if (rc) return rc;
+        if (hipMalloc((void **)set->rows.make(d.device), bytes) != hipSuccess)
+            return fail(d, TFHE_ERR_OOM, "hipMalloc(selector set)");
+        HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), set->rows, rows, d.stream));
+        HIPCHK(d, hipStreamSynchronize(d.stream));
+        return TFHE_OK;
+    });
+    if (rc) return rc;
+    *out = set.release();
+    return TFHE_OK;
+}
+
+void tfhe_gpu_trgsw_set_destroy(tfhe_gpu_trgsw_set *set) { delete set; }
+
+static int cmux_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *in0,
+                      const uint32_t *in1, uint32_t *out, size_t B, bool dev) {
+    if (!c || !set || (B && (!sel || !in0 || !in1 || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    for (size_t i = 0; i < B; i++)
+        if (sel[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "selector index >= the set's size");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return cmux_on(d, *set, sel, in0, in1, out, B, dev); });
+}
+
+int tfhe_gpu_cmux_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *in0,
+                        const uint32_t *in1, uint32_t *out, size_t B) {
+    return cmux_entry(c, set, sel, in0, in1, out, B, false);
+}
+
+int tfhe_gpu_cmux_batch_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *in0_dev,
+                            const uint32_t *in1_dev, uint32_t *out_dev, size_t B) {
+    return cmux_entry(c, set, sel, in0_dev, in1_dev, out_dev, B, true);
+}
+
+static int lookup_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                        const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
+    if (!c || !set || !table || (Q && (!addr || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (k < 1 || k > LOOKUP_MAX_K) return fail(c, TFHE_ERR_INVALID, "table lookup: k outside 1..12");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (Q > 0xFFFFFFFFull >> k) return fail(c, TFHE_ERR_INVALID, "table lookup: too many queries");
+    for (size_t i = 0; i < Q * k; i++)
+        if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");
+    if (Q == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return table_lookup_on(d, *set, addr, k, table, out, Q, dev); });
+}
+
+int tfhe_gpu_table_lookup_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                                const uint32_t *table, uint32_t *out_trlwe, size_t Q) {
+    return lookup_entry(c, set, addr, k, table, out_trlwe, Q, false);
+}
+
+int tfhe_gpu_table_lookup_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                              const uint32_t *table_dev, uint32_t *out_dev, size_t Q) {
+    return lookup_entry(c, set, addr, k, table_dev, out_dev, Q, true);
+}
+
+static int extract_entry(tfhe_gpu_ctx *c, const uint32_t *trlwe, const uint32_t *coef, size_t C, int key_switch,
+                         uint32_t *out, size_t B, bool dev) {
+    if (!c || (C && !coef) || (B && C && (!trlwe || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    for (size_t i = 0; i < C; i++)
+        if (coef[i] >= c->P.N) return fail(c, TFHE_ERR_INVALID, "coefficient index >= N");
+    if (B * C > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "sample extract: too many outputs");
+    return on_device0(c, [&](Device &d) { return sample_extract_on(d, trlwe, coef, C, key_switch != 0, out, B, dev); });
+}
+
+int tfhe_gpu_sample_extract_batch(tfhe_gpu_ctx *c, const uint32_t *trlwe, const uint32_t *coef, size_t C, int key_switch,
+                                  uint32_t *out, size_t B) {
+    return extract_entry(c, trlwe, coef, C, key_switch, out, B, false);
+}
+
+int tfhe_gpu_sample_extract_dev(tfhe_gpu_ctx *c, const uint32_t *trlwe_dev, const uint32_t *coef, size_t C, int key_switch,
+                                uint32_t *out_dev, size_t B) {
+    return extract_entry(c, trlwe_dev, coef, C, key_switch, out_dev, B, true);
+}
+
+}  // extern "C"

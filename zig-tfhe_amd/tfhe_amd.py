@@ -24,11 +24,11 @@ LIB_PATH = os.environ.get("TFHE_GPU_LIB") or os.path.join(HERE, "lib", "libtfhe_
 # tfhe_gpu_set_option keys / values (include/tfhe_gpu.h TFHE_OPT_*, TFHE_TWIDDLES_*)
 OPTIONS = {"br_form": 1, "br_loader": 2, "ks_form": 3, "ks_narrow": 4, "ks_item_groups": 5, "ks_sel_items": 6,
            "circuit_pack": 7, "twiddles": 8, "arith": 9, "br_sync": 10, "br_spin_cap": 11, "host_pipeline": 12,
-           "circuit_split": 13, "host_staging": 17}
+           "circuit_split": 13, "host_staging": 17, "cmux_form": 18}
 READONLY_OPTIONS = {"fused_admitted": 14, "level_issue_us": 15, "key_row_rms_ppm": 16}  # tfhe_gpu_get_option only
 OPTION_DEFAULTS = {"br_form": 0, "br_loader": 1, "ks_form": 3, "ks_narrow": 0, "ks_item_groups": 0,
                    "ks_sel_items": 8, "circuit_pack": 1, "twiddles": 0, "arith": 0, "br_sync": 1, "br_spin_cap": 0,
-                   "host_pipeline": 0, "circuit_split": 0, "host_staging": 0}
+                   "host_pipeline": 0, "circuit_split": 0, "host_staging": 0, "cmux_form": 0}
 # status codes (include/tfhe_gpu.h TFHE_ERR_*)
 ERR_INVALID, ERR_HIP, ERR_NO_KEY, ERR_OOM, ERR_IO, ERR_DEVICE = -1, -2, -3, -4, -5, -6
 # 2 split, 4 pair: removed (round 4); 6 duo, 7 wide2: A/B libraries only (tools/ab/, round 5); 5 octo: L = 1
@@ -37,6 +37,7 @@ BUILD_PRODUCT, BUILD_AB = 0, 1  # tfhe_gpu_build_kind
 TWIDDLES_GLIBC, TWIDDLES_FDLIBM = 0, 1
 ARITH_AUTO, ARITH_REFERENCE, ARITH_FUSED_FORCED = 0, 1, 2
 STAGING_PAGEABLE, STAGING_PINNED = 0, 1  # TFHE_OPT_HOST_STAGING
+CMUX_AUTO, CMUX_PER_WAVE, CMUX_SHARED = 0, 1, 2  # TFHE_OPT_CMUX_FORM
 
 # gate op codes, include/tfhe_gpu.h TFHE_GATE_* (gates.zig:48-121)
 NAND, OR, AND, XOR, XNOR, NOR, ANDNY, ANDYN, ORNY, ORYN = range(10)
@@ -158,6 +159,19 @@ _SIGS = {
                                                C.c_uint32, C.c_uint64, u32p]),
     "tfhe_reenc_key_gen_asymmetric": (C.c_int, [C.POINTER(TfheParams), u32p, u32p, C.c_size_t, C.c_double,
                                                 C.c_uint32, C.c_uint32, C.c_uint64, u32p]),
+    "tfhe_gpu_trlwe_encrypt_batch": (C.c_int, [vp, u32p, f64p, C.c_double, C.c_uint64, u32p, C.c_size_t]),
+    "tfhe_gpu_trlwe_decrypt_bool_batch": (C.c_int, [vp, u32p, u32p, u8p, C.c_size_t]),
+    "tfhe_gpu_trgsw_encrypt_batch": (C.c_int, [vp, u32p, u32p, C.c_double, C.c_uint64, f64p, C.c_size_t]),
+    "tfhe_gpu_trgsw_set_load": (C.c_int, [vp, f64p, C.c_size_t, C.POINTER(vp)]),
+    "tfhe_gpu_trgsw_set_destroy": (None, [vp]),
+    "tfhe_gpu_cmux_batch": (C.c_int, [vp, vp, u32p, u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_cmux_batch_dev": (C.c_int, [vp, vp, u32p, vp, vp, vp, C.c_size_t]),
+    "tfhe_gpu_table_lookup_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_table_lookup_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, vp, vp, C.c_size_t]),
+    "tfhe_gpu_sample_extract_batch": (C.c_int, [vp, u32p, u32p, C.c_size_t, C.c_int, u32p, C.c_size_t]),
+    "tfhe_gpu_sample_extract_dev": (C.c_int, [vp, vp, u32p, C.c_size_t, C.c_int, vp, C.c_size_t]),
+    "tfhe_lookup_table_pack_bits": (C.c_int, [C.POINTER(TfheParams), C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32,
+                                              u32p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -538,6 +552,87 @@ class Context:
                    "key_switch")
         return out
 
+    # ---- leveled operations: TRLWE / TRGSW encryption, CMUX, table lookup, extraction
+    def trlwe_encrypt(self, key_lv1, mu, alpha: float | None = None, seed0: int = 1):
+        """TRLWELv1.encryptF64 (trlwe.zig:30-64) of B plaintext polynomials mu (B, N) f64;
+        item i uses DefaultPrng(seed0 + i).  -> (B, 2N) uint32."""
+        mu, mp = _f64(np.atleast_2d(mu))
+        out = np.zeros((mu.shape[0], 2 * self.params.N), np.uint32)
+        alpha = self.params.alpha_lv1 if alpha is None else alpha
+        self.check(self.lib.tfhe_gpu_trlwe_encrypt_batch(self.h, _u32(key_lv1)[1], mp, alpha, seed0,
+                                                         out.ctypes.data_as(u32p), mu.shape[0]), "trlwe_encrypt")
+        return out
+
+    def trlwe_decrypt_bool(self, key_lv1, cts):
+        """TRLWELv1.decryptBool (trlwe.zig:85-98): (B, 2N) -> (B, N) bool."""
+        cts, cp = _u32(np.atleast_2d(cts))
+        out = np.zeros((cts.shape[0], self.params.N), np.uint8)
+        self.check(self.lib.tfhe_gpu_trlwe_decrypt_bool_batch(self.h, _u32(key_lv1)[1], cp, out.ctypes.data_as(u8p),
+                                                              cts.shape[0]), "trlwe_decrypt_bool")
+        return out.astype(bool)
+
+    def trgsw_encrypt(self, key_lv1, mu, alpha: float | None = None, seed0: int = 1):
+        """TRGSWLv1.encryptTorus + TRGSWLv1FFT.new (trgsw.zig:35-91) of the S torus words mu;
+        TRGSW s draws its row seeds from DefaultPrng(seed0 + s).  -> (S, 2L, 2, N) f64."""
+        mu, mp = _u32(np.atleast_1d(mu))
+        p = self.params
+        out = np.zeros((mu.size, 2 * p.L, 2, p.N), np.float64)
+        alpha = p.alpha_bsk if alpha is None else alpha
+        self.check(self.lib.tfhe_gpu_trgsw_encrypt_batch(self.h, _u32(key_lv1)[1], mp, alpha, seed0,
+                                                         out.ctypes.data_as(f64p), mu.size), "trgsw_encrypt")
+        return out
+
+    def cmux(self, selectors: "TrgswSet", sel, in0, in1):
+        """trgsw.cmux (trgsw.zig:260-284): out[i] = in1[i] where selectors[sel[i]] encrypts 1, else in0[i]."""
+        sel, sp = _u32(np.atleast_1d(sel))
+        in0, p0 = _u32(np.atleast_2d(in0))
+        in1, p1 = _u32(np.atleast_2d(in1))
+        out = np.zeros_like(in0)
+        self.check(self.lib.tfhe_gpu_cmux_batch(self.h, selectors.h, sp, p0, p1, out.ctypes.data_as(u32p), sel.size),
+                   "cmux")
+        return out
+
+    def cmux_dev(self, selectors: "TrgswSet", sel, in0_ptr, in1_ptr, out_ptr):
+        """tfhe_gpu_cmux_batch_dev: the ciphertexts in HBM (sel stays a host array), async on the context stream."""
+        sel, sp = _u32(np.atleast_1d(sel))
+        self.check(self.lib.tfhe_gpu_cmux_batch_dev(self.h, selectors.h, sp, vp(in0_ptr), vp(in1_ptr), vp(out_ptr),
+                                                    sel.size), "cmux_dev")
+
+    def table_lookup(self, selectors: "TrgswSet", addr, table):
+        """tfhe_gpu_table_lookup_batch: table (2^k, 2N) TRLWELv1, addr (Q, k) selector indices, bit 0 first.
+        -> (Q, 2N): table[address_q]."""
+        table, tp = _u32(np.atleast_2d(table))
+        addr, ap = _u32(np.atleast_2d(addr))
+        k = addr.shape[1]
+        if table.shape[0] != 1 << k:
+            raise ValueError(f"table_lookup: {k} address bits need a table of {1 << k} entries, got {table.shape[0]}")
+        out = np.zeros((addr.shape[0], 2 * self.params.N), np.uint32)
+        self.check(self.lib.tfhe_gpu_table_lookup_batch(self.h, selectors.h, ap, k, tp, out.ctypes.data_as(u32p),
+                                                        addr.shape[0]), "table_lookup")
+        return out
+
+    def table_lookup_dev(self, selectors: "TrgswSet", addr, table_ptr, out_ptr):
+        """tfhe_gpu_table_lookup_dev: table (2^k TRLWELv1) and outputs (Q TRLWELv1) in HBM, async."""
+        addr, ap = _u32(np.atleast_2d(addr))
+        self.check(self.lib.tfhe_gpu_table_lookup_dev(self.h, selectors.h, ap, addr.shape[1], vp(table_ptr),
+                                                      vp(out_ptr), addr.shape[0]), "table_lookup_dev")
+
+    def sample_extract(self, trlwes, coef, key_switch: bool = False):
+        """sampleExtractIndex (trlwe.zig:146-162) at coefficients coef of each TRLWE, then optionally
+        identityKeySwitching: -> (B, C, N+1) TLWELv1 or (B, C, n+1) TLWELv0."""
+        x, xp = _u32(np.atleast_2d(trlwes))
+        coef, cp = _u32(np.atleast_1d(coef))
+        out = np.zeros((x.shape[0], coef.size, self.n1 if key_switch else self.params.N + 1), np.uint32)
+        self.check(self.lib.tfhe_gpu_sample_extract_batch(self.h, xp, cp, coef.size, int(key_switch),
+                                                          out.ctypes.data_as(u32p), x.shape[0]), "sample_extract")
+        return out
+
+    def sample_extract_dev(self, trlwe_ptr, B, coef, out_ptr, key_switch: bool = False):
+        """tfhe_gpu_sample_extract_dev: B TRLWELv1 and the B * C outputs in HBM (coef stays a host array), async."""
+        coef, cp = _u32(np.atleast_1d(coef))
+        self.check(self.lib.tfhe_gpu_sample_extract_dev(self.h, vp(trlwe_ptr), cp, coef.size, int(key_switch),
+                                                        vp(out_ptr), B), "sample_extract_dev")
+
 
 @dataclass
 class SecretKey:
@@ -693,6 +788,45 @@ class HipReencryptor:
         """Device-resident batch (async on the context stream): B TLWELv0 at in_ptr -> out_ptr."""
         self.ctx.check(self.ctx.lib.tfhe_gpu_reencrypt_batch_dev(self.ctx.h, self.h, vp(in_ptr), vp(out_ptr), B),
                        "reencrypt_dev")
+
+
+class TrgswSet:
+    """S TRGSWLv1FFT selectors (reference layout (S, 2L, 2, N) f64, as Context.trgsw_encrypt returns them)
+    resident in HBM in the device layout (tfhe_gpu_trgsw_set): the `selectors` of Context.cmux /
+    table_lookup, addressed by index."""
+
+    def __init__(self, ctx: Context, trgsw_fft):
+        self.ctx, self.h = ctx, vp()
+        p = ctx.params
+        t, tp = _f64(trgsw_fft)
+        per = 2 * p.L * 2 * p.N
+        if t.size == 0 or t.size % per:
+            raise ValueError(f"TrgswSet: a TRGSWLv1FFT has 2L*2*N = {per} doubles, got {t.size}")
+        self.size = t.size // per
+        ctx.check(ctx.lib.tfhe_gpu_trgsw_set_load(ctx.h, tp, self.size, C.byref(self.h)), "trgsw_set_load")
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.tfhe_gpu_trgsw_set_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lookup_table_pack_bits(params: TfheParams, values, width: int) -> np.ndarray:
+    """tfhe_lookup_table_pack_bits: entry e as a trivial TRLWELv1 whose coefficient c < width is
+    +1/8 if bit c of values[e] is set, else -1/8.  -> (len(values), 2N) uint32."""
+    vals = np.ascontiguousarray(np.atleast_1d(values), dtype=np.uint64)
+    out = np.zeros((vals.size, 2 * params.N), np.uint32)
+    rc = load_library().tfhe_lookup_table_pack_bits(C.byref(params), vals.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    vals.size, width, out.ctypes.data_as(u32p))
+    if rc:
+        raise TfheError(f"lookup_table_pack_bits: status {rc}", rc)
+    return out
 
 
 class bit_utils:
