@@ -32,7 +32,9 @@ extern "C" {
 #define TFHE_GPU_ABI_VERSION 7  /* 7: tfhe_gpu_set_stream(NULL) = the null stream, tfhe_gpu_reset_stream; later
                                    additions that change no existing entry keep the number: the leveled
                                    entries (TRLWE / TRGSW encryption, selector sets, CMUX, table lookup,
-                                   sample extraction, tfhe_lookup_table_pack_bits) and TFHE_OPT_CMUX_FORM;
+                                   sample extraction, tfhe_lookup_table_pack_bits), TFHE_OPT_CMUX_FORM and the
+                                   LUT-circuit entries (LUT sets, tfhe_gpu_lut_apply_*, tfhe_gpu_lut_circuit_eval*,
+                                   tfhe_lut_circuit_schedule);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -448,6 +450,50 @@ int tfhe_gpu_sample_extract_batch(tfhe_gpu_ctx *ctx, const uint32_t *trlwe, cons
                                   int key_switch, uint32_t *out, size_t B);
 int tfhe_gpu_sample_extract_dev(tfhe_gpu_ctx *ctx, const uint32_t *trlwe_dev, const uint32_t *coef, size_t C,
                                 int key_switch, uint32_t *out_dev, size_t B);
+
+/* ---- LUT circuits: per-item tables and linear combinations on the device ----
+ * The unit of work of multi-bit arithmetic (radix digits, comparisons, bivariate functions through a + m*b): a small
+ * integer combination of ciphertexts, then a programmable bootstrap whose table is chosen per item.  Node i over a
+ * pool of P TLWELv0 computes, in wrapping u32 arithmetic on all n+1 words (TLWELv0.add / neg / addMul / subMul,
+ * tlwe.zig:120-240; term_coef is an int32 used as a Torus word in two's complement),
+ *     x_i = sum_{k in [term_off[i], term_off[i+1])} term_coef[k] * pool[term_src[k]] + (0, ..., 0, konst[i])
+ * (no terms: the trivial ciphertext of konst[i]) and out_i = exactly the words tfhe_gpu_bootstrap_lut_batch returns
+ * for the input x_i and the test vector set[lut[i]] (blindRotateWithTestvec, sampleExtractIndex(0),
+ * identityKeySwitching).  Encoder.encode is message * scale (encoder.zig:66-73), so an integer combination of
+ * ciphertexts encodes the same combination of messages.  All of these run on the context's first device.
+ * The descriptors (term_off, term_src / term_wire, term_coef, konst, lut) are HOST arrays in both variants and are
+ * checked before any launch: TFHE_ERR_INVALID unless term_off[0] == 0 and term_off is monotone, every source is
+ * < P (in a circuit: an earlier wire), every lut[i] < T and the set belongs to this context.  TFHE_ERR_NO_KEY
+ * without a cloud key; B == 0 / n_nodes == 0 is TFHE_OK.  The _dev variants take the ciphertexts in HBM, are
+ * asynchronous on the context stream and refuse a multi-device context. */
+typedef struct tfhe_gpu_lut_set tfhe_gpu_lut_set;
+/* T >= 1 test vectors (TRLWELv1, 2N words each, any a) resident on the context's first device. */
+int  tfhe_gpu_lut_set_load(tfhe_gpu_ctx *ctx, const uint32_t *testvecs /*T*2N*/, size_t T, tfhe_gpu_lut_set **out);
+void tfhe_gpu_lut_set_destroy(tfhe_gpu_lut_set *set);
+/* B nodes over a pool of P ciphertexts: out = B*(n+1) words. */
+int tfhe_gpu_lut_apply_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
+                             const uint32_t *term_off /*B+1*/, const uint32_t *term_src, const int32_t *term_coef,
+                             const uint32_t *konst /*B*/, const uint32_t *lut /*B*/, uint32_t *out, size_t B);
+int tfhe_gpu_lut_apply_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const uint32_t *pool_dev, size_t P,
+                           const uint32_t *term_off /*B+1*/, const uint32_t *term_src, const int32_t *term_coef,
+                           const uint32_t *konst /*B*/, const uint32_t *lut /*B*/, uint32_t *out_dev, size_t B);
+/* A DAG of such nodes: wires 0..n_inputs-1 are the inputs, node g drives wire n_inputs+g, every term wire of node g
+ * is < n_inputs+g.  Each dependency level is one combination launch and one bootstrap launch; every wire stays in
+ * HBM.  outputs receives the n_outputs wires out_wires[] (an input wire is allowed); *levels (may be NULL) the
+ * bootstrap depth. */
+int tfhe_gpu_lut_circuit_eval(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
+                              size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t n_outputs,
+                              const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels);
+int tfhe_gpu_lut_circuit_eval_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                  const uint32_t *inputs_dev, size_t n_nodes, const uint32_t *term_off,
+                                  const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                  const uint32_t *lut, size_t n_outputs, const uint32_t *out_wires,
+                                  uint32_t *outputs_dev, uint32_t *levels);
+/* The schedule tfhe_gpu_lut_circuit_eval runs, host only: levels[g] = 1 + the largest level of node g's term wires
+ * (inputs are level 0; a node without terms is level 1), *depth (may be NULL) the largest. */
+int tfhe_lut_circuit_schedule(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                              uint32_t *levels, uint32_t *depth);
 
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
 /* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,

@@ -573,4 +573,113 @@ class Circuit {
     std::vector<uint32_t> ia_, ib_, outs_;
 };
 
+// Generator.generateLookupTable (lut/generator.zig:65-135) for f given as a table over m messages: 2N words.
+inline std::vector<Torus> lutGenerate(const tfhe_params &p, const std::vector<uint32_t> &f_table) {
+    std::vector<Torus> tv(2 * (size_t)p.N);
+    check(tfhe_lut_generate(&p, (uint32_t)f_table.size(), f_table.data(), tv.data()), "lutGenerate");
+    return tv;
+}
+
+// Test vectors resident in HBM (tfhe_gpu_lut_set): T TRLWELv1 of 2N words each, the tables of a LutCircuit.
+class LutSet {
+  public:
+    LutSet(const CloudKey &ck, const std::vector<std::vector<Torus>> &tables) : size_(tables.size()) {
+        const size_t per = 2 * (size_t)ck.params().N;
+        std::vector<Torus> all;
+        for (const std::vector<Torus> &t : tables) {
+            if (t.size() != per) throw Error(TFHE_ERR_INVALID, "LutSet: a test vector has 2N words");
+            all.insert(all.end(), t.begin(), t.end());
+        }
+        tfhe_gpu_lut_set *h = nullptr;
+        check(tfhe_gpu_lut_set_load(ck.ctx(), all.data(), size_, &h), "lut_set_load", ck.ctx());
+        set_.reset(h, tfhe_gpu_lut_set_destroy);
+    }
+    const tfhe_gpu_lut_set *get() const { return set_.get(); }
+    size_t size() const { return size_; }
+
+  private:
+    std::shared_ptr<tfhe_gpu_lut_set> set_;
+    size_t size_ = 0;
+};
+
+// Level-scheduled LUT circuit (tfhe_gpu_lut_circuit_eval): a node is an integer combination of earlier
+// wires (TLWELv0.add / addMul / subMul, tlwe.zig:120-240), then a programmable bootstrap with its own table.
+class LutCircuit {
+  public:
+    using Wire = uint32_t;
+    using Term = std::pair<Wire, int32_t>;  // (wire, coefficient)
+    Wire input() {
+        if (!lut_.empty()) throw Error(TFHE_ERR_INVALID, "LutCircuit: declare inputs before nodes");
+        return n_inputs_++;
+    }
+    Wire node(uint32_t lut, const std::vector<Term> &terms, Torus konst = 0) {
+        const Wire w = (Wire)(n_inputs_ + lut_.size());
+        for (const Term &t : terms) {
+            if (t.first >= w) throw Error(TFHE_ERR_INVALID, "LutCircuit: node terms must read existing wires");
+            wire_.push_back(t.first);
+            coef_.push_back(t.second);
+        }
+        off_.push_back((uint32_t)wire_.size());
+        konst_.push_back(konst);
+        lut_.push_back(lut);
+        return w;
+    }
+    void output(Wire w) { outs_.push_back(w); }
+    // Least significant digit first: per digit s = a_i + b_i + carry, message = LUT_msg(s), carry = LUT_carry(s);
+    // returns the message wires, then the final carry as an extra digit.
+    std::vector<Wire> radixAdd(const std::vector<Wire> &a, const std::vector<Wire> &b, uint32_t msg_lut,
+                               uint32_t carry_lut) {
+        std::vector<Wire> out;
+        bool have_carry = false;
+        Wire carry = 0;
+        for (size_t i = 0; i < a.size() && i < b.size(); i++) {
+            std::vector<Term> terms{{a[i], 1}, {b[i], 1}};
+            if (have_carry) terms.push_back({carry, 1});
+            out.push_back(node(msg_lut, terms));
+            carry = node(carry_lut, terms);
+            have_carry = true;
+        }
+        if (have_carry) out.push_back(carry);
+        return out;
+    }
+    // tfhe_lut_circuit_schedule: the level of every node; *depth (may be NULL) the largest
+    std::vector<uint32_t> schedule(uint32_t *depth = nullptr) const {
+        std::vector<uint32_t> levels(lut_.size());
+        check(tfhe_lut_circuit_schedule(n_inputs_, lut_.size(), off_.data(), wire_.data(), levels.data(), depth),
+              "LutCircuit.schedule");
+        return levels;
+    }
+    std::vector<TLWELv0> run(const CloudKey &ck, const LutSet &set, const std::vector<TLWELv0> &inputs,
+                             uint32_t *levels = nullptr) const {
+        if (inputs.size() != n_inputs_) throw Error(TFHE_ERR_INVALID, "LutCircuit: wrong number of inputs");
+        const size_t w = ck.params().n + 1;
+        std::vector<Torus> in(inputs.size() * w), out(outs_.size() * w);
+        for (size_t k = 0; k < inputs.size(); k++) std::copy(inputs[k].p.begin(), inputs[k].p.end(), in.begin() + k * w);
+        check(tfhe_gpu_lut_circuit_eval(ck.ctx(), set.get(), n_inputs_, in.data(), lut_.size(), off_.data(), wire_.data(),
+                                        coef_.data(), konst_.data(), lut_.data(), outs_.size(), outs_.data(), out.data(),
+                                        levels),
+              "LutCircuit.run", ck.ctx());
+        std::vector<TLWELv0> r(outs_.size(), TLWELv0(ck.params().n));
+        for (size_t k = 0; k < outs_.size(); k++) std::copy(out.begin() + k * w, out.begin() + (k + 1) * w, r[k].p.begin());
+        return r;
+    }
+    // Inputs and outputs in HBM; async on the context stream (tfhe_gpu_lut_circuit_eval_dev).  Returns the depth.
+    uint32_t runDevice(const CloudKey &ck, const LutSet &set, const Torus *inputs_dev, Torus *outputs_dev) const {
+        uint32_t levels = 0;
+        check(tfhe_gpu_lut_circuit_eval_dev(ck.ctx(), set.get(), n_inputs_, inputs_dev, lut_.size(), off_.data(),
+                                            wire_.data(), coef_.data(), konst_.data(), lut_.data(), outs_.size(),
+                                            outs_.data(), outputs_dev, &levels),
+              "LutCircuit.runDevice", ck.ctx());
+        return levels;
+    }
+    size_t numInputs() const { return n_inputs_; }
+    size_t numNodes() const { return lut_.size(); }
+    size_t numOutputs() const { return outs_.size(); }
+
+  private:
+    uint32_t n_inputs_ = 0;
+    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, outs_;
+    std::vector<int32_t> coef_;
+};
+
 }  // namespace tfhe

@@ -312,6 +312,94 @@ std::vector<SubCircuit> split_circuit(size_t n_inputs, size_t n_gates, const uin
     return sub;
 }
 
+// ---- LUT circuits ---------------------------------------------------------
+const char *check_lut_nodes(size_t B, size_t P, size_t T, const uint32_t *term_off, const uint32_t *term_src,
+                            const uint32_t *lut) {
+    if (B == 0) return nullptr;
+    if (term_off[0] != 0) return "term_off[0] is not 0";
+    for (size_t i = 0; i < B; i++) {
+        if (term_off[i + 1] < term_off[i]) return "term_off is not monotone";
+        if (lut && lut[i] >= T) return "table index >= the set's size";
+    }
+    for (size_t k = 0; k < term_off[B]; k++)
+        if (term_src[k] >= P) return "term source is not a ciphertext of the pool";
+    return nullptr;
+}
+
+const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                                std::vector<uint32_t> &level, uint32_t &depth) {
+    level.assign(n_nodes, 0);
+    depth = 0;
+    if (n_nodes == 0) return nullptr;
+    if (n_inputs + n_nodes > 0xFFFFFFFFull) return "too many wires";
+    if (term_off[0] != 0) return "term_off[0] is not 0";
+    for (size_t g = 0; g < n_nodes; g++) {
+        if (term_off[g + 1] < term_off[g]) return "term_off is not monotone";
+        uint32_t r = 0;
+        for (size_t k = term_off[g]; k < term_off[g + 1]; k++) {
+            const size_t w = term_wire[k];
+            if (w >= n_inputs + g) return "term wire is not an earlier wire";
+            if (w >= n_inputs) r = std::max(r, level[w - n_inputs]);
+        }
+        level[g] = r + 1;
+        depth = std::max(depth, level[g]);
+    }
+    return nullptr;
+}
+
+const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                             const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
+                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl) {
+    const size_t W = n_inputs + n_nodes;
+    if (W > 0xFFFFFFFFull) return "too many wires";
+    if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth)) return why;
+    for (size_t g = 0; g < n_nodes; g++)
+        if (lut[g] >= T) return "table index >= the set's size";
+    for (size_t o = 0; o < n_outputs; o++)
+        if (out_wires[o] >= W) return "output wire out of range";
+    // slots in level order (a counting sort of the nodes by level keeps node order inside a level)
+    pl.first.assign((size_t)pl.depth + 1, 0);
+    for (size_t g = 0; g < n_nodes; g++) pl.first[pl.level[g]]++;                  // level lv's count at [lv]
+    for (uint32_t lv = 1; lv <= pl.depth; lv++) pl.first[lv] += pl.first[lv - 1];  // -> its end, its start at [lv - 1]
+    pl.order.assign(n_nodes, 0);
+    pl.slot.assign(W, 0);
+    for (size_t w = 0; w < n_inputs; w++) pl.slot[w] = (uint32_t)w;
+    {
+        std::vector<uint32_t> next(pl.first.begin(), pl.first.end());
+        for (size_t g = 0; g < n_nodes; g++) {
+            const uint32_t at = next[pl.level[g] - 1]++;
+            pl.order[at] = (uint32_t)g;
+            pl.slot[n_inputs + g] = (uint32_t)(n_inputs + at);
+        }
+    }
+    // per-level CSR descriptors over slots, concatenated in evaluation order
+    const size_t terms = n_nodes ? term_off[n_nodes] : 0;
+    pl.off.clear();
+    pl.src.clear();
+    pl.coef.clear();
+    pl.konst.clear();
+    pl.lut.clear();
+    pl.off.reserve(n_nodes + pl.depth);
+    pl.src.reserve(terms);
+    pl.coef.reserve(terms);
+    for (uint32_t lv = 1; lv <= pl.depth; lv++) {
+        pl.off.push_back((uint32_t)pl.src.size());
+        for (uint32_t at = pl.first[lv - 1]; at < pl.first[lv]; at++) {
+            const uint32_t g = pl.order[at];
+            for (size_t k = term_off[g]; k < term_off[g + 1]; k++) {
+                pl.src.push_back(pl.slot[term_wire[k]]);
+                pl.coef.push_back(term_coef[k]);
+            }
+            pl.off.push_back((uint32_t)pl.src.size());
+            pl.konst.push_back(konst[g]);
+            pl.lut.push_back(lut[g]);
+        }
+    }
+    pl.out_slots.resize(n_outputs);
+    for (size_t o = 0; o < n_outputs; o++) pl.out_slots[o] = pl.slot[out_wires[o]];
+    return nullptr;
+}
+
 }  // namespace tfhe
 
 using namespace tfhe;
@@ -517,6 +605,17 @@ int tfhe_circuit_partition(size_t n_inputs, size_t n_gates, const uint8_t *ops, 
     std::vector<uint32_t> dev;
     partition_gates(n_inputs, n_gates, ops, in_a, in_b, (size_t)num_devices, dev);
     std::copy(dev.begin(), dev.end(), device_of_gate);
+    return TFHE_OK;
+}
+
+int tfhe_lut_circuit_schedule(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                              uint32_t *levels, uint32_t *depth) {
+    if (n_nodes && (!term_off || !levels || (term_off[n_nodes] && !term_wire))) return TFHE_ERR_INVALID;
+    std::vector<uint32_t> level;
+    uint32_t d = 0;
+    if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d)) return TFHE_ERR_INVALID;
+    std::copy(level.begin(), level.end(), levels);
+    if (depth) *depth = d;
     return TFHE_OK;
 }
 

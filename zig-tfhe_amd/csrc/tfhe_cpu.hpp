@@ -60,6 +60,40 @@ std::vector<SubCircuit> split_circuit(size_t n_inputs, size_t n_gates, const uin
                                       const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
                                       const std::vector<uint32_t> &dev_of_gate, size_t D);
 
+// ---- LUT circuits (tfhe_lut.cpp evaluates the plan) -------------------------
+// The descriptors of B "linear combination, then bootstrap with table lut[i]" nodes
+// over a pool of P ciphertexts and a set of T tables: nullptr, or what is wrong
+// (term_off[0] != 0 or not monotone, a source >= P, a table >= T).  lut may be NULL
+// (the schedule call has none).
+const char *check_lut_nodes(size_t B, size_t P, size_t T, const uint32_t *term_off, const uint32_t *term_src,
+                            const uint32_t *lut);
+// ASAP levels: level[g] = 1 + the largest level of node g's term wires (inputs are
+// level 0; a node without terms is level 1).  Wire w < n_inputs is input w, node g
+// drives wire n_inputs + g and reads earlier wires only.  nullptr, or the reason.
+const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                                std::vector<uint32_t> &level, uint32_t &depth);
+
+// A LUT circuit's evaluation plan.  The device wire table is laid out in
+// evaluation order, inputs | nodes of level 1 | nodes of level 2 | ..., as
+// plan_circuit lays out a gate circuit's, so a level's bootstrap writes one
+// contiguous run of slots.  Level lv (1-based) evaluates the nodes
+// order[first[lv-1] .. first[lv]); its CSR offsets are the first[lv] - first[lv-1] + 1
+// entries of `off` from first[lv-1] + lv - 1 on and index src / coef directly;
+// src holds slots, not wires.  konst / lut are per node in evaluation order.
+struct LutCircuitPlan {
+    uint32_t depth = 0;
+    std::vector<uint32_t> level;  // per node
+    std::vector<uint32_t> first;  // depth + 1 entries
+    std::vector<uint32_t> order;  // the nodes in evaluation order
+    std::vector<uint32_t> slot;   // per wire
+    std::vector<uint32_t> off, src, konst, lut;
+    std::vector<int32_t> coef;
+    std::vector<uint32_t> out_slots;
+};
+const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                             const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
+                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl);
+
 // Device d's contiguous slice of B items over D devices: ceil(B/D) each, the
 // last non-empty one ragged, the ones after it empty.
 struct Slice {

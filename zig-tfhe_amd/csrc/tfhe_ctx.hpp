@@ -158,6 +158,7 @@ struct Device {
     DevBuf s_ties;                   // near-tie flags (KParams::tie_flags), one byte per item, zero between launches
     DevBuf s_kspart;                 // gemm key switch: the K splits' partial sums
     DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
+    DevBuf s_lut_x;                  // LUT circuits: a launch's combined ciphertexts (k_lut_combine), the bootstrap's inputs
     DevPtr<uint32_t> d_ksk_gemm;     // gemm key switch: the MFMA-layout KSK (ks_gemm_bytes), built from d_ksk
     bool ksk_gemm_ok = false;        // d_ksk_gemm matches d_ksk
     Event level_ev;                  // level-split circuits: this device's slice of a level is computed
@@ -278,7 +279,7 @@ int ks_gemm_args(Device &d, size_t B, KsGemm &G);                     // the gem
 int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint32_t *tv_b);
 int key_fingerprint(Device &d, uint64_t &bk, uint64_t &ksk);
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b, const uint32_t *testvec_dev,
-                      uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr);
+                      uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr, const uint32_t *tv_sel = nullptr);
 int sync_check(Device &d);
 int d2h_sync(Device &d, void *dst, const void *src, size_t bytes);
 int upload_plan(Device &d, const CircuitPlan &pl, size_t W, size_t n_inputs, const uint32_t *inputs, size_t n_outputs,

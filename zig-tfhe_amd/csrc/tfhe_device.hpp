@@ -1075,7 +1075,9 @@ DEV void br_pairs(const uint32_t *s_tmp, int bgbit, const LdsTw &T, const C2 *tw
     }
 }
 
-template <int L, bool SMALL, bool FU>
+// TV: item g starts from its own test vector, testvec + P.tv_sel[g] * 2N (LUT circuits); a separate
+// instantiation, so the kernels without it stay the code they were.
+template <int L, bool SMALL, bool FU, bool TV = false>
 __global__ __launch_bounds__(512, 1) void k_blind_rotate(
     KParams P, DevTables TT, const uint8_t *__restrict__ ops, const uint32_t *__restrict__ in_a,
     const uint32_t *__restrict__ in_b, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ testvec,
@@ -1149,6 +1151,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate(
     const uint32_t *A = in_a + ia * (size_t)(n + 1);
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
+    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table (the clamped g: a tail copy reads a real entry)
 
     if (tid < 4) s_sync[tid] = 0u;
     for (int x = tid; x < 511; x += 256) s_tw[x] = TT.tw[x];

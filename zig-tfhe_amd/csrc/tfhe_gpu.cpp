@@ -3,7 +3,8 @@
 // all bootstrap arithmetic runs in tfhe_kernels.hip.  The functions that take
 // no context, and the circuit planner, are in tfhe_cpu.cpp (no HIP); what only
 // a context over several devices runs is in tfhe_multi.cpp; the leveled entry
-// points (CMUX, selector sets, table lookup) are in tfhe_leveled.cpp.
+// points (CMUX, selector sets, table lookup) are in tfhe_leveled.cpp, the LUT circuits in
+// tfhe_lut.cpp.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -114,7 +115,8 @@ static int ensure_tie_flags(Device &d, size_t B) {
 
 // Blind rotation (+ key switch for RUN_BOOTSTRAP) over device buffers, async.
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b,
-                      const uint32_t *testvec_dev, uint32_t *out, size_t B, int kind, const uint32_t *idx) {
+                      const uint32_t *testvec_dev, uint32_t *out, size_t B, int kind, const uint32_t *idx,
+                      const uint32_t *tv_sel) {
     const bool key_switch = kind == RUN_BOOTSTRAP;
     const int out_mode = kind == RUN_BOOTSTRAP ? BR_OUT_LV1 : kind == RUN_TRLWE ? BR_OUT_TRLWE : BR_OUT_LV0_EXTRACT2;
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
@@ -124,6 +126,7 @@ int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const ui
     if (rc) return rc;
     KParams K = d.K;
     K.tie_flags = d.s_ties.as<uint8_t>();
+    K.tv_sel = tv_sel;  // LUT circuits: B table indices into testvec_dev (device), or NULL
     uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : out;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (d.profiling) {

@@ -39,6 +39,13 @@ struct KParams {
     // the fused arithmetic at load (key admission).
     uint8_t *tie_flags;
     int fallback;
+    // Per-item test vector (LUT circuits): NULL, or one entry per item of the
+    // launch; item g then starts from the TRLWELv1 at testvec + tv_sel[g] * 2N.  An item has
+    // its own wave or workgroup in every form, so the offset is wave-uniform.  The host checks
+    // every entry against the set's size before a launch.  Only the kernels' TV = true
+    // instantiations read it (the launchers pick them when it is set): as a run-time branch it
+    // changed the default kernel's registers and schedule and cost the bench 2.5 %.
+    const uint32_t *tv_sel = nullptr;
 };
 
 // Bits of the device error word.
@@ -131,7 +138,7 @@ struct BrEntry {
 };
 // The default whole-form kernels (fused arithmetic; L = 3: k_blind_rotate_assist), built in
 // their own unit with the max-memory-clause scheduler (tfhe_kernels_whole.hip).
-BrEntry whole_default_kernel(int L);
+BrEntry whole_default_kernel(int L, bool tv = false);  // tv: the per-item test vector instantiation (KParams::tv_sel)
 // Grid and block of a form ('w' whole, 'W' latency, 'o' octo) over B items, and the one
 // launch of a blind-rotation kernel: hipErrorInvalidValue for an entry without a kernel.
 struct BrGeometry {
@@ -226,5 +233,12 @@ hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b,
 // of B TRLWELv1: B * C TLWELv1 of N + 1 words, TRLWE-major
 hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,
                                  hipStream_t s);
+
+// ---- launcher (tfhe_kernels_lut.hip); asynchronous on `s` ---------------
+// The linear step of B LUT-circuit nodes: dst[i] = sum_{k in [off[i], off[i+1])} coef[k] * pool[src[k]]
+// + (0, ..., 0, konst[i]) in wrapping u32 arithmetic, n + 1 words each; every pointer is a device
+// pointer, off has B + 1 entries that index src / coef, and the host has checked src[k] against the pool.
+hipError_t launch_lut_combine(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,
+                              const int32_t *coef, const uint32_t *konst, uint32_t *dst, size_t B, hipStream_t s);
 
 }  // namespace tfhe

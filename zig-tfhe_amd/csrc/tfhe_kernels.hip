@@ -157,7 +157,7 @@ DEV void octo_rows(const uint32_t *tA, const uint32_t *tB, int bgbit, const LdsT
     }
 }
 
-template <int L, bool SMALL, bool FU>
+template <int L, bool SMALL, bool FU, bool TV = false>
 __global__ __launch_bounds__(512, 1) void k_blind_rotate_octo(
     KParams P, DevTables TT, const uint8_t *__restrict__ ops, const uint32_t *__restrict__ in_a,
     const uint32_t *__restrict__ in_b, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ testvec,
@@ -183,6 +183,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_octo(
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
     const uint32_t pairs = (uint32_t)n * L;
+    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table (the clamped g)
 
     if (lds_layout_bad(smem)) {
         if (tid == 0) __hip_atomic_fetch_or(P.err, (uint32_t)DEV_ERR_LDS_LAYOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -294,7 +295,7 @@ constexpr int WIDE_ROW45_PRIO = 1;
 // move to waves 2, 3 (the SIMDs that carry one row wave each: the first rows of the order land
 // first), rows 2, 3 to waves 0, 1 at issue priority 1 over rows 4, 5 on their shared SIMDs.
 // Same row order and arithmetic: the same words.
-template <int L, bool SMALL, bool FU = false, int RC = 0>
+template <int L, bool SMALL, bool FU = false, int RC = 0, bool TV = false>
 __global__ __launch_bounds__(512, 1) void k_blind_rotate_wide(
     KParams P, DevTables TT, const uint8_t *__restrict__ ops, const uint32_t *__restrict__ in_a,
     const uint32_t *__restrict__ in_b, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ testvec,
@@ -318,6 +319,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_wide(
     const uint32_t *A = in_a + ia * (size_t)(n + 1);
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
+    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table
     const size_t trgsw = (size_t)2 * L * 1024;  // double2 per BK[i]
 
     for (int x = tid; x < 511; x += 512) s_tw[x] = TT.tw[x];
@@ -1376,27 +1378,45 @@ bool kernels_ab_build() { return false; }
 // arithmetic of the exact-integer regime, so only with small; the fused whole
 // form is the default kernels' unit's (whole_default_kernel).  {nullptr, ""}:
 // no such instantiation.
+// tv: the instantiation that reads a test vector per item (KParams::tv_sel, LUT circuits); the
+// others are compiled without that read and stay the code they were.
 #define BR_ENTRY(K_, L_, S_, F_, WHAT_) BrEntry{K_<L_, S_, F_>, #K_ "<" #L_ "," #S_ "," #F_ "> (" WHAT_ ")"}
 #define BR_TREES(K_, L_, WHAT_) BR_ENTRY(K_, L_, false, false, WHAT_), BR_ENTRY(K_, L_, true, false, WHAT_)
 #define BR_ALL(K_, L_, WHAT_) BR_TREES(K_, L_, WHAT_), BR_ENTRY(K_, L_, true, true, WHAT_ ", fused")
-static BrEntry br_kernel(char form, int L, bool small, bool fused) {
+#define BR_ENTRY_TV(K_, L_, S_, F_, ...) \
+    BrEntry{K_<L_, S_, F_, __VA_ARGS__>, #K_ "<" #L_ "," #S_ "," #F_ ",TV> (per-item tables; "
+#define BR_TREES_TV(K_, L_, WHAT_, ...) \
+    BR_ENTRY_TV(K_, L_, false, false, __VA_ARGS__) WHAT_ ")"}, BR_ENTRY_TV(K_, L_, true, false, __VA_ARGS__) WHAT_ ")"}
+#define BR_ALL_TV(K_, L_, WHAT_, ...) \
+    BR_TREES_TV(K_, L_, WHAT_, __VA_ARGS__), BR_ENTRY_TV(K_, L_, true, true, __VA_ARGS__) WHAT_ ", fused)"}
+static BrEntry br_kernel(char form, int L, bool small, bool fused, bool tv) {
     static const BrEntry none{nullptr, ""};
-    static const BrEntry whole[3][2] = {{BR_TREES(k_blind_rotate, 1, "whole form")},
-                                        {BR_TREES(k_blind_rotate, 2, "whole form")},
-                                        {BR_TREES(k_blind_rotate, 3, "whole form")}};
-    static const BrEntry wide[3][3] = {{BR_ALL(k_blind_rotate_wide, 1, "latency form")},
-                                       {BR_ALL(k_blind_rotate_wide, 2, "latency form")},
-                                       {BR_ALL(k_blind_rotate_wide, 3, "latency form")}};
-    static const BrEntry octo[3] = {BR_ALL(k_blind_rotate_octo, 1, "octo form")};
+    static const BrEntry whole[2][3][2] = {{{BR_TREES(k_blind_rotate, 1, "whole form")},
+                                            {BR_TREES(k_blind_rotate, 2, "whole form")},
+                                            {BR_TREES(k_blind_rotate, 3, "whole form")}},
+                                           {{BR_TREES_TV(k_blind_rotate, 1, "whole form", true)},
+                                            {BR_TREES_TV(k_blind_rotate, 2, "whole form", true)},
+                                            {BR_TREES_TV(k_blind_rotate, 3, "whole form", true)}}};
+    static const BrEntry wide[2][3][3] = {{{BR_ALL(k_blind_rotate_wide, 1, "latency form")},
+                                           {BR_ALL(k_blind_rotate_wide, 2, "latency form")},
+                                           {BR_ALL(k_blind_rotate_wide, 3, "latency form")}},
+                                          {{BR_ALL_TV(k_blind_rotate_wide, 1, "latency form", 0, true)},
+                                           {BR_ALL_TV(k_blind_rotate_wide, 2, "latency form", 0, true)},
+                                           {BR_ALL_TV(k_blind_rotate_wide, 3, "latency form", 0, true)}}};
+    static const BrEntry octo[2][3] = {{BR_ALL(k_blind_rotate_octo, 1, "octo form")},
+                                       {BR_ALL_TV(k_blind_rotate_octo, 1, "octo form", true)}};
     if (L < 1 || L > 3 || (fused && !small)) return none;
     const int arith = (small ? 1 : 0) + (fused ? 1 : 0);
     switch (form) {
-    case 'w': return fused ? whole_default_kernel(L) : whole[L - 1][arith];
-    case 'W': return wide[L - 1][arith];
-    case 'o': return L == 1 ? octo[arith] : none;
+    case 'w': return fused ? whole_default_kernel(L, tv) : whole[tv][L - 1][arith];
+    case 'W': return wide[tv][L - 1][arith];
+    case 'o': return L == 1 ? octo[tv][arith] : none;
     default: return none;
     }
 }
+#undef BR_ALL_TV
+#undef BR_TREES_TV
+#undef BR_ENTRY_TV
 #undef BR_ALL
 #undef BR_TREES
 #undef BR_ENTRY
@@ -1426,7 +1446,7 @@ static hipError_t launch_br_form(const KParams &P, const DevTables &T, const BrB
     const bool small = small_products(P), fused = small && fused_allowed(O);
     if (form == 'a')
         return ab_launch_blind_rotate ? ab_launch_blind_rotate(O.br_form, P, T, b, s, fused, used) : hipErrorInvalidValue;
-    return launch_br(br_kernel(form, P.L, small, fused), br_geometry(form, b.B), P, T, b, s, used);
+    return launch_br(br_kernel(form, P.L, small, fused, P.tv_sel != nullptr), br_geometry(form, b.B), P, T, b, s, used);
 }
 
 #ifdef TFHE_AB_BUILD
@@ -1504,7 +1524,7 @@ double blind_rotate_cost(size_t B, size_t cus, int L) {
 }
 
 // Items [start, start + count) of a batch: their ops / idx entries / inputs /
-// outputs (their near-tie flags are KParams': the caller's to shift).
+// outputs (their near-tie flags and table selectors are KParams': the caller's to shift).
 static BrBatch slice(const BrBatch &b, const KParams &P, size_t start, size_t count) {
     const size_t in_words = (size_t)P.n + 1;
     const size_t out_words = b.out_mode == BR_OUT_LV1 ? (size_t)P.N + 1 : b.out_mode == BR_OUT_TRLWE ? 2 * (size_t)P.N : in_words;
@@ -1531,6 +1551,7 @@ hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBat
     hipError_t e;
     if (O.br_form) {  // forced form (TFHE_OPT_BR_FORM): the whole batch in one launch
         const char f = O.br_form == 3 ? 'W' : O.br_form == 5 ? 'o' : O.br_form >= 6 ? 'a' : 'w';  // 6-8, 30: A/B forms
+        if (f == 'a' && Q.tv_sel) return hipErrorInvalidValue;  // the A/B forms read one test vector per launch
         e = launch_br_form(Q, T, b, s, f, O, used);
     } else {
         switch (blind_rotate_plan(b.B, device_cus(), P.L, nullptr)) {
@@ -1542,6 +1563,7 @@ hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBat
             if (e != hipSuccess) return e;
             KParams Qt = Q;
             if (Qt.tie_flags) Qt.tie_flags += full;
+            if (Qt.tv_sel) Qt.tv_sel += full;
             e = launch_br_form(Qt, T, slice(b, P, full, b.B - full), s, 'W', O, nullptr);
             break;
         }
@@ -1553,7 +1575,7 @@ hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBat
     // reference's expression trees over the same B items, whose workgroups return
     // at once unless one of their 4 items was flagged by the fused launch.
     Q.fallback = 1;
-    return launch_br(br_kernel('w', P.L, true, false), br_geometry('w', b.B), Q, T, b, s, nullptr);
+    return launch_br(br_kernel('w', P.L, true, false, Q.tv_sel != nullptr), br_geometry('w', b.B), Q, T, b, s, nullptr);
 }
 
 // The key-switch shapes (t levels of basebit bits) with instantiated kernels, and

@@ -101,7 +101,7 @@ DEV void spin_short(const uint32_t *p, uint32_t target, uint32_t cap, uint32_t &
     fail |= f;
 }
 
-template <bool FU>
+template <bool FU, bool TV = false>
 __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     KParams P, DevTables TT, const uint8_t *__restrict__ ops, const uint32_t *__restrict__ in_a,
     const uint32_t *__restrict__ in_b, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ testvec,
@@ -134,6 +134,8 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     const uint32_t *A = in_a + ia * (size_t)(n + 1);
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
+    // the item's own table (the clamped g), for the gate wave's polynomial a and the loader wave's b alike
+    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;
     const uint32_t spin_cap = P.spin_cap ? P.spin_cap : BR_SPIN_CAP_DEFAULT;
     const uint32_t msbs = digit_msbs(L, P.bgbit);
     const uint32_t pairs = (uint32_t)n * L;
@@ -348,13 +350,18 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     }
 }
 
-BrEntry whole_default_kernel(int L) {
-    static const BrEntry kernels[3] = {
-        {k_blind_rotate<1, true, true>, "k_blind_rotate<1,true,true> (whole form, fused)"},
-        {k_blind_rotate<2, true, true>, "k_blind_rotate<2,true,true> (whole form, fused)"},
-        {k_blind_rotate_assist<true>, "k_blind_rotate_assist<true> (whole form, loader waves own polynomial b, fused)"},
+BrEntry whole_default_kernel(int L, bool tv) {
+    static const BrEntry kernels[2][3] = {
+        {{k_blind_rotate<1, true, true>, "k_blind_rotate<1,true,true> (whole form, fused)"},
+         {k_blind_rotate<2, true, true>, "k_blind_rotate<2,true,true> (whole form, fused)"},
+         {k_blind_rotate_assist<true>, "k_blind_rotate_assist<true> (whole form, loader waves own polynomial b, fused)"}},
+        // a test vector per item (KParams::tv_sel)
+        {{k_blind_rotate<1, true, true, true>, "k_blind_rotate<1,true,true,TV> (per-item tables; whole form, fused)"},
+         {k_blind_rotate<2, true, true, true>, "k_blind_rotate<2,true,true,TV> (per-item tables; whole form, fused)"},
+         {k_blind_rotate_assist<true, true>,
+          "k_blind_rotate_assist<true,TV> (per-item tables; whole form, loader waves own polynomial b, fused)"}},
     };
-    return L >= 1 && L <= 3 ? kernels[L - 1] : BrEntry{nullptr, ""};
+    return L >= 1 && L <= 3 ? kernels[tv][L - 1] : BrEntry{nullptr, ""};
 }
 
 }  // namespace tfhe

@@ -1,0 +1,211 @@
+// tfhe_lut.cpp — LUT circuits of the C ABI (include/tfhe_gpu.h): resident sets
+// of test vectors, batches of "linear combination, then programmable bootstrap
+// with the node's own table", and the level-scheduled evaluator for DAGs of such
+// nodes.  Host code: the combination runs in tfhe_kernels_lut.hip, the bootstrap
+// is run_bootstrap_dev with a per-item table selector (KParams::tv_sel), and the
+// planner is in tfhe_cpu.cpp.  Everything here runs on the context's first device.
+#include "tfhe_gpu.h"
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "tfhe_ctx.hpp"
+
+using namespace tfhe;
+
+// T test vectors (TRLWELv1, 2N words each) resident on one device.
+struct tfhe_gpu_lut_set {
+    const tfhe_gpu_ctx *ctx = nullptr;  // the context that loaded it (identity only, never dereferenced)
+    tfhe_params P{};
+    size_t T = 0;
+    DevPtr<uint32_t> tables;  // T * 2N words
+};
+
+namespace tfhe {
+
+template <class F>
+static int on_device0(tfhe_gpu_ctx *c, F f) {
+    return lift(c, 0, f(c->dev[0]));
+}
+
+static const char *set_mismatch(const tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set) {
+    if (set->ctx != c) return "the LUT set was loaded on another context";
+    if (std::memcmp(&set->P, &c->P, sizeof(tfhe_params)) != 0) return "the LUT set was loaded for another parameter set";
+    return nullptr;
+}
+
+// Descriptor arrays of one call, concatenated into one upload (u32 words; the
+// coefficients keep their bits): where each starts in the device copy.
+struct DescBlob {
+    std::vector<uint32_t> words;
+    size_t add(const void *p, size_t count) {
+        const size_t at = words.size();
+        words.resize(at + count);
+        if (count) std::memcpy(words.data() + at, p, count * sizeof(uint32_t));
+        return at;
+    }
+};
+
+// B nodes over a pool of P ciphertexts (checked descriptors).  dev: pool and out are
+// device pointers, and the call returns without waiting.
+static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, size_t P, const uint32_t *term_off,
+                        const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut,
+                        uint32_t *out, size_t B, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), terms = term_off[B];
+    DescBlob blob;
+    const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
+                 coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B);
+    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
+    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
+    if (!rc && !dev && terms) rc = h2d(d, d.s_a, pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
+    if (!rc && !dev) rc = ensure(d, d.s_out, B * w * 4);
+    if (!rc) rc = ensure(d, d.s_lut_x, B * w * 4);
+    if (rc) return rc;
+    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
+    uint32_t *x = d.s_lut_x.as<uint32_t>(), *res = dev ? out : d.s_out.as<uint32_t>();
+    HIPCHK(d, launch_lut_combine(d.K, dev ? pool : d.s_a.as<const uint32_t>(), desc + off_at, desc + src_at,
+                                 reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at, x, B, d.stream));
+    rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, res, B, RUN_BOOTSTRAP, nullptr, desc + lut_at);
+    if (rc) return rc;
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * w * 4);
+}
+
+// A whole LUT circuit: one combine and one bootstrap launch per level into the
+// wire table (d.s_wires, in the plan's slot order), the outputs gathered at the end.
+static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
+                          const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    if (n_nodes && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), W = n_inputs + n_nodes;
+    size_t widest = 0;
+    for (uint32_t lv = 1; lv <= pl.depth; lv++) widest = std::max<size_t>(widest, pl.first[lv] - pl.first[lv - 1]);
+    DescBlob blob;
+    const size_t off_at = blob.add(pl.off.data(), pl.off.size()), src_at = blob.add(pl.src.data(), pl.src.size()),
+                 coef_at = blob.add(pl.coef.data(), pl.coef.size()), konst_at = blob.add(pl.konst.data(), n_nodes),
+                 lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs);
+    int rc = ensure(d, d.s_wires, std::max<size_t>(W, 1) * w * 4);
+    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
+    if (!rc && !blob.words.empty()) rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
+    if (!rc) rc = ensure(d, d.s_lut_x, std::max<size_t>(widest, 1) * w * 4);
+    if (!rc && !dev) rc = ensure(d, d.s_out, std::max<size_t>(n_outputs, 1) * w * 4);
+    if (rc) return rc;
+    if (n_inputs)
+        HIPCHK(d, hipMemcpyAsync(d.s_wires.p, inputs, n_inputs * w * 4,
+                                 dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
+    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
+    uint32_t *wires = d.s_wires.as<uint32_t>(), *x = d.s_lut_x.as<uint32_t>();
+    for (uint32_t lv = 1; lv <= pl.depth; lv++) {
+        const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at;
+        // reads slots below this level's first (earlier wires), writes the staging buffer
+        HIPCHK(d, launch_lut_combine(d.K, wires, desc + off_at + at + (lv - 1), desc + src_at,
+                                     reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at, x, nb,
+                                     d.stream));
+        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, wires + (n_inputs + at) * w, nb, RUN_BOOTSTRAP, nullptr,
+                               desc + lut_at + at);
+        if (rc) return rc;
+    }
+    if (n_outputs)
+        HIPCHK(d, launch_tlwe_gather(d.K, wires, desc + out_at, dev ? outputs : d.s_out.as<uint32_t>(), n_outputs, false,
+                                     d.stream));
+    if (dev) return TFHE_OK;
+    return n_outputs ? d2h_sync(d, outputs, d.s_out.p, n_outputs * w * 4) : sync_check(d);
+}
+
+static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
+                       const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst,
+                       const uint32_t *lut, uint32_t *out, size_t B, bool dev) {
+    if (!c || !set || (B && (!term_off || !konst || !lut || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (B == 0) return TFHE_OK;
+    if (B > 0xFFFFFFFFull || P > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "LUT batch: too many nodes or ciphertexts");
+    if (term_off[B] && (!term_src || !term_coef || !pool)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (const char *why = check_lut_nodes(B, P, set->T, term_off, term_src, lut))
+        return fail(c, TFHE_ERR_INVALID, std::string("LUT batch: ") + why);
+    return on_device0(c, [&](Device &d) {
+        return lut_apply_on(d, *set, pool, P, term_off, term_src, term_coef, konst, lut, out, B, dev);
+    });
+}
+
+static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
+                         size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                         const uint32_t *konst, const uint32_t *lut, size_t n_outputs, const uint32_t *out_wires,
+                         uint32_t *outputs, uint32_t *levels, bool dev) {
+    if (!c || !set || (n_inputs && !inputs) || (n_nodes && (!term_off || !konst || !lut)) ||
+        (n_outputs && (!out_wires || !outputs)))
+        return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (n_nodes && term_off[n_nodes] && (!term_wire || !term_coef)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    LutCircuitPlan pl;
+    if (const char *why = plan_lut_circuit(n_inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, set->T,
+                                           n_outputs, out_wires, pl))
+        return fail(c, TFHE_ERR_INVALID, std::string("LUT circuit: ") + why);
+    const int rc = on_device0(
+        c, [&](Device &d) { return lut_circuit_on(d, *set, n_inputs, inputs, n_nodes, pl, n_outputs, outputs, dev); });
+    if (!rc && levels) *levels = pl.depth;
+    return rc;
+}
+
+}  // namespace tfhe
+
+extern "C" {
+
+int tfhe_gpu_lut_set_load(tfhe_gpu_ctx *c, const uint32_t *testvecs, size_t T, tfhe_gpu_lut_set **out) {
+    if (out) *out = nullptr;
+    if (!c || !testvecs || !out || T == 0 || T > 0xFFFFFFFFull / 2048) return fail(c, TFHE_ERR_INVALID, "null argument or empty set");
+    std::unique_ptr<tfhe_gpu_lut_set> set(new tfhe_gpu_lut_set);
+    set->ctx = c;
+    set->P = c->P;
+    set->T = T;
+    const int rc = on_device0(c, [&](Device &d) -> int {
+        HIPCHK(d, hipSetDevice(d.device));
+        const size_t bytes = T * 2 * d.P.N * sizeof(uint32_t);
+        if (hipMalloc((void **)set->tables.make(d.device), bytes) != hipSuccess)
+            return fail(d, TFHE_ERR_OOM, "hipMalloc(LUT set)");
+        HIPCHK(d, hipMemcpyAsync(set->tables, testvecs, bytes, hipMemcpyHostToDevice, d.stream));
+        HIPCHK(d, hipStreamSynchronize(d.stream));
+        return TFHE_OK;
+    });
+    if (rc) return rc;
+    *out = set.release();
+    return TFHE_OK;
+}
+
+void tfhe_gpu_lut_set_destroy(tfhe_gpu_lut_set *set) { delete set; }
+
+int tfhe_gpu_lut_apply_batch(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
+                             const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                             const uint32_t *konst, const uint32_t *lut, uint32_t *out, size_t B) {
+    return apply_entry(c, set, pool, P, term_off, term_src, term_coef, konst, lut, out, B, false);
+}
+
+int tfhe_gpu_lut_apply_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool_dev, size_t P,
+                           const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                           const uint32_t *konst, const uint32_t *lut, uint32_t *out_dev, size_t B) {
+    return apply_entry(c, set, pool_dev, P, term_off, term_src, term_coef, konst, lut, out_dev, B, true);
+}
+
+int tfhe_gpu_lut_circuit_eval(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
+                              size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t n_outputs,
+                              const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels) {
+    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, n_outputs,
+                         out_wires, outputs, levels, false);
+}
+
+int tfhe_gpu_lut_circuit_eval_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                  const uint32_t *inputs_dev, size_t n_nodes, const uint32_t *term_off,
+                                  const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                  const uint32_t *lut, size_t n_outputs, const uint32_t *out_wires,
+                                  uint32_t *outputs_dev, uint32_t *levels) {
+    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, n_outputs,
+                         out_wires, outputs_dev, levels, true);
+}
+
+}  // extern "C"

@@ -83,6 +83,7 @@ def make_params(name_or_dict="128") -> TfheParams:
 
 _lib = None
 u32p, f64p, u8p, vp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_void_p
+i32p = C.POINTER(C.c_int32)
 
 _SIGS = {
     "tfhe_gpu_abi_version": (C.c_int, []),
@@ -172,6 +173,15 @@ _SIGS = {
     "tfhe_gpu_sample_extract_dev": (C.c_int, [vp, vp, u32p, C.c_size_t, C.c_int, vp, C.c_size_t]),
     "tfhe_lookup_table_pack_bits": (C.c_int, [C.POINTER(TfheParams), C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32,
                                               u32p]),
+    "tfhe_gpu_lut_set_load": (C.c_int, [vp, u32p, C.c_size_t, C.POINTER(vp)]),
+    "tfhe_gpu_lut_set_destroy": (None, [vp]),
+    "tfhe_gpu_lut_apply_batch": (C.c_int, [vp, vp, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_lut_apply_dev": (C.c_int, [vp, vp, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p, vp, C.c_size_t]),
+    "tfhe_gpu_lut_circuit_eval": (C.c_int, [vp, vp, C.c_size_t, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p,
+                                            C.c_size_t, u32p, u32p, C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_lut_circuit_eval_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p,
+                                                C.c_size_t, u32p, vp, C.POINTER(C.c_uint32)]),
+    "tfhe_lut_circuit_schedule": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, C.POINTER(C.c_uint32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -633,6 +643,46 @@ class Context:
         self.check(self.lib.tfhe_gpu_sample_extract_dev(self.h, vp(trlwe_ptr), cp, coef.size, int(key_switch),
                                                         vp(out_ptr), B), "sample_extract_dev")
 
+    # ---- LUT circuits: linear combination, then bootstrap with the node's own table ----
+    def lut_apply(self, lut_set: "LutSet", pool, nodes):
+        """tfhe_gpu_lut_apply_batch: node i = (lut, terms[, const]) computes x = sum coef * pool[src] over its
+        terms [(src, coef), ...] plus const on the b word (wrapping u32), then bootstraps x with lut_set[lut].
+        pool (P, n+1) -> (B, n+1)."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        out = np.zeros((d.B, self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_apply_batch(self.h, lut_set.h, pp, pool.shape[0], *d.pointers(),
+                                                     out.ctypes.data_as(u32p), d.B), "lut_apply")
+        return out
+
+    def lut_apply_dev(self, lut_set: "LutSet", pool_ptr, P, nodes, out_ptr):
+        """tfhe_gpu_lut_apply_dev: the pool (P TLWELv0) and the B outputs in HBM (the nodes stay a host
+        description), async on the context stream."""
+        d = pack_lut_nodes(nodes)
+        self.check(self.lib.tfhe_gpu_lut_apply_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), vp(out_ptr), d.B),
+                   "lut_apply_dev")
+
+    def lut_circuit_eval(self, lut_set: "LutSet", inputs, nodes, out_wires):
+        """tfhe_gpu_lut_circuit_eval: nodes as in lut_apply with wires for sources -> (outputs, depth)."""
+        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        ow, owp = _u32(out_wires)
+        out = np.zeros((ow.size, self.n1), np.uint32)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval(self.h, lut_set.h, inputs.shape[0], ip, d.B, *d.pointers(), ow.size,
+                                                      owp, out.ctypes.data_as(u32p), C.byref(depth)), "lut_circuit_eval")
+        return out, depth.value
+
+    def lut_circuit_eval_dev(self, lut_set: "LutSet", inputs_ptr, n_inputs, nodes, out_wires, outputs_ptr):
+        """tfhe_gpu_lut_circuit_eval_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
+        d = pack_lut_nodes(nodes)
+        ow, owp = _u32(out_wires)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_dev(self.h, lut_set.h, n_inputs, vp(inputs_ptr), d.B, *d.pointers(),
+                                                          ow.size, owp, vp(outputs_ptr), C.byref(depth)),
+                   "lut_circuit_eval_dev")
+        return depth.value
+
 
 @dataclass
 class SecretKey:
@@ -815,6 +865,134 @@ class TrgswSet:
             self.close()
         except Exception:
             pass
+
+
+class LutSet:
+    """T test vectors ((T, 2N) u32 TRLWELv1, e.g. lut_generate's) resident in HBM (tfhe_gpu_lut_set): the
+    tables of Context.lut_apply and LutCircuit, addressed by index."""
+
+    def __init__(self, ctx: Context, tables):
+        self.ctx, self.h = ctx, vp()
+        t, tp = _u32(tables)
+        per = 2 * ctx.params.N
+        if t.size == 0 or t.size % per:
+            raise ValueError(f"LutSet: a test vector has 2N = {per} words, got {t.size}")
+        self.size = t.size // per
+        ctx.check(ctx.lib.tfhe_gpu_lut_set_load(ctx.h, tp, self.size, C.byref(self.h)), "lut_set_load")
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.tfhe_gpu_lut_set_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LutNodes:
+    """The C ABI's description of B LUT nodes: CSR terms (term_off, src, coef), konst and lut per node."""
+
+    def __init__(self, term_off, src, coef, konst, lut):
+        self.term_off = np.ascontiguousarray(term_off, np.uint32)
+        self.src = np.ascontiguousarray(src, np.uint32)
+        self.coef = np.ascontiguousarray(coef, np.int32)
+        self.konst = np.ascontiguousarray(konst, np.uint32)
+        self.lut = np.ascontiguousarray(lut, np.uint32)
+        self.B = self.lut.size
+        if self.term_off.size != self.B + 1 or self.konst.size != self.B or self.src.size != self.coef.size:
+            raise ValueError("LutNodes: term_off needs B + 1 entries, konst and lut B, src and coef one per term")
+
+    def pointers(self):
+        return (self.term_off.ctypes.data_as(u32p), self.src.ctypes.data_as(u32p), self.coef.ctypes.data_as(i32p),
+                self.konst.ctypes.data_as(u32p), self.lut.ctypes.data_as(u32p))
+
+
+def pack_lut_nodes(nodes) -> LutNodes:
+    """nodes: a LutNodes, or a sequence of (lut, terms) / (lut, terms, const) with terms = [(source, coef), ...];
+    const is a Torus word added to the b word."""
+    if isinstance(nodes, LutNodes):
+        return nodes
+    off, src, coef, konst, lut = [0], [], [], [], []
+    for node in nodes:
+        t, terms, k = (*node, 0) if len(node) == 2 else node
+        for s, c in terms:
+            src.append(s)
+            coef.append(c)
+        off.append(len(src))
+        konst.append(int(k) & 0xFFFFFFFF)
+        lut.append(t)
+    return LutNodes(off, src, coef, konst, lut)
+
+
+class LutCircuit:
+    """DAG builder for Context.lut_circuit_eval: every node is a small integer combination of earlier wires
+    followed by a programmable bootstrap with one table of a LutSet.  Evaluated level by level, one
+    combination launch and one bootstrap launch per level, every wire in HBM.
+
+        c = LutCircuit(); a, b = c.input(), c.input(); s = c.node(0, [(a, 1), (b, 1)]); c.output(s)
+        outs, depth = c.run(ctx, lut_set, [ct_a, ct_b])
+    """
+
+    def __init__(self):
+        self.n_inputs = 0
+        self.nodes = []  # (lut, terms, const)
+        self.outputs = []
+
+    def input(self) -> int:
+        if self.nodes:
+            raise ValueError("declare every input before the first node")
+        self.n_inputs += 1
+        return self.n_inputs - 1
+
+    def node(self, lut: int, terms=(), const: int = 0) -> int:
+        w = self.n_inputs + len(self.nodes)
+        terms = [(int(s), int(c)) for s, c in terms]
+        if any(not 0 <= s < w for s, _ in terms):
+            raise ValueError("node terms must read existing wires")
+        self.nodes.append((int(lut), terms, int(const)))
+        return w
+
+    def output(self, *wires):
+        self.outputs.extend(wires)
+
+    def radix_add(self, a_digits, b_digits, msg_lut: int, carry_lut: int):
+        """Radix addition, least significant digit first: per digit s = a_i + b_i + carry, message =
+        LUT_msg(s), carry = LUT_carry(s).  -> the message wires, then the final carry as an extra digit."""
+        out, carry = [], None
+        for a, b in zip(a_digits, b_digits):
+            terms = [(a, 1), (b, 1)] + ([(carry, 1)] if carry is not None else [])
+            out.append(self.node(msg_lut, terms))
+            carry = self.node(carry_lut, terms)
+        return out + [carry]
+
+    def packed(self) -> LutNodes:
+        return pack_lut_nodes(self.nodes)
+
+    def schedule(self):
+        """The level of every node as tfhe_gpu_lut_circuit_eval runs it (host only) -> (levels, depth)."""
+        lib = load_library()
+        d = self.packed()
+        levels = np.zeros(max(d.B, 1), np.uint32)
+        depth = C.c_uint32(0)
+        rc = lib.tfhe_lut_circuit_schedule(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
+                                           d.src.ctypes.data_as(u32p), levels.ctypes.data_as(u32p), C.byref(depth))
+        if rc:
+            raise TfheError(f"lut_circuit_schedule: status {rc}", rc)
+        return levels[:d.B], depth.value
+
+    def run(self, ctx: "Context", lut_set: LutSet, inputs):
+        inputs = np.asarray(inputs, np.uint32).reshape(-1, ctx.params.n + 1)
+        if inputs.shape[0] != self.n_inputs:
+            raise ValueError(f"circuit has {self.n_inputs} inputs, got {inputs.shape[0]}")
+        return ctx.lut_circuit_eval(lut_set, inputs, self.packed(), np.array(self.outputs, np.uint32))
+
+    def run_dev(self, ctx: "Context", lut_set: LutSet, inputs_ptr, outputs_ptr):
+        """Inputs (n_inputs TLWELv0) and outputs in HBM; returns the bootstrap depth."""
+        return ctx.lut_circuit_eval_dev(lut_set, inputs_ptr, self.n_inputs, self.packed(),
+                                        np.array(self.outputs, np.uint32), outputs_ptr)
 
 
 def lookup_table_pack_bits(params: TfheParams, values, width: int) -> np.ndarray:
