@@ -37,6 +37,23 @@ PARAM_SETS = {
                   alpha_lv1=0.00000000000000022204460492503131,
                   alpha_ksk=0.00000251676160959795544987084234,
                   alpha_bsk=0.0),  # :210-235; BSK noise below torus resolution, see DESIGN.md
+    "110": dict(n=630, N=1024, nbit=10, L=3, bgbit=6, basebit=2, iks_t=8,
+                alpha_lv0=3.0517578125e-05, alpha_lv1=2.9802322387695313e-8,
+                alpha_ksk=2.0e-5, alpha_bsk=2.0e-8),  # :98-123
+    "uint1": dict(n=700, N=1024, nbit=10, L=2, bgbit=10, basebit=2, iks_t=8,
+                  alpha_lv0=2.0e-5, alpha_lv1=2.0e-8, alpha_ksk=2.0e-5, alpha_bsk=2.0e-8),  # :126-151
+    # UINT2 / UINT3 as UINT4: the set's lv0 noise for the KSK, and a zero BSK noise (their lv1
+    # alphas, 2^-38.6 and 2^-52, are below the torus resolution too)
+    "uint2": dict(n=687, N=1024, nbit=10, L=1, bgbit=18, basebit=4, iks_t=3,
+                  alpha_lv0=0.00002120846893069971872305794214,
+                  alpha_lv1=0.00000000000231841227527049948463,
+                  alpha_ksk=0.00002120846893069971872305794214,
+                  alpha_bsk=0.0),  # :154-179
+    "uint3": dict(n=820, N=1024, nbit=10, L=1, bgbit=23, basebit=6, iks_t=2,
+                  alpha_lv0=0.00000251676160959795544987084234,
+                  alpha_lv1=0.00000000000000022204460492503131,
+                  alpha_ksk=0.00000251676160959795544987084234,
+                  alpha_bsk=0.0),  # :182-207
 }
 
 

@@ -181,6 +181,74 @@ def test_table_lookup_returns_the_addressed_entry(oracle, pname):
         assert tfhe_amd.bit_utils.convert(dec[v][:8]) == int(values[v]), v
 
 
+_REF = {}
+
+
+def address_rows(vals, k):
+    """(Q, k) selector indices of the addresses vals: bit value 0 -> selector 0, 1 -> selector 1 or 2."""
+    return np.array([[((v >> j) & 1) * (1 + (j + q) % 2) for j in range(k)] for q, v in enumerate(vals)], np.uint32)
+
+
+def test_table_lookup_second_chunk_at_the_maximum_k(oracle):
+    """k = 12 (LOOKUP_MAX_K), Q = 17 at UINT4: table_lookup_on takes 16 queries per chunk at k = 12
+    (2,048 level-0 pairs of 8 KB per query against the scratch cap), so query 16 runs alone in a
+    second chunk, with the selector offsets sel_at[j] + 16 cnt, index tables sized for the chunk and
+    the ping-pong buffers reused.  Queries 0, 15 and 16 address 0x000, 0xFFF and 0x5A5: 0 and 15
+    differ in every bit, and 16 differs from 0 in six bits and from 15 in the other six, so a second
+    chunk that re-read the first chunk's selectors (or its last query's) cannot pass.  The oracle's
+    CMUX tree on those three; all 17 outputs equal between the per-wave, workgroup and auto forms,
+    and again through tfhe_gpu_table_lookup_dev into a sentinel-filled buffer."""
+    import torch
+    e = env(oracle, "uint4")
+    k, Q = 12, 17
+    g = rng(1217)
+    table = u32rand(g, 1 << k, 2 * e.p.N)
+    vals = [0x000] + [int(v) for v in g.integers(0, 1 << k, 14)] + [0xFFF, 0x5A5]
+    assert len(vals) == Q and vals[0] ^ vals[15] == 0xFFF and vals[16] != vals[0] and vals[16] != vals[15]
+    addr = address_rows(vals, k)
+    outs = {}
+    for form, name in FORMS:
+        with e.ctx.options(cmux_form=form):
+            outs[name] = e.ctx.table_lookup(e.set, addr, table)
+            assert e.ctx.last_kernels() == expected_kernels(form, k, e.p.L)
+    for q in (0, 15, 16):
+        want = oracle_lookup(oracle, e, table, addr[q])
+        for name, got in outs.items():
+            assert np.array_equal(got[q], want), (name, q)
+    for name in ("wave", "shared"):
+        bad = np.flatnonzero((outs[name] != outs["auto"]).any(axis=1))
+        assert bad.size == 0, (name, bad.tolist())
+    SENTINEL = 0x5EA1AB1E
+    t_table = to_dev(table)
+    t_out = torch.full((Q, 2 * e.p.N), SENTINEL, dtype=torch.int32, device="cuda:0")
+    try:
+        e.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+        e.ctx.table_lookup_dev(e.set, addr, t_table.data_ptr(), t_out.data_ptr())
+        e.ctx.sync()
+    finally:
+        e.ctx.set_stream(None)
+    got = from_dev(t_out)
+    # every row overwritten: 2,048 uniform words equal the sentinel with probability 2^-21 per row
+    assert ((got != SENTINEL).sum(axis=1) > 2000).all()
+    assert np.array_equal(got, outs["auto"])
+
+
+@pytest.mark.parametrize("form", [f for f, _ in FORMS], ids=[n for _, n in FORMS])
+def test_table_lookup_mid_range_k(oracle, form):
+    """k = 8, Q = 3 at the 128-bit set (between the k <= 5 cases and LOOKUP_MAX_K): the oracle's tree
+    (255 CMUXes) on query 2, whose address 0xB6 mixes the bits."""
+    e = env(oracle, "128")
+    k = 8
+    table = u32rand(rng(108), 1 << k, 2 * e.p.N)
+    addr = address_rows([0x00, 0xFF, 0xB6], k)
+    with e.ctx.options(cmux_form=form):
+        got = e.ctx.table_lookup(e.set, addr, table)
+        assert e.ctx.last_kernels() == expected_kernels(form, k, e.p.L)
+    if "k8" not in _REF:
+        _REF["k8"] = oracle_lookup(oracle, e, table, addr[2])
+    assert np.array_equal(got[2], _REF["k8"])
+
+
 # ---- sample extraction (trlwe.zig:146-162) ---------------------------------------
 COEF = [0, 1, 7, 1023]
 

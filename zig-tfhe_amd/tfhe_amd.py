@@ -73,7 +73,24 @@ SECURITY_UINT4 = dict(n=820, N=1024, nbit=10, L=1, bgbit=22, basebit=5, iks_t=3,
                       # f64ToTorus would turn it into a {0,-1} bias that the
                       # L=1/Bg=2^22 gadget amplifies 2^21x
                       alpha_bsk=0.0)
-PARAM_SETS = {"128": SECURITY_128_BIT, "80": SECURITY_80_BIT, "uint4": SECURITY_UINT4}
+SECURITY_110_BIT = dict(n=630, N=1024, nbit=10, L=3, bgbit=6, basebit=2, iks_t=8,
+                        alpha_lv0=3.0517578125e-05, alpha_lv1=2.9802322387695313e-8,
+                        alpha_ksk=2.0e-5, alpha_bsk=2.0e-8)
+SECURITY_UINT1 = dict(n=700, N=1024, nbit=10, L=2, bgbit=10, basebit=2, iks_t=8,
+                      alpha_lv0=2.0e-5, alpha_lv1=2.0e-8, alpha_ksk=2.0e-5, alpha_bsk=2.0e-8)
+# UINT2 / UINT3 follow UINT4: the set's lv0 alpha for the KSK, a zero BSK noise
+SECURITY_UINT2 = dict(n=687, N=1024, nbit=10, L=1, bgbit=18, basebit=4, iks_t=3,
+                      alpha_lv0=0.00002120846893069971872305794214,
+                      alpha_lv1=0.00000000000231841227527049948463,
+                      alpha_ksk=0.00002120846893069971872305794214,
+                      alpha_bsk=0.0)
+SECURITY_UINT3 = dict(n=820, N=1024, nbit=10, L=1, bgbit=23, basebit=6, iks_t=2,
+                      alpha_lv0=0.00000251676160959795544987084234,
+                      alpha_lv1=0.00000000000000022204460492503131,
+                      alpha_ksk=0.00000251676160959795544987084234,
+                      alpha_bsk=0.0)
+PARAM_SETS = {"128": SECURITY_128_BIT, "80": SECURITY_80_BIT, "uint4": SECURITY_UINT4,
+              "110": SECURITY_110_BIT, "uint1": SECURITY_UINT1, "uint2": SECURITY_UINT2, "uint3": SECURITY_UINT3}
 
 
 def make_params(name_or_dict="128") -> TfheParams:
