@@ -32,9 +32,10 @@ extern "C" {
 #define TFHE_GPU_ABI_VERSION 7  /* 7: tfhe_gpu_set_stream(NULL) = the null stream, tfhe_gpu_reset_stream; later
                                    additions that change no existing entry keep the number: the leveled
                                    entries (TRLWE / TRGSW encryption, selector sets, CMUX, table lookup,
-                                   sample extraction, tfhe_lookup_table_pack_bits), TFHE_OPT_CMUX_FORM and the
+                                   sample extraction, tfhe_lookup_table_pack_bits), TFHE_OPT_CMUX_FORM, the
                                    LUT-circuit entries (LUT sets, tfhe_gpu_lut_apply_*, tfhe_gpu_lut_circuit_eval*,
-                                   tfhe_lut_circuit_schedule);
+                                   tfhe_lut_circuit_schedule) and the packed lookup (tfhe_gpu_rotate_by_bits_*,
+                                   tfhe_gpu_packed_lookup_*, tfhe_packed_lookup_plan, tfhe_lookup_table_pack_slots);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -443,6 +444,38 @@ int tfhe_gpu_table_lookup_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set
                                 const uint32_t *table, uint32_t *out_trlwe /*Q*2N*/, size_t Q);
 int tfhe_gpu_table_lookup_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
                               const uint32_t *table_dev, uint32_t *out_dev, size_t Q);
+/* Rotation by encrypted bits ("horizontal packing"): h CMUX steps on each of B TRLWELv1.  With acc_0 = in[b],
+ *     acc_{j+1} = trgsw.cmux(acc_j, X^rot[j] * acc_j, set[sel[b*h + j]])     (polyMulWithXK, trgsw.zig:442-466)
+ * for j = 0 .. h-1 in this order, and out[b] = acc_h: the accumulator is multiplied by X^rot[j] where selector j
+ * encrypts 1.  One launch; the accumulator stays on chip for the whole chain.  1 <= h <= TFHE_ROTATE_MAX_STEPS,
+ * every rot[j] <= 2N (shared by the batch); sel and rot are HOST arrays in both variants.  The _dev one takes the
+ * ciphertexts in HBM, is asynchronous on the context stream and refuses a multi-device context; out_dev must not
+ * overlap in_dev. */
+#define TFHE_ROTATE_MAX_STEPS 32
+int tfhe_gpu_rotate_by_bits_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *sel /*B*h*/,
+                                  const uint32_t *rot /*h*/, uint32_t h, const uint32_t *in /*B*2N*/,
+                                  uint32_t *out /*B*2N*/, size_t B);
+int tfhe_gpu_rotate_by_bits_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *sel /*B*h*/,
+                                const uint32_t *rot /*h*/, uint32_t h, const uint32_t *in_dev, uint32_t *out_dev,
+                                size_t B);
+/* Packed table lookup: 2^k entries of `width` bits (1 <= width <= N), `slots` = N / stride of them side by side in
+ * one TRLWELv1 (stride = the next power of two >= width).  Entry e lives in TRLWE e >> h, bit c of it at
+ * coefficient (e & (2^h - 1)) * stride + c, h = min(k, log2 slots); the table is 2^v TRLWELv1, v = k - h <= 12
+ * (TFHE_ERR_INVALID beyond), shared by the Q queries.  Address bits as in tfhe_gpu_table_lookup_*.  The CMUX tree
+ * over the 2^v TRLWEs runs under bits h .. k-1, then the rotation above under bits 0 .. h-1 with
+ * rot[j] = 2N - stride * 2^j: coefficient c < width of out[q] is bit c of table[address_q], (2^v - 1) + h CMUXes
+ * per query where the tree alone needs 2^k - 1.  tfhe_gpu_sample_extract_* at coefficients 0 .. width-1 makes
+ * gate inputs of it.  tfhe_packed_lookup_plan (host only) gives the shape; rot[j] = 0 for j >= h. */
+typedef struct {
+    uint32_t stride, slots, h, v, trlwes, cmuxes;
+    uint32_t rot[10];
+} tfhe_packed_plan;
+int tfhe_packed_lookup_plan(const tfhe_params *params, uint32_t k, uint32_t width, tfhe_packed_plan *out);
+int tfhe_gpu_packed_lookup_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
+                                 uint32_t k, uint32_t width, const uint32_t *table /*2^v*2N*/,
+                                 uint32_t *out_trlwe /*Q*2N*/, size_t Q);
+int tfhe_gpu_packed_lookup_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
+                               uint32_t k, uint32_t width, const uint32_t *table_dev, uint32_t *out_dev, size_t Q);
 /* sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (host, each < N) of each of B TRLWELv1,
  * TRLWE-major; key_switch != 0 adds identityKeySwitching (trgsw.zig:471-502; TFHE_ERR_NO_KEY without a cloud
  * key): out = B*C*(N+1) or B*C*(n+1) words, ordinary TLWELv1 / TLWELv0 (gate inputs). */
@@ -501,6 +534,10 @@ int tfhe_lut_circuit_schedule(size_t n_inputs, size_t n_nodes, const uint32_t *t
  * are 0.  width <= N (bits past 63 read as clear). */
 int tfhe_lookup_table_pack_bits(const tfhe_params *params, const uint64_t *values, size_t entries, uint32_t width,
                                 uint32_t *table /*entries*2N*/);
+/* Host only: the packed table of tfhe_gpu_packed_lookup_* from 2^k values of `width` <= 64 bits: trlwes * 2N
+ * words (tfhe_packed_lookup_plan), trivial TRLWELv1 (a = 0), +-1/8 per bit as above, unused coefficients 0. */
+int tfhe_lookup_table_pack_slots(const tfhe_params *params, const uint64_t *values /*2^k*/, uint32_t k, uint32_t width,
+                                 uint32_t *table /*trlwes*2N*/);
 /* SecretKey.new (key.zig:41-57) from DefaultPrng(seed): n lv0 bits, then N lv1 bits. */
 int tfhe_secret_key_new(const tfhe_params *params, uint64_t seed, uint32_t *key_lv0, uint32_t *key_lv1);
 /* TLWELv0.encryptBool (tlwe.zig:52-55 -> encryptF64 :34-49); item i uses

@@ -10,7 +10,7 @@
 //   proxy_reenc.zig   -> tfhe::PublicKeyLv0, tfhe::ProxyReencryptionKey, tfhe::HipReencryptor
 //                        (reencryptTLWELv0 on the GPU)
 //   trlwe.zig         -> tfhe::TRLWELv1 (encryptF64 / encryptBool / decryptBool, sampleExtractIndex)
-//   trgsw.zig         -> tfhe::TRGSWLv1FFT::encryptTorus (encryptTorus + TRGSWLv1FFT.new), tfhe::cmux,
+//   trgsw.zig         -> tfhe::TRGSWLv1FFT::encryptTorus (encryptTorus + TRGSWLv1FFT.new), tfhe::cmux, tfhe::rotateByBits,
 //                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
@@ -382,6 +382,47 @@ struct TableLookup {
               "sample_extract", ck.ctx());
         std::vector<TLWELv0> r(coef.size(), TLWELv0(ck.params().n));
         for (size_t c = 0; c < coef.size(); c++) std::copy(out.begin() + c * w, out.begin() + (c + 1) * w, r[c].p.begin());
+        return r;
+    }
+};
+
+// Rotation by encrypted bits (tfhe_gpu_rotate_by_bits_batch): for j = 0 .. h-1 in order,
+// acc = cmux(acc, (polyMulWithXK(acc.a, rot[j]), polyMulWithXK(acc.b, rot[j])), set[sel[j]]) (trgsw.zig:260-284, :442-466).
+inline TRLWELv1 rotateByBits(const TRLWELv1 &in, const std::vector<uint32_t> &rot, const TrgswSet &set,
+                             const std::vector<uint32_t> &sel, const CloudKey &ck) {
+    TRLWELv1 out;
+    if (sel.size() != rot.size()) throw Error(TFHE_ERR_INVALID, "rotateByBits: one selector per exponent");
+    check(tfhe_gpu_rotate_by_bits_batch(ck.ctx(), set.get(), sel.data(), rot.data(), (uint32_t)rot.size(), in.p.data(),
+                                        out.p.data(), 1),
+          "rotate_by_bits", ck.ctx());
+    return out;
+}
+
+// A table of 2^k entries of `width` bits packed side by side into 2^v TRLWELv1 (tfhe_packed_lookup_plan) and addressed
+// by k TRGSW-encrypted bits per query: the CMUX tree under the high v bits, then the rotation under the low h
+// (tfhe_gpu_packed_lookup_batch), (2^v - 1) + h CMUXes.  TableLookup::extractBits at 0 .. width-1 makes gate inputs.
+struct PackedTableLookup {
+    std::vector<Torus> table;  // plan.trlwes x 2N
+    uint32_t k = 0, width = 0;
+    tfhe_packed_plan plan{};
+    static PackedTableLookup fromBits(const tfhe_params &p, const std::vector<uint64_t> &values, uint32_t width) {
+        PackedTableLookup t;
+        while (((size_t)1 << t.k) < values.size()) t.k++;
+        if (values.size() != (size_t)1 << t.k || t.k < 1) throw Error(TFHE_ERR_INVALID, "PackedTableLookup: 2^k entries, k >= 1");
+        t.width = width;
+        check(tfhe_packed_lookup_plan(&p, t.k, width, &t.plan), "packed_lookup_plan");
+        t.table.assign((size_t)t.plan.trlwes * 2 * p.N, 0u);
+        check(tfhe_lookup_table_pack_slots(&p, values.data(), t.k, width, t.table.data()), "pack_slots");
+        return t;
+    }
+    // addr[q * k + j]: the selector of `set` that encrypts bit j (least significant first) of query q's address
+    std::vector<TRLWELv1> lookup(const CloudKey &ck, const TrgswSet &set, const std::vector<uint32_t> &addr) const {
+        const size_t Q = addr.size() / k, w = 2 * (size_t)ck.params().N;
+        std::vector<Torus> out(Q * w);
+        check(tfhe_gpu_packed_lookup_batch(ck.ctx(), set.get(), addr.data(), k, width, table.data(), out.data(), Q),
+              "packed_lookup", ck.ctx());
+        std::vector<TRLWELv1> r(Q);
+        for (size_t q = 0; q < Q; q++) std::copy(out.begin() + q * w, out.begin() + (q + 1) * w, r[q].p.begin());
         return r;
     }
 };

@@ -699,6 +699,44 @@ int tfhe_lookup_table_pack_bits(const tfhe_params *p, const uint64_t *values, si
     return TFHE_OK;
 }
 
+// The packed lookup's shape (tfhe_gpu_packed_lookup_*): entries of `width` bits sit `stride` (the
+// next power of two) coefficients apart, N / stride to a TRLWE; the low h address bits choose
+// the slot (one rotate-CMUX each, by X^-(stride 2^j) = X^(2N - stride 2^j)), the other v the TRLWE.
+int tfhe_packed_lookup_plan(const tfhe_params *p, uint32_t k, uint32_t width, tfhe_packed_plan *out) {
+    std::string why;
+    if (!params_ok(p, why) || !out || k == 0 || width == 0 || width > p->N) return TFHE_ERR_INVALID;
+    uint32_t stride = 1, slot_bits = 0;
+    while (stride < width) stride *= 2;
+    while ((stride << slot_bits) < p->N) slot_bits++;
+    const uint32_t h = std::min(k, slot_bits);
+    if (k - h > 12) return TFHE_ERR_INVALID;  // the tree's limit (tfhe_gpu_table_lookup_*)
+    tfhe_packed_plan pl{};
+    pl.stride = stride;
+    pl.slots = p->N / stride;
+    pl.h = h;
+    pl.v = k - h;
+    pl.trlwes = 1u << pl.v;
+    pl.cmuxes = pl.trlwes - 1 + h;
+    for (uint32_t j = 0; j < h; j++) pl.rot[j] = 2 * p->N - (stride << j);
+    *out = pl;
+    return TFHE_OK;
+}
+
+// The packed table of 2^k values: entry e in TRLWE e >> h, bit c of it at coefficient
+// (e & (2^h - 1)) * stride + c as +-1/8 (tfhe_lookup_table_pack_bits' plaintexts); trivial (a = 0).
+int tfhe_lookup_table_pack_slots(const tfhe_params *p, const uint64_t *values, uint32_t k, uint32_t width, uint32_t *table) {
+    tfhe_packed_plan pl;
+    if (!values || !table || width > 64 || tfhe_packed_lookup_plan(p, k, width, &pl) != TFHE_OK) return TFHE_ERR_INVALID;
+    const size_t N = p->N, entries = (size_t)1 << k;
+    const uint32_t plus = host::f64_to_torus(0.125), minus = host::f64_to_torus(-0.125);
+    std::memset(table, 0, (size_t)pl.trlwes * 2 * N * sizeof(uint32_t));
+    for (size_t e = 0; e < entries; e++) {
+        uint32_t *b = table + (e >> pl.h) * 2 * N + N + (e & (((size_t)1 << pl.h) - 1)) * pl.stride;
+        for (uint32_t c = 0; c < width; c++) b[c] = ((values[e] >> c) & 1u) ? plus : minus;
+    }
+    return TFHE_OK;
+}
+
 int tfhe_fft_tables(uint32_t N, int source, double *twist_re, double *twist_im, double *stage_re, double *stage_im) {
     if (N < 4 || (N & (N - 1)) || (source != TFHE_TWIDDLES_GLIBC && source != TFHE_TWIDDLES_FDLIBM))
         return TFHE_ERR_INVALID;

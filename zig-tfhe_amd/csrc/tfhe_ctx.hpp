@@ -158,6 +158,7 @@ struct Device {
     DevBuf s_ties;                   // near-tie flags (KParams::tie_flags), one byte per item, zero between launches
     DevBuf s_kspart;                 // gemm key switch: the K splits' partial sums
     DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
+    DevBuf s_rot_idx, s_rot_in;       // rotation by encrypted bits: selector / exponent / gather indices; the packed lookup's tree outputs
     DevBuf s_lut_x;                  // LUT circuits: a launch's combined ciphertexts (k_lut_combine), the bootstrap's inputs
     DevPtr<uint32_t> d_ksk_gemm;     // gemm key switch: the MFMA-layout KSK (ks_gemm_bytes), built from d_ksk
     bool ksk_gemm_ok = false;        // d_ksk_gemm matches d_ksk

@@ -229,6 +229,19 @@ struct CmuxBatch {
 constexpr size_t CMUX_SHARED_ITEMS = 4;
 hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b, bool shared, hipStream_t s,
                        const char **used = nullptr);
+// One batch of rotations by encrypted bits (k_rotate_chain), device pointers: item g runs the h steps
+// acc <- cmux(acc, X^rot[j] acc, selector sel[g h + j]) from acc = src[i_src[g]] (i_src NULL: slot g) and
+// writes out[g]; rot[j] <= 2N, h >= 1; out must not overlap src.
+struct RotateBatch {
+    const double *sel_rows = nullptr;
+    const uint32_t *sel = nullptr, *rot = nullptr;
+    uint32_t h = 0;
+    const uint32_t *src = nullptr, *i_src = nullptr;
+    uint32_t *out = nullptr;
+    size_t B = 0;
+};
+hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const RotateBatch &b, hipStream_t s,
+                               const char **used = nullptr);
 // sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (device, each < N) of each
 // of B TRLWELv1: B * C TLWELv1 of N + 1 words, TRLWE-major
 hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,

@@ -1,6 +1,7 @@
 // tfhe_kernels_leveled.hip — the leveled half of zig-tfhe on the device: CMUX
-// against caller-supplied TRGSW selectors (trgsw.zig:260-284) and
-// sampleExtractIndex at any coefficient (trlwe.zig:146-162).  Its own unit: the
+// against caller-supplied TRGSW selectors (trgsw.zig:260-284), the rotation by
+// encrypted bits built from it (k_rotate_chain) and sampleExtractIndex at any
+// coefficient (trlwe.zig:146-162).  Its own unit: the
 // bootstrap kernels' objects (tfhe_kernels.o, tfhe_kernels_whole.o), which
 // tfhe_gpu_build_id() hashes, do not change with it.  Same flags as theirs
 // (-ffp-contract=off: every f64 multiply and add rounds separately).
@@ -166,6 +167,118 @@ __global__ __launch_bounds__(64 * CMUX_WAVES) void k_cmux_shared(KParams P, DevT
     }
 }
 
+// Rotation by encrypted bits (horizontal packing): h CMUX steps on one TRLWE,
+//   acc <- cmux(acc, X^rot[j] acc, selector sel[g h + j]),  j = 0 .. h - 1
+// (trgsw.zig:260-284 on polyMulWithXK, :442-466), one wavefront per item for the
+// whole chain.  The accumulator lives in a wave-private 8 KB of LDS beside the
+// wave's 16 KB transform exchange (96 KB per workgroup): a step reads
+// tmp = X^rot acc - acc + offset out of it (rot_read, as the blind rotation
+// does), runs the external product on the item's own selector rows, reloads acc
+// into the accumulator registers only for inverse_and_add and stores the sum
+// back, so no ciphertext goes to HBM between steps and in0 is not held in 32
+// registers across the transforms.  The LDS executes one wave's DS instructions
+// in issue order, so a wavefront fence between the store and the next step's
+// rotated reads (other lanes' words) is the whole synchronisation.  rot[] and h
+// are wave-uniform; rot[j] in [0, 2N] (rot_read masks the index: no value of it
+// reads outside the accumulator).  acc_0 = src[i_src[g]] (i_src NULL: g).  Waves
+// past B return before they read or write anything; no workgroup barrier.
+// ext_pairs_global for the chain's loop, the same arithmetic in the same order.
+// Inside the loop hipcc defers half of every pair's multiply-accumulate (the
+// imaginary sums) to the inverse transform and keeps the selector words and
+// digits they need until then: 1.2-1.6 KB of scratch per lane at L = 3, 150-500 B
+// at L = 2 (k_cmux, the same code without a loop, has none).  An empty asm on the
+// accumulated spectra after each pair makes them complete there, which removes
+// all of it; each pair's row offset behind an opaque asm as well keeps its
+// selector reads at the pair (256 + 187 registers at L = 3 against 256 + 250).
+template <int L, int RP = 0>
+DEV void ext_pairs_chain(const uint32_t *tA, const uint32_t *tB, const double2 *__restrict__ row, int bgbit,
+                         const RegTw &T, const C2 *twl, C2 *xb, int t, C2 *fa, C2 *fb) {
+    if constexpr (RP < L) {
+        C2 d[2][8];
+        forward_pair<L, RP, 1>(tA, tB, bgbit, T, twl, xb, t, d);
+        size_t at = (size_t)RP * 2048;
+        asm volatile("" : "+s"(at)::"memory");
+        mac_pair<RP>(fa, fb, d, row + at, t);
+#pragma unroll
+        for (int q = 0; q < 8; q++) asm volatile("" : "+v"(fa[q].x), "+v"(fa[q].y), "+v"(fb[q].x), "+v"(fb[q].y));
+        ext_pairs_chain<L, RP + 1>(tA, tB, row, bgbit, T, twl, xb, t, fa, fb);
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_rotate_chain(KParams P, DevTables TT,
+                                                                  const double2 *__restrict__ sel_rows,
+                                                                  const uint32_t *__restrict__ sel,
+                                                                  const uint32_t *__restrict__ rot, uint32_t h,
+                                                                  const uint32_t *__restrict__ src,
+                                                                  const uint32_t *__restrict__ i_src,
+                                                                  uint32_t *__restrict__ out, size_t B) {
+    __shared__ C2 s_x[CMUX_WAVES][2 * 512];
+    __shared__ uint32_t s_acc[CMUX_WAVES][2048];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const size_t g = (size_t)blockIdx.x * CMUX_WAVES + w;
+    if (g >= B) return;
+    const uint32_t *x = src + (size_t)(i_src ? i_src[g] : g) * 2048;
+    const uint32_t *s = sel + g * h;
+    uint32_t *acc = s_acc[w];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        acc[lane + 64 * m] = x[lane + 64 * m];
+        acc[1024 + lane + 64 * m] = x[1024 + lane + 64 * m];
+    }
+    wave_sync();
+    uint32_t accA[16], accB[16];
+    for (uint32_t j = 0; j < h; j++) {
+        // The lane index goes through an opaque asm in every step: everything a step derives
+        // from it (the exchanges' swizzled LDS addresses, the twiddle and twist reads, the
+        // accumulator's addresses) is then computed in the step.  Hoisted out of the loop, as
+        // hipcc does otherwise, some 60 such values stay live across all of it and are spilled
+        // in the loop's preheader.
+        int t = lane;
+        asm volatile("" : "+v"(t));
+        const int r = __builtin_amdgcn_readfirstlane((int)rot[j]);
+        const double2 *row = sel_rows + (size_t)s[j] * (2 * L * 1024);
+        RegTw T;
+        T.init(TT.tw, t);
+        C2 twl[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+        uint32_t tA[16], tB[16];
+#pragma unroll
+        for (int m = 0; m < 16; m++) {
+            tA[m] = rot_read(acc, t + 64 * m, r) - acc[t + 64 * m] + P.offset;
+            tB[m] = rot_read(acc + 1024, t + 64 * m, r) - acc[1024 + t + 64 * m] + P.offset;
+        }
+        C2 fa[8], fb[8];
+        ext_pairs_chain<L>(tA, tB, row, P.bgbit, T, twl, s_x[w], t, fa, fb);
+        // acc_j again, from LDS: not held in 32 registers across the transforms
+        int tr = lane;
+        asm volatile("" : "+v"(tr));
+#pragma unroll
+        for (int m = 0; m < 16; m++) {
+            accA[m] = acc[tr + 64 * m];
+            accB[m] = acc[1024 + tr + 64 * m];
+        }
+        uint32_t near = NEAR_NONE;
+        inverse_and_add<false, 1>(fa, fb, s_x[w], T, twl, t, accA, accB, near);
+        if (j + 1 < h) {
+            wave_sync();  // this step's reads of acc precede the stores
+#pragma unroll
+            for (int m = 0; m < 16; m++) {
+                acc[tr + 64 * m] = accA[m];
+                acc[1024 + tr + 64 * m] = accB[m];
+            }
+            wave_sync();  // the stores precede the next step's rotated reads (other lanes' words)
+        }
+    }
+    uint32_t *o = out + g * 2048;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        o[lane + 64 * m] = accA[m];
+        o[1024 + lane + 64 * m] = accB[m];
+    }
+}
+
 // sampleExtractIndex(trlwe, k) (trlwe.zig:146-162) for k < N = 1024: block
 // b * C + c extracts coefficient coef[c] of TRLWE b into TLWELv1 b * C + c
 // (1025 words): p[i] = a[k - i] (i <= k), -a[N + k - i] (i > k), p[N] = b[k].
@@ -201,6 +314,30 @@ hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b,
     case 1: name = cmux_launch<1>(shared, grid, block, s, P, T, b); break;
     case 2: name = cmux_launch<2>(shared, grid, block, s, P, T, b); break;
     case 3: name = cmux_launch<3>(shared, grid, block, s, P, T, b); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (used) *used = name;
+    return hipGetLastError();
+}
+
+template <int L>
+static const char *rotate_launch(dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
+                                 const RotateBatch &b) {
+    hipLaunchKernelGGL(k_rotate_chain<L>, grid, block, 0, s, P, T, reinterpret_cast<const double2 *>(b.sel_rows), b.sel,
+                       b.rot, b.h, b.src, b.i_src, b.out, b.B);
+    return L == 1 ? "k_rotate_chain<1>" : L == 2 ? "k_rotate_chain<2>" : "k_rotate_chain<3>";
+}
+
+hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const RotateBatch &b, hipStream_t s,
+                               const char **used) {
+    if (b.B == 0) return hipSuccess;
+    if (b.h == 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((b.B + CMUX_WAVES - 1) / CMUX_WAVES)), block(64 * CMUX_WAVES);
+    const char *name = "";
+    switch (P.L) {
+    case 1: name = rotate_launch<1>(grid, block, s, P, T, b); break;
+    case 2: name = rotate_launch<2>(grid, block, s, P, T, b); break;
+    case 3: name = rotate_launch<3>(grid, block, s, P, T, b); break;
     default: return hipErrorInvalidValue;
     }
     if (used) *used = name;

@@ -1,6 +1,7 @@
 // tfhe_leveled.cpp — the leveled half of the C ABI (include/tfhe_gpu.h):
 // TRLWE / TRGSW encryption, resident selector sets, CMUX, table lookup by a
-// CMUX tree and sample extraction at any coefficient.  Host code; the
+// CMUX tree, rotation by encrypted bits and the packed lookup built on both, and
+// sample extraction at any coefficient.  Host code; the
 // arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
 // tfhe_kernels.hip.  Everything here runs on the context's first device and,
 // but for the key switch after an extraction, needs no cloud key.
@@ -185,6 +186,76 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
     return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, Q * TRLWE_BYTES);
 }
 
+// h rotate-CMUX steps on B TRLWELv1 (k_rotate_chain), one launch: item g starts from src[i_src[g]]
+// (i_src NULL: slot g; a host array of B entries otherwise) and takes selectors sel[g h + j]; all
+// device pointers but sel / rot / i_src.  The three go up once, in one array.
+static int rotate_launch_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
+                            const uint32_t *src, const uint32_t *i_src, uint32_t *out, size_t B, const char **used) {
+    std::vector<uint32_t> idx(B * h + h + (i_src ? B : 0));
+    std::copy(sel, sel + B * h, idx.begin());
+    std::copy(rot, rot + h, idx.begin() + B * h);
+    if (i_src) std::copy(i_src, i_src + B, idx.begin() + B * h + h);
+    const int rc = h2d(d, d.s_rot_idx, idx.data(), idx.size() * sizeof(uint32_t));
+    if (rc) return rc;
+    const uint32_t *didx = d.s_rot_idx.as<const uint32_t>();
+    RotateBatch b;
+    b.sel_rows = set.rows;
+    b.sel = didx;
+    b.rot = didx + B * h;
+    b.h = h;
+    b.src = src;
+    b.i_src = i_src ? didx + B * h + h : nullptr;
+    b.out = out;
+    b.B = B;
+    HIPCHK(d, launch_rotate_chain(leveled_params(d), tables(d), b, d.stream, used));
+    return TFHE_OK;
+}
+
+static int rotate_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
+                     const uint32_t *in, uint32_t *out, size_t B, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    int rc = dev ? TFHE_OK : h2d(d, d.s_a, in, B * TRLWE_BYTES);
+    if (!rc && !dev) rc = ensure(d, d.s_out, B * TRLWE_BYTES);
+    if (rc) return rc;
+    d.last_ks = "";
+    rc = rotate_launch_on(d, set, sel, rot, h, dev ? in : d.s_a.as<const uint32_t>(), nullptr,
+                          dev ? out : d.s_out.as<uint32_t>(), B, &d.last_br);
+    if (rc) return rc;
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * TRLWE_BYTES);
+}
+
+// The packed lookup (tfhe_packed_lookup_plan): the CMUX tree over the 2^v table TRLWEs under address
+// bits h .. k - 1 (table_lookup_on, into context scratch), then one k_rotate_chain launch under bits
+// 0 .. h - 1.  v = 0: every query's chain starts from table TRLWE 0; h = 0 (an entry fills a TRLWE):
+// the tree alone.
+static int packed_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
+                            const tfhe_packed_plan &pl, const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
+    HIPCHK(d, hipSetDevice(d.device));
+    const uint32_t h = pl.h, v = pl.v;
+    int rc = dev ? TFHE_OK : h2d(d, d.s_a, table, (size_t)pl.trlwes * TRLWE_BYTES);
+    if (!rc && !dev) rc = ensure(d, d.s_out, Q * TRLWE_BYTES);
+    if (!rc && v && h) rc = ensure(d, d.s_rot_in, Q * TRLWE_BYTES);
+    if (rc) return rc;
+    const uint32_t *tab = dev ? table : d.s_a.as<const uint32_t>();
+    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
+    d.last_br = d.last_ks = "";
+    if (v) {
+        std::vector<uint32_t> hi(Q * v);
+        for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.begin() + q * v);
+        rc = table_lookup_on(d, set, hi.data(), v, tab, h ? d.s_rot_in.as<uint32_t>() : res, Q, /*dev*/ true);
+        if (rc) return rc;
+    }
+    if (h) {
+        std::vector<uint32_t> lo(Q * h), first(v ? 0 : Q, 0u);
+        for (size_t q = 0; q < Q; q++) std::copy(addr + q * k, addr + q * k + h, lo.begin() + q * h);
+        // last_kernels: the tree's first level, then the chain
+        rc = rotate_launch_on(d, set, lo.data(), pl.rot, h, v ? d.s_rot_in.as<const uint32_t>() : tab,
+                              v ? nullptr : first.data(), res, Q, v ? &d.last_ks : &d.last_br);
+        if (rc) return rc;
+    }
+    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, Q * TRLWE_BYTES);
+}
+
 static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *coef, size_t C, bool key_switch,
                              uint32_t *out, size_t B, bool dev) {
     HIPCHK(d, hipSetDevice(d.device));
@@ -342,6 +413,56 @@ int tfhe_gpu_table_lookup_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, 
 int tfhe_gpu_table_lookup_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
                               const uint32_t *table_dev, uint32_t *out_dev, size_t Q) {
     return lookup_entry(c, set, addr, k, table_dev, out_dev, Q, true);
+}
+
+static int rotate_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
+                        const uint32_t *in, uint32_t *out, size_t B, bool dev) {
+    if (!c || !set || !rot || (B && (!sel || !in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (h < 1 || h > TFHE_ROTATE_MAX_STEPS) return fail(c, TFHE_ERR_INVALID, "rotate by bits: h outside 1..32");
+    for (uint32_t j = 0; j < h; j++)
+        if (rot[j] > 2 * c->P.N) return fail(c, TFHE_ERR_INVALID, "rotate by bits: exponent > 2N");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (B > 0xFFFFFFFFull / h) return fail(c, TFHE_ERR_INVALID, "rotate by bits: too many items");
+    for (size_t i = 0; i < B * h; i++)
+        if (sel[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "selector index >= the set's size");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return rotate_on(d, *set, sel, rot, h, in, out, B, dev); });
+}
+
+int tfhe_gpu_rotate_by_bits_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *rot,
+                                  uint32_t h, const uint32_t *in, uint32_t *out, size_t B) {
+    return rotate_entry(c, set, sel, rot, h, in, out, B, false);
+}
+
+int tfhe_gpu_rotate_by_bits_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *rot,
+                                uint32_t h, const uint32_t *in_dev, uint32_t *out_dev, size_t B) {
+    return rotate_entry(c, set, sel, rot, h, in_dev, out_dev, B, true);
+}
+
+static int packed_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k, uint32_t width,
+                        const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
+    if (!c || !set || !table || (Q && (!addr || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    tfhe_packed_plan pl;
+    if (tfhe_packed_lookup_plan(&c->P, k, width, &pl) != TFHE_OK)
+        return fail(c, TFHE_ERR_INVALID, "packed lookup: width outside 1..N, k = 0, or more than 12 address bits left to the tree");
+    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (Q > 0xFFFFFFFFull >> pl.v) return fail(c, TFHE_ERR_INVALID, "packed lookup: too many queries");
+    for (size_t i = 0; i < Q * k; i++)
+        if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");
+    if (Q == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return packed_lookup_on(d, *set, addr, k, pl, table, out, Q, dev); });
+}
+
+int tfhe_gpu_packed_lookup_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                                 uint32_t width, const uint32_t *table, uint32_t *out_trlwe, size_t Q) {
+    return packed_entry(c, set, addr, k, width, table, out_trlwe, Q, false);
+}
+
+int tfhe_gpu_packed_lookup_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                               uint32_t width, const uint32_t *table_dev, uint32_t *out_dev, size_t Q) {
+    return packed_entry(c, set, addr, k, width, table_dev, out_dev, Q, true);
 }
 
 static int extract_entry(tfhe_gpu_ctx *c, const uint32_t *trlwe, const uint32_t *coef, size_t C, int key_switch,

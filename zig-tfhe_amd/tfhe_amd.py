@@ -58,6 +58,16 @@ class TfheParams(C.Structure):
                 f"basebit={self.basebit}, iks_t={self.iks_t})")
 
 
+class PackedPlan(C.Structure):
+    """tfhe_packed_plan: the shape of a packed lookup (tfhe_packed_lookup_plan)."""
+    _fields_ = [("stride", C.c_uint32), ("slots", C.c_uint32), ("h", C.c_uint32), ("v", C.c_uint32),
+                ("trlwes", C.c_uint32), ("cmuxes", C.c_uint32), ("rot", C.c_uint32 * 10)]
+
+    def __repr__(self):
+        return (f"PackedPlan(stride={self.stride}, slots={self.slots}, h={self.h}, v={self.v}, "
+                f"trlwes={self.trlwes}, cmuxes={self.cmuxes})")
+
+
 # params.zig parameter sets (runtime form).  KSK/BSK noise: the reference's
 # KSK_ALPHA/BSK_ALPHA (params.zig:419-422) are the 128-bit constants; UINT4
 # keeps its own set's alphas (DESIGN.md §6.3).
@@ -190,6 +200,13 @@ _SIGS = {
     "tfhe_gpu_sample_extract_dev": (C.c_int, [vp, vp, u32p, C.c_size_t, C.c_int, vp, C.c_size_t]),
     "tfhe_lookup_table_pack_bits": (C.c_int, [C.POINTER(TfheParams), C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32,
                                               u32p]),
+    "tfhe_gpu_rotate_by_bits_batch": (C.c_int, [vp, vp, u32p, u32p, C.c_uint32, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_rotate_by_bits_dev": (C.c_int, [vp, vp, u32p, u32p, C.c_uint32, vp, vp, C.c_size_t]),
+    "tfhe_packed_lookup_plan": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, C.c_uint32, C.POINTER(PackedPlan)]),
+    "tfhe_lookup_table_pack_slots": (C.c_int, [C.POINTER(TfheParams), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32,
+                                               u32p]),
+    "tfhe_gpu_packed_lookup_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_packed_lookup_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
     "tfhe_gpu_lut_set_load": (C.c_int, [vp, u32p, C.c_size_t, C.POINTER(vp)]),
     "tfhe_gpu_lut_set_destroy": (None, [vp]),
     "tfhe_gpu_lut_apply_batch": (C.c_int, [vp, vp, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, C.c_size_t]),
@@ -660,6 +677,51 @@ class Context:
         self.check(self.lib.tfhe_gpu_sample_extract_dev(self.h, vp(trlwe_ptr), cp, coef.size, int(key_switch),
                                                         vp(out_ptr), B), "sample_extract_dev")
 
+    def rotate_by_bits(self, selectors: "TrgswSet", sel, rot, trlwes):
+        """tfhe_gpu_rotate_by_bits_batch: acc <- cmux(acc, X^rot[j] acc, selectors[sel[b, j]]) for j = 0 .. h-1 on
+        each of the B TRLWELv1 `trlwes`; sel (B, h) selector indices, rot (h,) exponents in [0, 2N].  -> (B, 2N)."""
+        rot, rp = _u32(np.atleast_1d(rot))
+        x, xp = _u32(np.atleast_2d(trlwes))
+        sel, sp = _u32(np.asarray(sel, np.uint32).reshape(x.shape[0], -1))
+        if sel.shape[1] != rot.size:
+            raise ValueError(f"rotate_by_bits: {rot.size} exponents need {rot.size} selectors per item, got {sel.shape[1]}")
+        out = np.zeros_like(x)
+        self.check(self.lib.tfhe_gpu_rotate_by_bits_batch(self.h, selectors.h, sp, rp, rot.size, xp,
+                                                          out.ctypes.data_as(u32p), x.shape[0]), "rotate_by_bits")
+        return out
+
+    def rotate_by_bits_dev(self, selectors: "TrgswSet", sel, rot, in_ptr, out_ptr):
+        """tfhe_gpu_rotate_by_bits_dev: the B = len(sel) TRLWELv1 and the outputs in HBM (sel (B, h) and rot stay
+        host arrays), async on the context stream; the outputs must not overlap the inputs."""
+        rot, rp = _u32(np.atleast_1d(rot))
+        sel, sp = _u32(np.atleast_2d(sel))
+        if sel.shape[1] != rot.size:
+            raise ValueError(f"rotate_by_bits_dev: {rot.size} exponents need {rot.size} selectors per item, got {sel.shape[1]}")
+        self.check(self.lib.tfhe_gpu_rotate_by_bits_dev(self.h, selectors.h, sp, rp, rot.size, vp(in_ptr), vp(out_ptr),
+                                                        sel.shape[0]), "rotate_by_bits_dev")
+
+    def packed_lookup(self, selectors: "TrgswSet", addr, width: int, table):
+        """tfhe_gpu_packed_lookup_batch: table (2^v, 2N) TRLWELv1 holding 2^k entries of `width` bits side by side
+        (packed_lookup_plan / lookup_table_pack_slots), addr (Q, k) selector indices, bit 0 first.  -> (Q, 2N):
+        coefficient c < width of row q carries bit c of table[address_q]."""
+        table, tp = _u32(np.atleast_2d(table))
+        addr, ap = _u32(np.atleast_2d(addr))
+        k = addr.shape[1]
+        plan = packed_lookup_plan(self.params, k, width)
+        if table.shape[0] != plan.trlwes:
+            raise ValueError(f"packed_lookup: k = {k}, width = {width} need a table of {plan.trlwes} TRLWEs, "
+                             f"got {table.shape[0]}")
+        out = np.zeros((addr.shape[0], 2 * self.params.N), np.uint32)
+        self.check(self.lib.tfhe_gpu_packed_lookup_batch(self.h, selectors.h, ap, k, width, tp, out.ctypes.data_as(u32p),
+                                                         addr.shape[0]), "packed_lookup")
+        return out
+
+    def packed_lookup_dev(self, selectors: "TrgswSet", addr, width: int, table_ptr, out_ptr):
+        """tfhe_gpu_packed_lookup_dev: the packed table and the Q outputs (TRLWELv1) in HBM, async."""
+        addr, ap = _u32(np.atleast_2d(addr))
+        self.check(self.lib.tfhe_gpu_packed_lookup_dev(self.h, selectors.h, ap, addr.shape[1], width, vp(table_ptr),
+                                                       vp(out_ptr), addr.shape[0]), "packed_lookup_dev")
+
     # ---- LUT circuits: linear combination, then bootstrap with the node's own table ----
     def lut_apply(self, lut_set: "LutSet", pool, nodes):
         """tfhe_gpu_lut_apply_batch: node i = (lut, terms[, const]) computes x = sum coef * pool[src] over its
@@ -1021,6 +1083,32 @@ def lookup_table_pack_bits(params: TfheParams, values, width: int) -> np.ndarray
                                                     vals.size, width, out.ctypes.data_as(u32p))
     if rc:
         raise TfheError(f"lookup_table_pack_bits: status {rc}", rc)
+    return out
+
+
+def packed_lookup_plan(params: TfheParams, k: int, width: int) -> PackedPlan:
+    """tfhe_packed_lookup_plan: the shape of a packed lookup of 2^k entries of `width` bits (stride, slots, h
+    rotation steps, v tree levels, trlwes, cmuxes per query, rot[j] = 2N - stride * 2^j)."""
+    plan = PackedPlan()
+    rc = load_library().tfhe_packed_lookup_plan(C.byref(params), k, width, C.byref(plan))
+    if rc:
+        raise TfheError(f"packed_lookup_plan(k = {k}, width = {width}): status {rc}", rc)
+    return plan
+
+
+def lookup_table_pack_slots(params: TfheParams, values, width: int) -> np.ndarray:
+    """tfhe_lookup_table_pack_slots: the 2^k values (width <= 64 bits each) as the packed table of
+    Context.packed_lookup, +-1/8 per bit, unused coefficients 0.  -> (trlwes, 2N) uint32."""
+    vals = np.ascontiguousarray(np.atleast_1d(values), dtype=np.uint64)
+    k = int(vals.size).bit_length() - 1
+    if vals.size != 1 << k or k == 0:
+        raise ValueError(f"lookup_table_pack_slots: {vals.size} values are not 2^k, k >= 1")
+    plan = packed_lookup_plan(params, k, width)
+    out = np.zeros((plan.trlwes, 2 * params.N), np.uint32)
+    rc = load_library().tfhe_lookup_table_pack_slots(C.byref(params), vals.ctypes.data_as(C.POINTER(C.c_uint64)), k,
+                                                     width, out.ctypes.data_as(u32p))
+    if rc:
+        raise TfheError(f"lookup_table_pack_slots: status {rc}", rc)
     return out
 
 
