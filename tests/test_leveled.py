@@ -364,6 +364,40 @@ def test_dev_forms_equal_host_forms(oracle, keyed80):
     sels.close()
 
 
+# ---- host staging ------------------------------------------------------------------
+def test_host_staging_modes_same_words_leveled(oracle):
+    """TFHE_OPT_HOST_STAGING on the leveled host entry points: pinned staging and pageable copies
+    return the same words for cmux (B = 5: one full workgroup and a tail of 1), table_lookup
+    (k = 3, Q = 2), rotate_by_bits (h = 2, B = 2) and sample_extract (2 coefficients of 2 TRLWEs,
+    no key switch), the smallest shapes that pass through every staged input and output.  Each
+    call runs twice under pinned staging, so the arena is reused from offset 0."""
+    e = env(oracle, "uint4")
+    g = rng(71)
+    N2 = 2 * e.p.N
+    in0, in1, table, x = u32rand(g, 5, N2), u32rand(g, 5, N2), u32rand(g, 8, N2), u32rand(g, 2, N2)
+    sel = np.array([1, 0, 2, 1, 0], np.uint32)
+    _, addr = lookup_addresses(3, 2, g)
+    calls = {
+        "cmux": lambda: e.ctx.cmux(e.set, sel, in0, in1),
+        "table_lookup": lambda: e.ctx.table_lookup(e.set, addr, table),
+        "rotate_by_bits": lambda: e.ctx.rotate_by_bits(e.set, [[1, 0], [0, 2]], [1, e.p.N + 3], x),
+        "sample_extract": lambda: e.ctx.sample_extract(x, [0, e.p.N - 1]),
+    }
+    assert e.ctx.get_option("host_staging") == tfhe_amd.STAGING_PAGEABLE
+    want = {name: f() for name, f in calls.items()}
+    with e.ctx.options(host_staging=tfhe_amd.STAGING_PINNED):
+        for name, f in calls.items():
+            for rep in range(2):
+                assert np.array_equal(f(), want[name]), (name, rep)
+    assert e.ctx.get_option("host_staging") == tfhe_amd.STAGING_PAGEABLE
+    for name, f in calls.items():  # and back: pageable copies after the arena was in use
+        assert np.array_equal(f(), want[name]), name
+    # the pageable words are the oracle's, so a staging bug cannot hide in a shared reference
+    assert np.array_equal(want["cmux"][4], oracle.cmux(e.p, in0[4], in1[4], e.trgsw[sel[4]], e.off))
+    assert np.array_equal(want["table_lookup"][1], oracle_lookup(oracle, e, table, addr[1]))
+    assert np.array_equal(want["sample_extract"][1, 1], oracle.sample_extract_index(x[1], e.p.N - 1))
+
+
 # ---- argument checks (no launch follows a refused call) -----------------------------
 def test_error_returns(oracle, keyed80):
     e = env(oracle, "128")

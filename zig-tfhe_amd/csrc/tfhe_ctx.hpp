@@ -1,8 +1,8 @@
 // tfhe_ctx.hpp — the two types behind the C handle and what the host units
 // share: Device (everything that belongs to one GPU) and tfhe_gpu_ctx (the
 // handle: one Device or several), the owners of their HIP resources, error
-// reporting, and the functions tfhe_gpu.cpp and tfhe_multi.cpp call in each
-// other.  Not installed.
+// reporting, a call's host-or-device buffers (Io), and the functions the host
+// units call in each other.  Not installed.
 #pragma once
 
 #include "tfhe_gpu.h"
@@ -11,6 +11,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: librccl is dlopen'ed on first multi-device key load
 
 #include <condition_variable>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -262,6 +263,25 @@ int for_each_slice(tfhe_gpu_ctx *c, size_t B, F f) {
     return TFHE_OK;
 }
 
+// f(device 0), with that device current, for an entry point that works on one device; a
+// failure is lifted into the handle's.
+template <class F>
+int on_device0(tfhe_gpu_ctx *c, F f) {
+    Device &d = c->dev[0];
+    const hipError_t e = hipSetDevice(d.device);
+    return lift(c, 0, e == hipSuccess ? f(d) : hip_fail(d, e, "hipSetDevice(d.device)"));
+}
+
+// Refuses a resident set (`what`: "selector set", "LUT set") that does not belong to this
+// context and its parameter set.
+template <class Set>
+int set_mismatch(tfhe_gpu_ctx *c, const Set *set, const char *what) {
+    const char *why = nullptr;
+    if (set->ctx != c) why = "on another context";
+    else if (std::memcmp(&set->P, &c->P, sizeof(tfhe_params)) != 0) why = "for another parameter set";
+    return why ? fail(c, TFHE_ERR_INVALID, std::string("the ") + what + " was loaded " + why) : TFHE_OK;
+}
+
 inline size_t tlwe0_words(const tfhe_params &p) { return (size_t)p.n + 1; }
 inline double level_cost(size_t items, size_t cus) { return blind_rotate_cost(items, cus); }  // the planner's CostModel
 
@@ -272,12 +292,14 @@ enum RunKind : int {
     RUN_NO_KEYSWITCH = 2,  // sampleExtractIndex2, n+1 words (vanilla.zig:58-69)
 };
 
-// ---- tfhe_gpu.cpp, for tfhe_multi.cpp and tfhe_leveled.cpp -----------------------
+// ---- tfhe_gpu.cpp, for the other host units --------------------------------------
 int ensure(Device &d, DevBuf &b, size_t bytes);                       // device scratch of at least `bytes`
 int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes);       // host -> `buf`, async on the device's stream
 DevTables tables(const Device &d);
 int ks_gemm_args(Device &d, size_t B, KsGemm &G);                     // the gemm key switch's buffers for B items
 int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint32_t *tv_b);
+int upload_ksk(Device &d, const uint32_t *ksk);                       // host KSK (reference layout) -> device KSK, async
+int key_loaded(Device &d, bool from_keygen);                          // the end of every key load on device 0: admission
 int key_fingerprint(Device &d, uint64_t &bk, uint64_t &ksk);
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b, const uint32_t *testvec_dev,
                       uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr, const uint32_t *tv_sel = nullptr);
@@ -288,6 +310,44 @@ int upload_plan(Device &d, const CircuitPlan &pl, size_t W, size_t n_inputs, con
 int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t n_gates, const uint8_t *ops,
                      const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
                      uint32_t *outputs, uint32_t *levels_out, bool dev = false);
+
+// The buffers of one call on one device.  Host buffers (dev = false) are staged through the
+// device's scratch: in() uploads one and out() reserves room for one, each leaving its
+// pointer at the scratch copy for the launches that follow, and finish() copies the output
+// back and waits.  Device pointers (dev = true) stay as they are, and nothing is waited for.
+struct Io {
+    Device &d;
+    bool dev;
+    void *host_out = nullptr;  // out(): the caller's buffer, its scratch copy and size
+    const void *staged_out = nullptr;
+    size_t out_bytes = 0;
+
+    template <class T>
+    int in(DevBuf &buf, const T *&p, size_t bytes) {
+        if (dev) return TFHE_OK;
+        const int rc = h2d(d, buf, p, bytes);
+        p = buf.as<const T>();
+        return rc;
+    }
+    template <class T>
+    int out(T *&p, size_t bytes, DevBuf &buf) {
+        if (dev) return TFHE_OK;
+        const int rc = ensure(d, buf, bytes);
+        host_out = p;
+        out_bytes = bytes;
+        staged_out = p = buf.as<T>();
+        return rc;
+    }
+    template <class T>
+    int out(T *&p, size_t bytes) {
+        return out(p, bytes, d.s_out);
+    }
+    // The host call waits: for its output, or without one for the work and the error word.
+    int finish() {
+        if (dev) return TFHE_OK;
+        return host_out ? d2h_sync(d, host_out, staged_out, out_bytes) : sync_check(d);
+    }
+};
 
 // ---- tfhe_multi.cpp, for tfhe_gpu.cpp ------------------------------------------
 int enable_peer_access(const std::vector<int> &devs, std::string &why);

@@ -1,10 +1,10 @@
 // tfhe_gpu.cpp — C-ABI implementation (include/tfhe_gpu.h): contexts, device
-// key residency, batch entry points and seeded key generation.  Host code;
-// all bootstrap arithmetic runs in tfhe_kernels.hip.  The functions that take
-// no context, and the circuit planner, are in tfhe_cpu.cpp (no HIP); what only
-// a context over several devices runs is in tfhe_multi.cpp; the leveled entry
-// points (CMUX, selector sets, table lookup) are in tfhe_leveled.cpp, the LUT circuits in
-// tfhe_lut.cpp.
+// key residency and the batch entry points.  Host code; all bootstrap arithmetic
+// runs in tfhe_kernels.hip.  The functions that take no context, and the circuit
+// planner, are in tfhe_cpu.cpp (no HIP); what only a context over several devices
+// runs is in tfhe_multi.cpp; seeded key generation and TRLWE / TRGSW encryption
+// are in tfhe_encrypt.cpp; the leveled entry points (CMUX, selector sets, table
+// lookup) are in tfhe_leveled.cpp, the LUT circuits in tfhe_lut.cpp.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -22,7 +22,7 @@ using namespace tfhe;
 // ---- One device ------------------------------------------------------------------
 // Everything here works on one Device and reports into its `err`; the entry
 // points lift a failure into the handle's (lift, for_each_slice).  The functions
-// tfhe_multi.cpp calls too are declared in tfhe_ctx.hpp, the rest are static.
+// the other host units call too are declared in tfhe_ctx.hpp, the rest are static.
 namespace tfhe {
 
 // the calling thread's last failed create (tfhe_gpu_last_error(NULL))
@@ -52,7 +52,7 @@ static size_t ksk_dev_bytes(const tfhe_params &p) {
 }
 
 // host KSK (reference layout) -> device KSK (padded rows), async on the device's stream
-static int upload_ksk(Device &d, const uint32_t *ksk) {
+int upload_ksk(Device &d, const uint32_t *ksk) {
     const size_t w = d.P.n + 1, stride = d.K.ks_stride;
     d.ksk_gemm_ok = false;
     HIPCHK(d, hipMemsetAsync(d.d_ksk, 0, d.ksk_bytes, d.stream));
@@ -278,7 +278,6 @@ static int key_admission(Device &d) {
     d.opts.key_fused_ok = 0;
     auto *dw = reinterpret_cast<unsigned long long *>(d.d_err + 2);
     auto *h = reinterpret_cast<volatile unsigned long long *>(d.h_err + 2);
-    HIPCHK(d, hipSetDevice(d.device));
     HIPCHK(d, launch_absmax(d.d_bk, d.bk_bytes / sizeof(double), dw, d.stream));
     HIPCHK(d, launch_row_energy_max(d.d_bk, (size_t)d.P.n * 2 * d.P.L, dw + 1, d.stream));
     HIPCHK(d, hipMemcpyAsync(d.h_err + 2, dw, 16, hipMemcpyDeviceToHost, d.stream));
@@ -354,7 +353,7 @@ static int build_tables(Device &d, int source) {
 
 // Every key load on device 0 ends here: admit the fused arithmetic or not.  An
 // unmeasured key is not a loaded key.
-static int key_loaded(Device &d, bool from_keygen) {
+int key_loaded(Device &d, bool from_keygen) {
     d.key_from_keygen = from_keygen;
     const int rc = key_admission(d);
     d.has_key = rc == TFHE_OK;
@@ -379,12 +378,6 @@ static int init_device(Device &d, const tfhe_params &p, int device) {
     std::memset(d.h_err, 0, 64);
     d.K.err = d.d_err;
     return build_tables(d, TFHE_TWIDDLES_GLIBC);
-}
-
-// f(device 0) for an entry point that works on one device, its failure lifted into the handle's.
-template <class F>
-static int on_device0(tfhe_gpu_ctx *c, F f) {
-    return lift(c, 0, f(c->dev[0]));
 }
 
 }  // namespace tfhe
@@ -461,10 +454,7 @@ int tfhe_gpu_key_fingerprint(tfhe_gpu_ctx *c, uint64_t *bk, uint64_t *ksk) {
 
 int tfhe_gpu_sync(tfhe_gpu_ctx *c) {
     if (!c) return TFHE_ERR_INVALID;
-    return on_device0(c, [](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        return sync_check(d);
-    });
+    return on_device0(c, sync_check);
 }
 
 // The device queues its own work on its stream too (the MFMA-layout KSK build,
@@ -472,7 +462,6 @@ int tfhe_gpu_sync(tfhe_gpu_ctx *c) {
 // queued on the old one, so a _dev call on the new stream never overtakes it.
 static int switch_stream(Device &d, hipStream_t ns) {
     if (ns == d.stream) return TFHE_OK;
-    HIPCHK(d, hipSetDevice(d.device));
     if (!d.stream_ev) HIPCHK(d, hipEventCreateWithFlags(d.stream_ev.make(d.device), hipEventDisableTiming));
     HIPCHK(d, hipEventRecord(d.stream_ev, d.stream));
     HIPCHK(d, hipStreamWaitEvent(ns, d.stream_ev, 0));
@@ -486,12 +475,12 @@ static int switch_stream(Device &d, hipStream_t ns) {
 // non-blocking stream, unordered with torch's work.  Both act on device 0 only.
 int tfhe_gpu_set_stream(tfhe_gpu_ctx *c, void *s) {
     if (!c) return TFHE_ERR_INVALID;
-    return lift(c, 0, switch_stream(c->dev[0], (hipStream_t)s));
+    return on_device0(c, [&](Device &d) { return switch_stream(d, (hipStream_t)s); });
 }
 
 int tfhe_gpu_reset_stream(tfhe_gpu_ctx *c) {
     if (!c) return TFHE_ERR_INVALID;
-    return lift(c, 0, switch_stream(c->dev[0], c->dev[0].own_stream));
+    return on_device0(c, [](Device &d) { return switch_stream(d, d.own_stream); });
 }
 
 int tfhe_gpu_load_cloud_key(tfhe_gpu_ctx *c, uint32_t offset, const uint32_t *tv_a, const uint32_t *tv_b,
@@ -501,7 +490,6 @@ int tfhe_gpu_load_cloud_key(tfhe_gpu_ctx *c, uint32_t offset, const uint32_t *tv
     if (bsk_len != rows * 2 * c->P.N) return fail(c, TFHE_ERR_INVALID, "bsk_len != n*2L*2*N");
     if (ksk_len != ksk_words(c->P)) return fail(c, TFHE_ERR_INVALID, "ksk_len != N*t*2^basebit*(n+1)");
     const int rc = on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         int rc = set_key_common(d, offset, tv_a, tv_b);
         if (rc) return rc;
         rc = h2d(d, d.s_tmp, bsk, bsk_len * sizeof(double));
@@ -528,7 +516,6 @@ int tfhe_gpu_export_key_device(tfhe_gpu_ctx *c, void *bsk_dev, void *ksk_dev, ui
     if (!c || !bsk_dev || !ksk_dev) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (!c->dev[0].has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         HIPCHK(d, hipMemcpyAsync(bsk_dev, d.d_bk, d.bk_bytes, hipMemcpyDeviceToDevice, d.stream));
         HIPCHK(d, hipMemcpyAsync(ksk_dev, d.d_ksk, d.ksk_bytes, hipMemcpyDeviceToDevice, d.stream));
         HIPCHK(d, hipStreamSynchronize(d.stream));
@@ -542,7 +529,6 @@ int tfhe_gpu_import_key_device(tfhe_gpu_ctx *c, const void *bsk_dev, const void 
                                const uint32_t *testvec) {
     if (!c || !bsk_dev || !ksk_dev || !testvec) return fail(c, TFHE_ERR_INVALID, "null argument");
     const int rc = on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         int rc = set_key_common(d, offset, testvec, testvec + d.P.N);
         if (rc) return rc;
         HIPCHK(d, hipMemcpyAsync(d.d_bk, bsk_dev, d.bk_bytes, hipMemcpyDeviceToDevice, d.stream));
@@ -562,7 +548,6 @@ int tfhe_gpu_export_cloud_key(tfhe_gpu_ctx *c, uint32_t *offset, uint32_t *tv_a,
     if (!c) return TFHE_ERR_INVALID;
     if (!c->dev[0].has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         const size_t N = d.P.N;
         if (offset) *offset = d.offset;
         if (tv_a) std::memcpy(tv_a, d.testvec.data(), N * sizeof(uint32_t));
@@ -607,93 +592,6 @@ int tfhe_gpu_load_cloud_key_file(tfhe_gpu_ctx *c, const char *path) {
     if (rc == TFHE_ERR_IO) return fail(c, rc, std::string("cannot read key file ") + path);
     if (rc) return fail(c, rc, std::string(path) + ": not a key file of this parameter set, or checksum mismatch");
     return tfhe_gpu_load_cloud_key(c, off, ta.data(), tb.data(), bsk.data(), bl, ksk.data(), kl);
-}
-
-// SecretKey.new + CloudKey.new, seeded.  Host: every RNG draw in reference
-// order; device: the FFT-based poly_mul of each TRLWE encryption
-// (trlwe.zig:56-61) and the TRGSWLv1FFT forward transforms (trgsw.zig:81-91).
-int tfhe_gpu_keygen(tfhe_gpu_ctx *c, uint64_t secret_seed, uint64_t cloud_seed, uint32_t *key_lv0,
-                    uint32_t *key_lv1, double *bsk_out, uint32_t *ksk_out) {
-    if (!c || !key_lv0 || !key_lv1) return fail(c, TFHE_ERR_INVALID, "null argument");
-    const int rc = on_device0(c, [&](Device &d) -> int {
-        const tfhe_params &p = d.P;
-        const uint32_t N = p.N, n = p.n, L = p.L, T = p.iks_t, base = 1u << p.basebit;
-        HIPCHK(d, hipSetDevice(d.device));
-        tfhe_secret_key_new(&p, secret_seed, key_lv0, key_lv1);
-        host::Rng master(cloud_seed);
-        // genKeySwitchingKey (key.zig:148-172): k = 0 rows are zeroed
-        std::vector<uint32_t> ksk(ksk_words(p), 0u);
-        for (uint32_t i = 0; i < N; i++)
-            for (uint32_t j = 0; j < T; j++)
-                for (uint32_t k = 1; k < base; k++) {
-                    size_t idx = (size_t)base * T * i + (size_t)base * j + k;
-                    uint32_t shift = (j + 1) * p.basebit;
-                    double pv = ((double)k * (double)key_lv1[i]) / (double)(1u << shift);
-                    tlwe_encrypt(n, pv, p.alpha_ksk, key_lv0, master.next(), ksk.data() + idx * (n + 1));
-                }
-        // genBootstrappingKey (key.zig:175-212): per i, TRGSW encryptTorus of
-        // key_lv0[i]: 2L TRLWE encryptions of zero (trlwe.zig:30-64), gadget on
-        // a[0] of row l / b[0] of row L+l.
-        const size_t R = bk_rows(p);  // n*2L TRLWE rows
-        std::vector<uint32_t> rows(R * 2 * N);
-        std::vector<uint32_t> noise(R * N);
-        for (size_t row = 0; row < R; row++) {
-            host::Rng r(master.next());
-            uint32_t *a = rows.data() + row * 2 * N;
-            for (uint32_t x = 0; x < N; x++) a[x] = r.u32();
-            host::NormalDist nd(0.0, p.alpha_bsk);
-            for (uint32_t x = 0; x < N; x++) noise[row * N + x] = host::gaussian_torus(0u, nd, r);
-        }
-        int rc = h2d(d, d.s_b, key_lv1, N * sizeof(uint32_t));
-        if (rc) return rc;
-        rc = ensure(d, d.s_out, R * N * sizeof(uint32_t));
-        if (rc) return rc;
-        // a*s for all rows: a_i lives at stride 2N inside `rows`
-        std::vector<uint32_t> a_only(R * N);
-        for (size_t row = 0; row < R; row++)
-            std::memcpy(a_only.data() + row * N, rows.data() + row * 2 * N, N * sizeof(uint32_t));
-        rc = h2d(d, d.s_a, a_only.data(), a_only.size() * sizeof(uint32_t));
-        if (rc) return rc;
-        HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 0,
-                                  d.s_out.as<uint32_t>(), R, d.stream));
-        std::vector<uint32_t> as(R * N);
-        rc = d2h_sync(d, as.data(), d.s_out.p, as.size() * sizeof(uint32_t));
-        if (rc) return rc;
-        for (size_t row = 0; row < R; row++) {
-            uint32_t *b = rows.data() + row * 2 * N + N;
-            for (uint32_t x = 0; x < N; x++) b[x] = noise[row * N + x] + as[row * N + x];
-        }
-        for (uint32_t i = 0; i < n; i++) {
-            uint32_t mu = key_lv0[i];
-            for (uint32_t l = 0; l < L; l++) {
-                uint32_t h = host::f64_to_torus(std::ldexp(1.0, -(int)((l + 1) * p.bgbit)));
-                rows[((size_t)i * 2 * L + l) * 2 * N] += mu * h;              // trlwe[l].a[0]
-                rows[((size_t)i * 2 * L + L + l) * 2 * N + N] += mu * h;      // trlwe[L+l].b[0]
-            }
-        }
-        // TRGSWLv1FFT.new: ifft of every a and b polynomial -> reference BK layout
-        rc = h2d(d, d.s_a, rows.data(), rows.size() * sizeof(uint32_t));
-        if (rc) return rc;
-        rc = ensure(d, d.s_tmp, R * 2 * N * sizeof(double));
-        if (rc) return rc;
-        HIPCHK(d, launch_fft_forward(tables(d), d.s_a.as<const uint32_t>(), d.s_tmp.as<double>(), R * 2, d.stream));
-        std::vector<uint32_t> tv(2 * N);
-        for (uint32_t x = 0; x < N; x++) {  // genTestvec (key.zig:134-145)
-            tv[x] = 0;
-            tv[N + x] = host::f64_to_torus(0.125);
-        }
-        rc = set_key_common(d, decomposition_offset(p), tv.data(), tv.data() + N);
-        if (rc) return rc;
-        HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), d.d_bk, R, d.stream));
-        rc = upload_ksk(d, ksk.data());
-        if (rc) return rc;
-        if (bsk_out)
-            HIPCHK(d, hipMemcpyAsync(bsk_out, d.s_tmp.p, R * 2 * N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCHK(d, hipStreamSynchronize(d.stream));
-        if (ksk_out) std::memcpy(ksk_out, ksk.data(), ksk.size() * sizeof(uint32_t));
-        return key_loaded(d, /*from_keygen*/ true);
-    });
-    return rc ? rc : broadcast_key(c);
 }
 
 }  // extern "C"
@@ -896,15 +794,12 @@ static int reencrypt_on(Device &d, const tfhe_gpu_reenc_key &key, size_t slot, c
     if (B == 0) return TFHE_OK;
     HIPCHK(d, hipSetDevice(d.device));
     const size_t w = tlwe0_words(d.P);
+    Io io{d, dev};
     int rc = ensure(d, d.s_a, B * w * 4 + KS_GEMM_INPUT_SLACK);  // the gemm form reads whole blocks of 8
+    if (!rc) rc = io.out(out, B * w * 4);
     if (rc) return rc;
-    if (dev) {
-        HIPCHK(d, hipMemcpyAsync(d.s_a.p, in, B * w * 4, hipMemcpyDeviceToDevice, d.stream));
-    } else {
-        rc = h2d(d, d.s_a, in, B * w * 4);
-        if (!rc) rc = ensure(d, d.s_out, B * w * 4);
-        if (rc) return rc;
-    }
+    if (dev) HIPCHK(d, hipMemcpyAsync(d.s_a.p, in, B * w * 4, hipMemcpyDeviceToDevice, d.stream));
+    else if ((rc = h2d(d, d.s_a, in, B * w * 4))) return rc;
     KsGemm G;
     if (k.key_gemm) {
         rc = ensure(d, d.s_kspart, ks_gemm_part_bytes(d.K, B, (int)d.P.n, (int)key.basebit));
@@ -912,9 +807,9 @@ static int reencrypt_on(Device &d, const tfhe_gpu_reenc_key &key, size_t slot, c
         G.kg = k.key_gemm;
         G.part = d.s_kspart.as<uint32_t>();
     }
-    HIPCHK(d, launch_reencrypt(d.K, (int)key.t, (int)key.basebit, d.s_a.as<const uint32_t>(), k.key,
-                               dev ? out : d.s_out.as<uint32_t>(), B, d.stream, d.opts, &d.last_ks, &G));
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * w * 4);
+    HIPCHK(d, launch_reencrypt(d.K, (int)key.t, (int)key.basebit, d.s_a.as<const uint32_t>(), k.key, out, B, d.stream,
+                               d.opts, &d.last_ks, &G));
+    return io.finish();
 }
 
 }  // namespace tfhe
@@ -973,7 +868,9 @@ int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t 
     if (const char *why = plan_circuit(n_inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires, d.circuit_pack != 0,
                                        device_cus(), level_cost, pl))
         return fail(d, TFHE_ERR_INVALID, why);
+    Io io{d, dev};
     int rc = upload_plan(d, pl, W, n_inputs, inputs, n_outputs, dev);
+    if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w1 * 4);  // room made by upload_plan
     if (rc) return rc;
     const auto &bs = pl.bs;
     const auto &nots = pl.nots;
@@ -998,13 +895,8 @@ int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t 
             sp += nn;
         }
     }
-    if (n_outputs)
-        HIPCHK(d, launch_tlwe_gather(d.K, wires, d_idx + ip, dev ? outputs : d.s_out.as<uint32_t>(), n_outputs, false,
-                                     d.stream));
-    if (!dev) {  // the host call waits: for its outputs, or without any for the work and the error word
-        rc = n_outputs ? d2h_sync(d, outputs, d.s_out.p, n_outputs * w1 * 4) : sync_check(d);
-        if (rc) return rc;
-    }
+    if (n_outputs) HIPCHK(d, launch_tlwe_gather(d.K, wires, d_idx + ip, outputs, n_outputs, false, d.stream));
+    if ((rc = io.finish())) return rc;
     if (levels_out) *levels_out = max_level;
     return TFHE_OK;
 }
@@ -1013,15 +905,14 @@ static int key_switch_on(Device &d, const uint32_t *in_lv1, uint32_t *out_lv0, s
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     if (B == 0) return TFHE_OK;
     HIPCHK(d, hipSetDevice(d.device));
-    const size_t w = tlwe0_words(d.P);
-    int rc = h2d(d, d.s_lv1, in_lv1, B * 1025 * 4);
-    if (!rc) rc = ensure(d, d.s_out, B * w * 4);
+    Io io{d, /*dev*/ false};
+    int rc = io.in(d.s_lv1, in_lv1, B * 1025 * 4);
+    if (!rc) rc = io.out(out_lv0, B * tlwe0_words(d.P) * 4);
     if (rc) return rc;
     KsGemm G;
     if ((rc = ks_gemm_args(d, B, G))) return rc;
-    HIPCHK(d, launch_key_switch(d.K, d.s_lv1.as<const uint32_t>(), d.d_ksk, d.s_out.as<uint32_t>(), B, d.stream,
-                                d.opts, &d.last_ks, &G));
-    return d2h_sync(d, out_lv0, d.s_out.p, B * w * 4);
+    HIPCHK(d, launch_key_switch(d.K, in_lv1, d.d_ksk, out_lv0, B, d.stream, d.opts, &d.last_ks, &G));
+    return io.finish();
 }
 
 }  // namespace tfhe
@@ -1032,7 +923,6 @@ int tfhe_gpu_gate_batch_dev(tfhe_gpu_ctx *c, const uint8_t *ops_dev, const uint3
                             uint32_t *out_dev, size_t B) {
     if (!c || (B && (!ops_dev || !a_dev || !b_dev || !out_dev))) return fail(c, TFHE_ERR_INVALID, "null argument");
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         return run_bootstrap_dev(d, ops_dev, a_dev, b_dev, nullptr, out_dev, B, RUN_BOOTSTRAP);
     });
 }
@@ -1040,7 +930,6 @@ int tfhe_gpu_gate_batch_dev(tfhe_gpu_ctx *c, const uint8_t *ops_dev, const uint3
 int tfhe_gpu_bootstrap_batch_dev(tfhe_gpu_ctx *c, const uint32_t *in_dev, uint32_t *out_dev, size_t B) {
     if (!c || (B && (!in_dev || !out_dev))) return fail(c, TFHE_ERR_INVALID, "null argument");
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         return run_bootstrap_dev(d, nullptr, in_dev, nullptr, nullptr, out_dev, B, RUN_BOOTSTRAP);
     });
 }
@@ -1050,7 +939,6 @@ int tfhe_gpu_bootstrap_lut_batch_dev(tfhe_gpu_ctx *c, const uint32_t *in_dev, co
     if (!c || !testvec_dev || (B && (!in_dev || !out_dev))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
         return run_bootstrap_dev(d, nullptr, in_dev, nullptr, testvec_dev, out_dev, B, RUN_BOOTSTRAP);
     });
@@ -1092,12 +980,12 @@ int tfhe_gpu_fft_forward_batch(tfhe_gpu_ctx *c, const uint32_t *in, double *out,
     if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        int rc = h2d(d, d.s_a, in, B * 1024 * 4);
-        if (!rc) rc = ensure(d, d.s_tmp, B * 1024 * 8);
+        Io io{d, /*dev*/ false};
+        int rc = io.in(d.s_a, in, B * 1024 * 4);
+        if (!rc) rc = io.out(out, B * 1024 * 8, d.s_tmp);
         if (rc) return rc;
-        HIPCHK(d, launch_fft_forward(tables(d), d.s_a.as<const uint32_t>(), d.s_tmp.as<double>(), B, d.stream));
-        return d2h_sync(d, out, d.s_tmp.p, B * 1024 * 8);
+        HIPCHK(d, launch_fft_forward(tables(d), in, out, B, d.stream));
+        return io.finish();
     });
 }
 
@@ -1105,12 +993,12 @@ int tfhe_gpu_fft_inverse_batch(tfhe_gpu_ctx *c, const double *in, uint32_t *out,
     if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        int rc = h2d(d, d.s_tmp, in, B * 1024 * 8);
-        if (!rc) rc = ensure(d, d.s_out, B * 1024 * 4);
+        Io io{d, /*dev*/ false};
+        int rc = io.in(d.s_tmp, in, B * 1024 * 8);
+        if (!rc) rc = io.out(out, B * 1024 * 4);
         if (rc) return rc;
-        HIPCHK(d, launch_fft_inverse(tables(d), d.s_tmp.as<const double>(), d.s_out.as<uint32_t>(), B, d.stream));
-        return d2h_sync(d, out, d.s_out.p, B * 1024 * 4);
+        HIPCHK(d, launch_fft_inverse(tables(d), in, out, B, d.stream));
+        return io.finish();
     });
 }
 
@@ -1118,14 +1006,13 @@ int tfhe_gpu_poly_mul_batch(tfhe_gpu_ctx *c, const uint32_t *a, const uint32_t *
     if (!c || (B && (!a || !b || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        int rc = h2d(d, d.s_a, a, B * 1024 * 4);
-        if (!rc) rc = h2d(d, d.s_b, b, B * 1024 * 4);
-        if (!rc) rc = ensure(d, d.s_out, B * 1024 * 4);
+        Io io{d, /*dev*/ false};
+        int rc = io.in(d.s_a, a, B * 1024 * 4);
+        if (!rc) rc = io.in(d.s_b, b, B * 1024 * 4);
+        if (!rc) rc = io.out(out, B * 1024 * 4);
         if (rc) return rc;
-        HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 1024,
-                                  d.s_out.as<uint32_t>(), B, d.stream));
-        return d2h_sync(d, out, d.s_out.p, B * 1024 * 4);
+        HIPCHK(d, launch_poly_mul(tables(d), a, b, 1024, out, B, d.stream));
+        return io.finish();
     });
 }
 
@@ -1134,15 +1021,15 @@ int tfhe_gpu_external_product_batch(tfhe_gpu_ctx *c, const double *trgsw_fft, ui
     if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         const size_t row_d = (size_t)2 * d.P.L * 2048;  // doubles per TRGSW
         const double *row = nullptr;
+        Io io{d, /*dev*/ false};
         int rc = TFHE_OK;
         if (trgsw_fft) {
-            rc = h2d(d, d.s_tmp, trgsw_fft, row_d * 8);
+            rc = io.in(d.s_tmp, trgsw_fft, row_d * 8);
             if (!rc) rc = ensure(d, d.s_tv, row_d * 8);
             if (rc) return rc;
-            HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), d.s_tv.as<double>(), 2 * d.P.L, d.stream));
+            HIPCHK(d, launch_bk_permute(d.K, trgsw_fft, d.s_tv.as<double>(), 2 * d.P.L, d.stream));
             row = d.s_tv.as<const double>();
             if (d.K.offset == 0) d.K.offset = decomposition_offset(d.P);  // no key loaded yet: the parameter set's
         } else {
@@ -1150,12 +1037,11 @@ int tfhe_gpu_external_product_batch(tfhe_gpu_ctx *c, const double *trgsw_fft, ui
             if (bk_index >= d.P.n) return fail(d, TFHE_ERR_INVALID, "bk_index >= n");
             row = d.d_bk + (size_t)bk_index * row_d;
         }
-        rc = h2d(d, d.s_a, in, B * 2048 * 4);
-        if (!rc) rc = ensure(d, d.s_out, B * 2048 * 4);
+        rc = io.in(d.s_a, in, B * 2048 * 4);
+        if (!rc) rc = io.out(out, B * 2048 * 4);
         if (rc) return rc;
-        HIPCHK(d, launch_external_product(d.K, tables(d), row, d.s_a.as<const uint32_t>(), d.s_out.as<uint32_t>(), B,
-                                          d.stream));
-        return d2h_sync(d, out, d.s_out.p, B * 2048 * 4);
+        HIPCHK(d, launch_external_product(d.K, tables(d), row, in, out, B, d.stream));
+        return io.finish();
     });
 }
 

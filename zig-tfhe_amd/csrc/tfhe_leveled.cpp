@@ -1,20 +1,17 @@
 // tfhe_leveled.cpp — the leveled half of the C ABI (include/tfhe_gpu.h):
-// TRLWE / TRGSW encryption, resident selector sets, CMUX, table lookup by a
-// CMUX tree, rotation by encrypted bits and the packed lookup built on both, and
-// sample extraction at any coefficient.  Host code; the
-// arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
+// resident selector sets, CMUX, table lookup by a CMUX tree, rotation by
+// encrypted bits and the packed lookup built on both, and sample extraction at
+// any coefficient (TRLWE / TRGSW encryption is in tfhe_encrypt.cpp).  Host code;
+// the arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
 // tfhe_kernels.hip.  Everything here runs on the context's first device and,
 // but for the key switch after an extraction, needs no cloud key.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
-#include <cmath>
-#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "host_math.hpp"
 #include "tfhe_ctx.hpp"
 
 using namespace tfhe;
@@ -37,11 +34,6 @@ constexpr size_t LOOKUP_SCRATCH_CAP = (size_t)256 << 20;
 constexpr uint32_t LOOKUP_MAX_K = 12;
 constexpr size_t TRLWE_BYTES = 2048 * sizeof(uint32_t);
 
-template <class F>
-static int on_device0(tfhe_gpu_ctx *c, F f) {
-    return lift(c, 0, f(c->dev[0]));
-}
-
 // The kernels' parameter block with the parameter set's own decomposition
 // offset (key.zig:121-131), whether or not a cloud key (which carries one) is loaded.
 static KParams leveled_params(const Device &d) {
@@ -50,64 +42,25 @@ static KParams leveled_params(const Device &d) {
     return K;
 }
 
-// TRLWELv1.encryptF64 (trlwe.zig:30-64) of R rows, row r from DefaultPrng(seeds[r]):
-// a uniform, b = gaussianTorus(f64ToTorus(mu), alpha) + a * s, the products on the
-// device (k_poly_mul) as in tfhe_gpu_keygen.  mu: R * N values, or NULL for zeros.
-// rows receives R TRLWELv1 (a then b).
-static int trlwe_encrypt_rows(Device &d, const uint32_t *key_lv1, const std::vector<uint64_t> &seeds, const double *mu,
-                              double alpha, uint32_t *rows) {
-    const size_t N = d.P.N, R = seeds.size();
-    std::vector<uint32_t> a_only(R * N);
-    for (size_t row = 0; row < R; row++) {
-        host::Rng r(seeds[row]);
-        uint32_t *a = rows + row * 2 * N, *b = a + N;
-        for (size_t x = 0; x < N; x++) a[x] = r.u32();
-        host::NormalDist nd(0.0, alpha);
-        for (size_t x = 0; x < N; x++) b[x] = host::gaussian_torus(mu ? host::f64_to_torus(mu[row * N + x]) : 0u, nd, r);
-        std::memcpy(a_only.data() + row * N, a, N * sizeof(uint32_t));
-    }
-    int rc = h2d(d, d.s_b, key_lv1, N * sizeof(uint32_t));
-    if (!rc) rc = h2d(d, d.s_a, a_only.data(), a_only.size() * sizeof(uint32_t));
-    if (!rc) rc = ensure(d, d.s_out, R * N * sizeof(uint32_t));
-    if (rc) return rc;
-    HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 0,
-                              d.s_out.as<uint32_t>(), R, d.stream));
-    std::vector<uint32_t> as(R * N);
-    rc = d2h_sync(d, as.data(), d.s_out.p, as.size() * sizeof(uint32_t));
-    if (rc) return rc;
-    for (size_t row = 0; row < R; row++) {
-        uint32_t *b = rows + row * 2 * N + N;
-        for (size_t x = 0; x < N; x++) b[x] += as[row * N + x];
-    }
-    return TFHE_OK;
-}
-
-// The set belongs to this context and its parameter set.
-static const char *set_mismatch(const tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set) {
-    if (set->ctx != c) return "the selector set was loaded on another context";
-    if (std::memcmp(&set->P, &c->P, sizeof(tfhe_params)) != 0) return "the selector set was loaded for another parameter set";
-    return nullptr;
-}
-
 // in0 / in1 / out: B TRLWELv1 each, host (dev = false: staged, synchronous) or device.
 static int cmux_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *in0, const uint32_t *in1,
                    uint32_t *out, size_t B, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
+    Io io{d, dev};
     int rc = h2d(d, d.s_cidx, sel, B * sizeof(uint32_t));
-    if (!rc && !dev) rc = h2d(d, d.s_a, in0, B * TRLWE_BYTES);
-    if (!rc && !dev) rc = h2d(d, d.s_b, in1, B * TRLWE_BYTES);
-    if (!rc && !dev) rc = ensure(d, d.s_out, B * TRLWE_BYTES);
+    if (!rc) rc = io.in(d.s_a, in0, B * TRLWE_BYTES);
+    if (!rc) rc = io.in(d.s_b, in1, B * TRLWE_BYTES);
+    if (!rc) rc = io.out(out, B * TRLWE_BYTES);
     if (rc) return rc;
     CmuxBatch b;
     b.sel_rows = set.rows;
     b.sel = d.s_cidx.as<const uint32_t>();
-    b.src0 = dev ? in0 : d.s_a.as<const uint32_t>();
-    b.src1 = dev ? in1 : d.s_b.as<const uint32_t>();
-    b.out = dev ? out : d.s_out.as<uint32_t>();
+    b.src0 = in0;
+    b.src1 = in1;
+    b.out = out;
     b.B = B;
     d.last_ks = "";
     HIPCHK(d, launch_cmux(leveled_params(d), tables(d), b, /*shared*/ false, d.stream, &d.last_br));
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * TRLWE_BYTES);
+    return io.finish();
 }
 
 // The CMUX tree (vertical packing): level j pairs entries 2i, 2i + 1 of level j - 1
@@ -120,7 +73,6 @@ static int cmux_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel
 //   level j > 0 reads slots 2g, 2g + 1 of the previous level's buffer for its item g.
 static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
                            const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
     const size_t entries = (size_t)1 << k, cnt0 = entries / 2, cnt1 = cnt0 / 2;
     const size_t chunk = std::min(Q, std::max<size_t>(1, LOOKUP_SCRATCH_CAP / (cnt0 * TRLWE_BYTES)));
     std::vector<size_t> sel_at(k);
@@ -145,22 +97,21 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
         idx[even_at + g] = (uint32_t)(2 * g);
         idx[odd_at + g] = (uint32_t)(2 * g + 1);
     }
+    Io io{d, dev};
     // hipMemcpyAsync stages a pageable source before it returns (upload_plan): idx may go
     int rc = h2d(d, d.s_lk_idx, idx.data(), idx.size() * sizeof(uint32_t));
     if (!rc && k > 1) rc = ensure(d, d.s_lk_a, chunk * cnt0 * TRLWE_BYTES);
     if (!rc && k > 2) rc = ensure(d, d.s_lk_b, chunk * cnt1 * TRLWE_BYTES);
-    if (!rc && !dev) rc = h2d(d, d.s_a, table, entries * TRLWE_BYTES);
-    if (!rc && !dev) rc = ensure(d, d.s_out, Q * TRLWE_BYTES);
+    if (!rc) rc = io.in(d.s_a, table, entries * TRLWE_BYTES);
+    if (!rc) rc = io.out(out, Q * TRLWE_BYTES);
     if (rc) return rc;
     const uint32_t *didx = d.s_lk_idx.as<const uint32_t>();
-    const uint32_t *tab = dev ? table : d.s_a.as<const uint32_t>();
-    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
     const KParams K = leveled_params(d);
     const DevTables T = tables(d);
     d.last_br = d.last_ks = "";
     for (size_t q0 = 0; q0 < Q; q0 += chunk) {
         const size_t nq = std::min(chunk, Q - q0);
-        const uint32_t *prev = tab;
+        const uint32_t *prev = table;
         for (uint32_t j = 0; j < k; j++) {
             const size_t cnt = cnt0 >> j;
             CmuxBatch b;
@@ -169,7 +120,7 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
             b.src0 = b.src1 = prev;
             b.i0 = didx + (j ? even_at : l0a_at);
             b.i1 = didx + (j ? odd_at : l0b_at);
-            b.out = j + 1 == k ? res + q0 * 2048 : (j & 1) ? d.s_lk_b.as<uint32_t>() : d.s_lk_a.as<uint32_t>();
+            b.out = j + 1 == k ? out + q0 * 2048 : (j & 1) ? d.s_lk_b.as<uint32_t>() : d.s_lk_a.as<uint32_t>();
             b.B = nq * cnt;
             // the workgroup form where 4 consecutive items share their selector (>= 4 pairs per
             // query; cnt is a power of two) unless TFHE_OPT_CMUX_FORM = 1 forces the per-wave form:
@@ -183,7 +134,7 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
             prev = b.out;
         }
     }
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, Q * TRLWE_BYTES);
+    return io.finish();
 }
 
 // h rotate-CMUX steps on B TRLWELv1 (k_rotate_chain), one launch: item g starts from src[i_src[g]]
@@ -213,15 +164,13 @@ static int rotate_launch_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint
 
 static int rotate_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
                      const uint32_t *in, uint32_t *out, size_t B, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
-    int rc = dev ? TFHE_OK : h2d(d, d.s_a, in, B * TRLWE_BYTES);
-    if (!rc && !dev) rc = ensure(d, d.s_out, B * TRLWE_BYTES);
+    Io io{d, dev};
+    int rc = io.in(d.s_a, in, B * TRLWE_BYTES);
+    if (!rc) rc = io.out(out, B * TRLWE_BYTES);
     if (rc) return rc;
     d.last_ks = "";
-    rc = rotate_launch_on(d, set, sel, rot, h, dev ? in : d.s_a.as<const uint32_t>(), nullptr,
-                          dev ? out : d.s_out.as<uint32_t>(), B, &d.last_br);
-    if (rc) return rc;
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * TRLWE_BYTES);
+    rc = rotate_launch_on(d, set, sel, rot, h, in, nullptr, out, B, &d.last_br);
+    return rc ? rc : io.finish();
 }
 
 // The packed lookup (tfhe_packed_lookup_plan): the CMUX tree over the 2^v table TRLWEs under address
@@ -230,123 +179,54 @@ static int rotate_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *s
 // the tree alone.
 static int packed_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
                             const tfhe_packed_plan &pl, const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
     const uint32_t h = pl.h, v = pl.v;
-    int rc = dev ? TFHE_OK : h2d(d, d.s_a, table, (size_t)pl.trlwes * TRLWE_BYTES);
-    if (!rc && !dev) rc = ensure(d, d.s_out, Q * TRLWE_BYTES);
+    Io io{d, dev};
+    int rc = io.in(d.s_a, table, (size_t)pl.trlwes * TRLWE_BYTES);
+    if (!rc) rc = io.out(out, Q * TRLWE_BYTES);
     if (!rc && v && h) rc = ensure(d, d.s_rot_in, Q * TRLWE_BYTES);
     if (rc) return rc;
-    const uint32_t *tab = dev ? table : d.s_a.as<const uint32_t>();
-    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
     d.last_br = d.last_ks = "";
-    if (v) {
+    if (v) {  // the table is on the device by now, staged or the caller's
         std::vector<uint32_t> hi(Q * v);
         for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.begin() + q * v);
-        rc = table_lookup_on(d, set, hi.data(), v, tab, h ? d.s_rot_in.as<uint32_t>() : res, Q, /*dev*/ true);
+        rc = table_lookup_on(d, set, hi.data(), v, table, h ? d.s_rot_in.as<uint32_t>() : out, Q, /*dev*/ true);
         if (rc) return rc;
     }
     if (h) {
         std::vector<uint32_t> lo(Q * h), first(v ? 0 : Q, 0u);
         for (size_t q = 0; q < Q; q++) std::copy(addr + q * k, addr + q * k + h, lo.begin() + q * h);
         // last_kernels: the tree's first level, then the chain
-        rc = rotate_launch_on(d, set, lo.data(), pl.rot, h, v ? d.s_rot_in.as<const uint32_t>() : tab,
-                              v ? nullptr : first.data(), res, Q, v ? &d.last_ks : &d.last_br);
+        rc = rotate_launch_on(d, set, lo.data(), pl.rot, h, v ? d.s_rot_in.as<const uint32_t>() : table,
+                              v ? nullptr : first.data(), out, Q, v ? &d.last_ks : &d.last_br);
         if (rc) return rc;
     }
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, Q * TRLWE_BYTES);
+    return io.finish();
 }
 
 static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *coef, size_t C, bool key_switch,
                              uint32_t *out, size_t B, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
     if (key_switch && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t items = B * C, wo = key_switch ? tlwe0_words(d.P) : (size_t)d.P.N + 1;
     if (items == 0) return TFHE_OK;
+    Io io{d, dev};
     int rc = h2d(d, d.s_cidx, coef, C * sizeof(uint32_t));
-    if (!rc && !dev) rc = h2d(d, d.s_a, trlwe, B * TRLWE_BYTES);
-    if (!rc && !dev) rc = ensure(d, d.s_out, items * wo * 4);
+    if (!rc) rc = io.in(d.s_a, trlwe, B * TRLWE_BYTES);
+    if (!rc) rc = io.out(out, items * wo * 4);
     if (!rc && key_switch) rc = ensure(d, d.s_lv1, items * 1025 * 4 + KS_GEMM_INPUT_SLACK);
     if (rc) return rc;
-    uint32_t *res = dev ? out : d.s_out.as<uint32_t>();
-    uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : res;
-    HIPCHK(d, launch_sample_extract(dev ? trlwe : d.s_a.as<const uint32_t>(), d.s_cidx.as<const uint32_t>(), C, lv1, B,
-                                    d.stream));
+    uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : out;
+    HIPCHK(d, launch_sample_extract(trlwe, d.s_cidx.as<const uint32_t>(), C, lv1, B, d.stream));
     if (key_switch) {
         KsGemm G;
         if ((rc = ks_gemm_args(d, items, G))) return rc;
-        HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, res, items, d.stream, d.opts, &d.last_ks, &G));
+        HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, items, d.stream, d.opts, &d.last_ks, &G));
     }
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, items * wo * 4);
+    return io.finish();
 }
 
 }  // namespace tfhe
 
 extern "C" {
-
-int tfhe_gpu_trlwe_encrypt_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const double *mu, double alpha, uint64_t seed0,
-                                 uint32_t *out, size_t B) {
-    if (!c || !key_lv1 || (B && (!mu || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        std::vector<uint64_t> seeds(B);
-        for (size_t i = 0; i < B; i++) seeds[i] = seed0 + i;
-        return trlwe_encrypt_rows(d, key_lv1, seeds, mu, alpha, out);
-    });
-}
-
-int tfhe_gpu_trlwe_decrypt_bool_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const uint32_t *ct, uint8_t *bits,
-                                      size_t B) {
-    if (!c || !key_lv1 || (B && (!ct || !bits))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (B == 0) return TFHE_OK;
-    return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        const size_t N = d.P.N;
-        std::vector<uint32_t> a_only(B * N), as(B * N);
-        for (size_t i = 0; i < B; i++) std::memcpy(a_only.data() + i * N, ct + i * 2 * N, N * sizeof(uint32_t));
-        int rc = h2d(d, d.s_b, key_lv1, N * sizeof(uint32_t));
-        if (!rc) rc = h2d(d, d.s_a, a_only.data(), a_only.size() * sizeof(uint32_t));
-        if (!rc) rc = ensure(d, d.s_out, B * N * sizeof(uint32_t));
-        if (rc) return rc;
-        HIPCHK(d, launch_poly_mul(tables(d), d.s_a.as<const uint32_t>(), d.s_b.as<const uint32_t>(), 0,
-                                  d.s_out.as<uint32_t>(), B, d.stream));
-        rc = d2h_sync(d, as.data(), d.s_out.p, as.size() * sizeof(uint32_t));
-        if (rc) return rc;
-        for (size_t i = 0; i < B; i++)
-            for (size_t x = 0; x < N; x++) bits[i * N + x] = (int32_t)(ct[i * 2 * N + N + x] - as[i * N + x]) >= 0;
-        return TFHE_OK;
-    });
-}
-
-int tfhe_gpu_trgsw_encrypt_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const uint32_t *mu, double alpha,
-                                 uint64_t seed0, double *out_fft, size_t S) {
-    if (!c || !key_lv1 || (S && (!mu || !out_fft))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (S == 0) return TFHE_OK;
-    return on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
-        const size_t N = d.P.N, L = d.P.L, R = S * 2 * L;
-        std::vector<uint64_t> seeds(R);
-        for (size_t s = 0; s < S; s++) {
-            host::Rng master(seed0 + s);
-            for (size_t r = 0; r < 2 * L; r++) seeds[s * 2 * L + r] = master.next();
-        }
-        std::vector<uint32_t> rows(R * 2 * N);
-        int rc = trlwe_encrypt_rows(d, key_lv1, seeds, nullptr, alpha, rows.data());
-        if (rc) return rc;
-        for (size_t s = 0; s < S; s++)
-            for (size_t l = 0; l < L; l++) {  // the gadget: a[0] of row l, b[0] of row L + l (trgsw.zig:35-71)
-                const uint32_t h = host::f64_to_torus(std::ldexp(1.0, -(int)((l + 1) * d.P.bgbit)));
-                rows[(s * 2 * L + l) * 2 * N] += mu[s] * h;
-                rows[(s * 2 * L + L + l) * 2 * N + N] += mu[s] * h;
-            }
-        // TRGSWLv1FFT.new (trgsw.zig:81-91): ifft of every a and b polynomial
-        rc = h2d(d, d.s_a, rows.data(), rows.size() * sizeof(uint32_t));
-        if (!rc) rc = ensure(d, d.s_tmp, R * 2 * N * sizeof(double));
-        if (rc) return rc;
-        HIPCHK(d, launch_fft_forward(tables(d), d.s_a.as<const uint32_t>(), d.s_tmp.as<double>(), R * 2, d.stream));
-        return d2h_sync(d, out_fft, d.s_tmp.p, R * 2 * N * sizeof(double));
-    });
-}
 
 int tfhe_gpu_trgsw_set_load(tfhe_gpu_ctx *c, const double *trgsw_fft, size_t S, tfhe_gpu_trgsw_set **out) {
     if (out) *out = nullptr;
@@ -356,7 +236,6 @@ int tfhe_gpu_trgsw_set_load(tfhe_gpu_ctx *c, const double *trgsw_fft, size_t S, 
     set->P = c->P;
     set->S = S;
     const int rc = on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         const size_t rows = S * 2 * d.P.L, bytes = rows * 2048 * sizeof(double);
         int rc = h2d(d, d.s_tmp, trgsw_fft, bytes);
         if (rc) return rc;
@@ -376,7 +255,7 @@ void tfhe_gpu_trgsw_set_destroy(tfhe_gpu_trgsw_set *set) { delete set; }
 static int cmux_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *sel, const uint32_t *in0,
                       const uint32_t *in1, uint32_t *out, size_t B, bool dev) {
     if (!c || !set || (B && (!sel || !in0 || !in1 || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
     for (size_t i = 0; i < B; i++)
         if (sel[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "selector index >= the set's size");
     if (B == 0) return TFHE_OK;
@@ -397,7 +276,7 @@ static int lookup_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const ui
                         const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
     if (!c || !set || !table || (Q && (!addr || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (k < 1 || k > LOOKUP_MAX_K) return fail(c, TFHE_ERR_INVALID, "table lookup: k outside 1..12");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
     if (Q > 0xFFFFFFFFull >> k) return fail(c, TFHE_ERR_INVALID, "table lookup: too many queries");
     for (size_t i = 0; i < Q * k; i++)
         if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");
@@ -422,7 +301,7 @@ static int rotate_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const ui
     if (h < 1 || h > TFHE_ROTATE_MAX_STEPS) return fail(c, TFHE_ERR_INVALID, "rotate by bits: h outside 1..32");
     for (uint32_t j = 0; j < h; j++)
         if (rot[j] > 2 * c->P.N) return fail(c, TFHE_ERR_INVALID, "rotate by bits: exponent > 2N");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
     if (B > 0xFFFFFFFFull / h) return fail(c, TFHE_ERR_INVALID, "rotate by bits: too many items");
     for (size_t i = 0; i < B * h; i++)
         if (sel[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "selector index >= the set's size");
@@ -447,7 +326,7 @@ static int packed_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const ui
     tfhe_packed_plan pl;
     if (tfhe_packed_lookup_plan(&c->P, k, width, &pl) != TFHE_OK)
         return fail(c, TFHE_ERR_INVALID, "packed lookup: width outside 1..N, k = 0, or more than 12 address bits left to the tree");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
     if (Q > 0xFFFFFFFFull >> pl.v) return fail(c, TFHE_ERR_INVALID, "packed lookup: too many queries");
     for (size_t i = 0; i < Q * k; i++)
         if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");

@@ -26,17 +26,6 @@ struct tfhe_gpu_lut_set {
 
 namespace tfhe {
 
-template <class F>
-static int on_device0(tfhe_gpu_ctx *c, F f) {
-    return lift(c, 0, f(c->dev[0]));
-}
-
-static const char *set_mismatch(const tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set) {
-    if (set->ctx != c) return "the LUT set was loaded on another context";
-    if (std::memcmp(&set->P, &c->P, sizeof(tfhe_params)) != 0) return "the LUT set was loaded for another parameter set";
-    return nullptr;
-}
-
 // Descriptor arrays of one call, concatenated into one upload (u32 words; the
 // coefficients keep their bits): where each starts in the device copy.
 struct DescBlob {
@@ -54,32 +43,30 @@ struct DescBlob {
 static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, size_t P, const uint32_t *term_off,
                         const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut,
                         uint32_t *out, size_t B, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t w = tlwe0_words(d.P), terms = term_off[B];
     DescBlob blob;
     const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
                  coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B);
+    Io io{d, dev};
     // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
     int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
-    if (!rc && !dev && terms) rc = h2d(d, d.s_a, pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
-    if (!rc && !dev) rc = ensure(d, d.s_out, B * w * 4);
+    if (!rc && terms) rc = io.in(d.s_a, pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
+    if (!rc) rc = io.out(out, B * w * 4);
     if (!rc) rc = ensure(d, d.s_lut_x, B * w * 4);
     if (rc) return rc;
     const uint32_t *desc = d.s_cidx.as<const uint32_t>();
-    uint32_t *x = d.s_lut_x.as<uint32_t>(), *res = dev ? out : d.s_out.as<uint32_t>();
-    HIPCHK(d, launch_lut_combine(d.K, dev ? pool : d.s_a.as<const uint32_t>(), desc + off_at, desc + src_at,
-                                 reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at, x, B, d.stream));
-    rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, res, B, RUN_BOOTSTRAP, nullptr, desc + lut_at);
-    if (rc) return rc;
-    return dev ? TFHE_OK : d2h_sync(d, out, d.s_out.p, B * w * 4);
+    uint32_t *x = d.s_lut_x.as<uint32_t>();
+    HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
+                                 desc + konst_at, x, B, d.stream));
+    rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, out, B, RUN_BOOTSTRAP, nullptr, desc + lut_at);
+    return rc ? rc : io.finish();
 }
 
 // A whole LUT circuit: one combine and one bootstrap launch per level into the
 // wire table (d.s_wires, in the plan's slot order), the outputs gathered at the end.
 static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
                           const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev) {
-    HIPCHK(d, hipSetDevice(d.device));
     if (n_nodes && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t w = tlwe0_words(d.P), W = n_inputs + n_nodes;
     size_t widest = 0;
@@ -88,11 +75,12 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     const size_t off_at = blob.add(pl.off.data(), pl.off.size()), src_at = blob.add(pl.src.data(), pl.src.size()),
                  coef_at = blob.add(pl.coef.data(), pl.coef.size()), konst_at = blob.add(pl.konst.data(), n_nodes),
                  lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs);
+    Io io{d, dev};
     int rc = ensure(d, d.s_wires, std::max<size_t>(W, 1) * w * 4);
     // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
     if (!rc && !blob.words.empty()) rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
     if (!rc) rc = ensure(d, d.s_lut_x, std::max<size_t>(widest, 1) * w * 4);
-    if (!rc && !dev) rc = ensure(d, d.s_out, std::max<size_t>(n_outputs, 1) * w * 4);
+    if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w * 4);
     if (rc) return rc;
     if (n_inputs)
         HIPCHK(d, hipMemcpyAsync(d.s_wires.p, inputs, n_inputs * w * 4,
@@ -109,11 +97,8 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
                                desc + lut_at + at);
         if (rc) return rc;
     }
-    if (n_outputs)
-        HIPCHK(d, launch_tlwe_gather(d.K, wires, desc + out_at, dev ? outputs : d.s_out.as<uint32_t>(), n_outputs, false,
-                                     d.stream));
-    if (dev) return TFHE_OK;
-    return n_outputs ? d2h_sync(d, outputs, d.s_out.p, n_outputs * w * 4) : sync_check(d);
+    if (n_outputs) HIPCHK(d, launch_tlwe_gather(d.K, wires, desc + out_at, outputs, n_outputs, false, d.stream));
+    return io.finish();
 }
 
 static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
@@ -121,7 +106,7 @@ static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint3
                        const uint32_t *lut, uint32_t *out, size_t B, bool dev) {
     if (!c || !set || (B && (!term_off || !konst || !lut || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
     if (B == 0) return TFHE_OK;
     if (B > 0xFFFFFFFFull || P > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "LUT batch: too many nodes or ciphertexts");
     if (term_off[B] && (!term_src || !term_coef || !pool)) return fail(c, TFHE_ERR_INVALID, "null argument");
@@ -140,7 +125,7 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
         (n_outputs && (!out_wires || !outputs)))
         return fail(c, TFHE_ERR_INVALID, "null argument");
     if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
-    if (const char *why = set_mismatch(c, set)) return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
     if (n_nodes && term_off[n_nodes] && (!term_wire || !term_coef)) return fail(c, TFHE_ERR_INVALID, "null argument");
     LutCircuitPlan pl;
     if (const char *why = plan_lut_circuit(n_inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, set->T,
@@ -164,7 +149,6 @@ int tfhe_gpu_lut_set_load(tfhe_gpu_ctx *c, const uint32_t *testvecs, size_t T, t
     set->P = c->P;
     set->T = T;
     const int rc = on_device0(c, [&](Device &d) -> int {
-        HIPCHK(d, hipSetDevice(d.device));
         const size_t bytes = T * 2 * d.P.N * sizeof(uint32_t);
         if (hipMalloc((void **)set->tables.make(d.device), bytes) != hipSuccess)
             return fail(d, TFHE_ERR_OOM, "hipMalloc(LUT set)");
