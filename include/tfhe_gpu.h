@@ -35,7 +35,9 @@ extern "C" {
                                    sample extraction, tfhe_lookup_table_pack_bits), TFHE_OPT_CMUX_FORM, the
                                    LUT-circuit entries (LUT sets, tfhe_gpu_lut_apply_*, tfhe_gpu_lut_circuit_eval*,
                                    tfhe_lut_circuit_schedule) and the packed lookup (tfhe_gpu_rotate_by_bits_*,
-                                   tfhe_gpu_packed_lookup_*, tfhe_packed_lookup_plan, tfhe_lookup_table_pack_slots);
+                                   tfhe_gpu_packed_lookup_*, tfhe_packed_lookup_plan, tfhe_lookup_table_pack_slots)
+                                   and the packing key switch (tfhe_gpu_packing_key_*, tfhe_gpu_pack_tlwe_*,
+                                   tfhe_pack_tlwe, TFHE_OPT_PACK_SCRATCH_MB);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -216,12 +218,15 @@ enum {
                                      pageable copies 52.9 GB/s in total against 47.2 staged, and the one-card
                                      8-shard step 54.5 vs 56.6 ms, so staging is for hosts whose pageable
                                      copies serialise */
-    TFHE_OPT_CMUX_FORM = 18       /* table lookup's CMUX levels: 0 auto (default: the measured-faster form, which
+    TFHE_OPT_CMUX_FORM = 18,      /* table lookup's CMUX levels: 0 auto (default: the measured-faster form, which
                                      is 2: 4.8 vs 9.6 ms per 1,024 lookups of a 256-entry table, DESIGN.md
                                      §4.8), 1 one wavefront per CMUX, each reading its selector from L2, 2 where
                                      a level has >= 4 pairs per query, workgroups of 4 CMUXes that stage their
                                      shared selector's rows in LDS once.  Same words either way;
                                      tfhe_gpu_last_kernels names what the last lookup ran */
+    TFHE_OPT_PACK_SCRATCH_MB = 19 /* packing key switch: bound in MB on the context scratch that holds a chunk's
+                                     GEMM sums, 1..256 (default 256).  Same words at any value; tests lower it to
+                                     run a small batch in several chunks */
 };
 enum { TFHE_STAGING_PAGEABLE = 0, TFHE_STAGING_PINNED = 1 };  /* TFHE_OPT_HOST_STAGING */
 /* TFHE_ARITH_AUTO (default): at the L=3 / Bg=2^6 sets the blind rotation
@@ -483,6 +488,47 @@ int tfhe_gpu_sample_extract_batch(tfhe_gpu_ctx *ctx, const uint32_t *trlwe, cons
                                   int key_switch, uint32_t *out, size_t B);
 int tfhe_gpu_sample_extract_dev(tfhe_gpu_ctx *ctx, const uint32_t *trlwe_dev, const uint32_t *coef, size_t C,
                                 int key_switch, uint32_t *out_dev, size_t B);
+
+/* ---- Packing key switch: TLWELv0 -> a coefficient slot of a TRLWELv1 --------
+ * The way from the bootstrapped half (gates, circuits, LUT bootstraps: TLWELv0) into the leveled half (CMUX, table
+ * lookup, packed lookup: TRLWELv1 tables): the public key switch of identityKeySwitching (trgsw.zig:471-502) and
+ * reencryptTLWELv0 with a key whose rows are TRLWELv1.  Shape (basebit, t), base = 2^basebit: n*t*base rows of 2N
+ * words, row[base*t*i + base*j + k] for k >= 1 = TRLWELv1.encryptF64 (trlwe.zig:30-64) under key_lv1 of the
+ * polynomial whose coefficient 0 is (f64)k * (f64)key_lv0[i] / (f64)(1 << ((j+1)*basebit)) (key.zig:164) and whose
+ * other coefficients are 0.0, with alpha and DefaultPrng(seed0 + idx): the words tfhe_gpu_trlwe_encrypt_batch gives
+ * for that mu and seed.  Rows with k = 0 are zero.
+ * Pack: B*C TLWELv0 in[b*C + c] and C distinct coefficients coef[] (HOST array, each < N, shared by the batch, as in
+ * tfhe_gpu_sample_extract_*) give B TRLWELv1.  With PREC = 1 << (32 - (1 + basebit*t)), a'_i = a_i + PREC and
+ * d_ij = (a'_i >> (32 - (j+1)*basebit)) & (base - 1), in wrapping u32 arithmetic on all 2N words,
+ *     R    = (a = 0, b = (in.b, 0, ..., 0)) - sum_{i<n, j<t} row[base*t*i + base*j + d_ij]
+ *     out[b] = sum_c X^coef[c] * R_{b,c}     (polyMulWithXK, trgsw.zig:442-466, on the a half and on the b half)
+ * so the phase of out[b] at coefficient coef[c] is that of in[b*C + c] plus key-switch noise, and the other
+ * coefficients hold noise only: a gate output (+-1/8) becomes a table bit in the encoding of
+ * tfhe_lookup_table_pack_bits / _pack_slots, a LUT output keeps its message.  Integer-exact: one defined word pattern.
+ * Shapes: those with the one-hot GEMM form, basebit 2 with t 7..9 and basebit 5 with t 2..3; TFHE_ERR_INVALID
+ * otherwise, and TFHE_OPT_KS_FORM does not apply (there is one form).  TFHE_ERR_INVALID too, before any launch or
+ * upload: len != n*t*base*2N, C = 0 or > N, a coef >= N or listed twice, a key of another context, a null argument.
+ * B = 0 is TFHE_OK.  Like the leveled entries these run on the context's first device and need no cloud key; _dev
+ * takes in / out in HBM, is asynchronous on the context stream and refuses a multi-device context.
+ * After tfhe_gpu_packing_key_load only the matrix-core layout of the key stays resident (n'*t*base*2N*4 bytes with
+ * n' = n rounded up to blocks of 8 (basebit 2) or 4 (basebit 5): 184.5 MB at the 128-bit set with (2, 8), 644.9 MB at
+ * UINT4 with (5, 3)); the u32 rows are staged in HBM and freed.  The
+ * per-item GEMM sums (K splits x items x 2N words) live in context scratch: a batch runs in chunks of items that
+ * keep them within TFHE_OPT_PACK_SCRATCH_MB (default 256 MB, the table lookup's bound). */
+/* host rows: n*t*2^basebit*2N words; needs a context for the poly_mul of each TRLWE encryption */
+int  tfhe_gpu_packing_key_gen(tfhe_gpu_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
+                              uint32_t basebit, uint32_t t, uint64_t seed0, uint32_t *rows);
+typedef struct tfhe_gpu_packing_key tfhe_gpu_packing_key;
+int  tfhe_gpu_packing_key_load(tfhe_gpu_ctx *ctx, const uint32_t *rows, size_t len /*words*/, uint32_t basebit,
+                               uint32_t t, tfhe_gpu_packing_key **out);
+void tfhe_gpu_packing_key_destroy(tfhe_gpu_packing_key *key);
+int  tfhe_gpu_pack_tlwe_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *key, const uint32_t *in /*B*C*(n+1)*/,
+                              const uint32_t *coef /*C, host*/, size_t C, uint32_t *out_trlwe /*B*2N*/, size_t B);
+int  tfhe_gpu_pack_tlwe_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *key, const uint32_t *in_dev,
+                            const uint32_t *coef /*C, host*/, size_t C, uint32_t *out_dev, size_t B);
+/* host only, no device: the definition above, for callers without a GPU */
+int  tfhe_pack_tlwe(const tfhe_params *params, const uint32_t *rows, uint32_t basebit, uint32_t t, const uint32_t *in,
+                    const uint32_t *coef, size_t C, uint32_t *out_trlwe, size_t B);
 
 /* ---- LUT circuits: per-item tables and linear combinations on the device ----
  * The unit of work of multi-bit arithmetic (radix digits, comparisons, bivariate functions through a + m*b): a small

@@ -11,7 +11,8 @@
 //                        (reencryptTLWELv0 on the GPU)
 //   trlwe.zig         -> tfhe::TRLWELv1 (encryptF64 / encryptBool / decryptBool, sampleExtractIndex)
 //   trgsw.zig         -> tfhe::TRGSWLv1FFT::encryptTorus (encryptTorus + TRGSWLv1FFT.new), tfhe::cmux, tfhe::rotateByBits,
-//                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits)
+//                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits),
+//                        tfhe::PackingKey / tfhe::packTlwe (identityKeySwitching's arithmetic with TRLWE rows)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
 #pragma once
@@ -398,6 +399,10 @@ inline TRLWELv1 rotateByBits(const TRLWELv1 &in, const std::vector<uint32_t> &ro
     return out;
 }
 
+class PackingKey;  // below
+inline std::vector<TRLWELv1> packTlwe(const CloudKey &ck, const PackingKey &key, const std::vector<TLWELv0> &in,
+                               const std::vector<uint32_t> &coef);
+
 // A table of 2^k entries of `width` bits packed side by side into 2^v TRLWELv1 (tfhe_packed_lookup_plan) and addressed
 // by k TRGSW-encrypted bits per query: the CMUX tree under the high v bits, then the rotation under the low h
 // (tfhe_gpu_packed_lookup_batch), (2^v - 1) + h CMUXes.  TableLookup::extractBits at 0 .. width-1 makes gate inputs.
@@ -415,6 +420,21 @@ struct PackedTableLookup {
         check(tfhe_lookup_table_pack_slots(&p, values.data(), t.k, width, t.table.data()), "pack_slots");
         return t;
     }
+    // the same table from 2^k * width ciphertexts computed on the server (entry-major, then bit), by one
+    // packTlwe call: B = plan.trlwes, coef[s * width + c] = s * stride + c
+    static PackedTableLookup fromCiphertexts(const CloudKey &ck, const PackingKey &key, const std::vector<TLWELv0> &cts,
+                                             uint32_t k, uint32_t width) {
+        PackedTableLookup t;
+        t.k = k;
+        t.width = width;
+        check(tfhe_packed_lookup_plan(&ck.params(), k, width, &t.plan), "packed_lookup_plan");
+        if (cts.size() != (size_t)width << k) throw Error(TFHE_ERR_INVALID, "PackedTableLookup: 2^k * width ciphertexts");
+        std::vector<uint32_t> coef;
+        for (uint32_t s = 0; s < 1u << t.plan.h; s++)
+            for (uint32_t c = 0; c < width; c++) coef.push_back(s * t.plan.stride + c);
+        for (const TRLWELv1 &x : packTlwe(ck, key, cts, coef)) t.table.insert(t.table.end(), x.p.begin(), x.p.end());
+        return t;
+    }
     // addr[q * k + j]: the selector of `set` that encrypts bit j (least significant first) of query q's address
     std::vector<TRLWELv1> lookup(const CloudKey &ck, const TrgswSet &set, const std::vector<uint32_t> &addr) const {
         const size_t Q = addr.size() / k, w = 2 * (size_t)ck.params().N;
@@ -426,6 +446,48 @@ struct PackedTableLookup {
         return r;
     }
 };
+
+// The packing key (tfhe_gpu_packing_key) of the TLWELv0 -> TRLWELv1 key switch, resident on `ck`'s context:
+// generated from the secret key (tfhe_gpu_packing_key_gen, row idx from DefaultPrng(seed0 + idx)) or loaded
+// from host rows.  Shapes: basebit 2 with t 7..9, basebit 5 with t 2..3.
+class PackingKey {
+  public:
+    PackingKey(const CloudKey &ck, const std::vector<Torus> &rows, uint32_t basebit, uint32_t t) : basebit_(basebit), t_(t) {
+        tfhe_gpu_packing_key *h = nullptr;
+        check(tfhe_gpu_packing_key_load(ck.ctx(), rows.data(), rows.size(), basebit, t, &h), "packing_key_load", ck.ctx());
+        key_.reset(h, tfhe_gpu_packing_key_destroy);
+    }
+    static PackingKey generate(const CloudKey &ck, const SecretKey &sk, uint64_t seed0, double alpha, uint32_t basebit,
+                               uint32_t t) {
+        const tfhe_params &p = ck.params();
+        std::vector<Torus> rows(((size_t)p.n * t << basebit) * 2 * p.N);
+        check(tfhe_gpu_packing_key_gen(ck.ctx(), sk.key_lv0.data(), sk.key_lv1.data(), alpha, basebit, t, seed0, rows.data()),
+              "packing_key_gen", ck.ctx());
+        return PackingKey(ck, rows, basebit, t);
+    }
+    const tfhe_gpu_packing_key *get() const { return key_.get(); }
+    uint32_t basebit() const { return basebit_; }
+    uint32_t t() const { return t_; }
+
+  private:
+    std::shared_ptr<tfhe_gpu_packing_key> key_;
+    uint32_t basebit_ = 0, t_ = 0;
+};
+
+// tfhe_gpu_pack_tlwe_batch: in[b * C + c] goes to coefficient coef[c] (distinct, each < N) of output b;
+// in.size() = B * coef.size().  A gate output (+-1/8) becomes a table bit of TableLookup / PackedTableLookup.
+inline std::vector<TRLWELv1> packTlwe(const CloudKey &ck, const PackingKey &key, const std::vector<TLWELv0> &in,
+                                      const std::vector<uint32_t> &coef) {
+    const size_t C = coef.size(), w = ck.params().n + 1, W = 2 * (size_t)ck.params().N;
+    if (C == 0 || in.size() % C) throw Error(TFHE_ERR_INVALID, "packTlwe: B * C inputs for C coefficients");
+    const size_t B = in.size() / C;
+    std::vector<Torus> x(in.size() * w), out(B * W);
+    for (size_t k = 0; k < in.size(); k++) std::copy(in[k].p.begin(), in[k].p.end(), x.begin() + k * w);
+    check(tfhe_gpu_pack_tlwe_batch(ck.ctx(), key.get(), x.data(), coef.data(), C, out.data(), B), "pack_tlwe", ck.ctx());
+    std::vector<TRLWELv1> r(B);
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * W, out.begin() + (b + 1) * W, r[b].p.begin());
+    return r;
+}
 
 // reencryptTLWELv0 (proxy_reenc.zig:267-306) on the GPU: the key is uploaded once to HBM; a
 // context of its own (no cloud key needed).

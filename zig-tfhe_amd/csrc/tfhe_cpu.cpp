@@ -400,6 +400,25 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     return nullptr;
 }
 
+// ---- Packing key switch: the argument checks shared with the device path ----
+bool pack_shape_ok(uint32_t basebit, uint32_t t) {
+    return (basebit == 2 && t >= 7 && t <= 9) || (basebit == 5 && t >= 2 && t <= 3);
+}
+size_t pack_key_words(const tfhe_params &p, uint32_t basebit, uint32_t t) {
+    return (size_t)p.n * t * ((size_t)1 << basebit) * 2 * p.N;
+}
+const char *check_pack_args(const tfhe_params &p, uint32_t basebit, uint32_t t, const uint32_t *coef, size_t C) {
+    if (!pack_shape_ok(basebit, t)) return "pack: (basebit, t) has no GEMM form (basebit 2: t 7..9, basebit 5: t 2..3)";
+    if (C == 0 || C > p.N) return "pack: C outside 1..N";
+    std::vector<bool> seen(p.N, false);
+    for (size_t c = 0; c < C; c++) {
+        if (coef[c] >= p.N) return "pack: coefficient index >= N";
+        if (seen[coef[c]]) return "pack: a coefficient is listed twice";
+        seen[coef[c]] = true;
+    }
+    return nullptr;
+}
+
 }  // namespace tfhe
 
 using namespace tfhe;
@@ -733,6 +752,43 @@ int tfhe_lookup_table_pack_slots(const tfhe_params *p, const uint64_t *values, u
     for (size_t e = 0; e < entries; e++) {
         uint32_t *b = table + (e >> pl.h) * 2 * N + N + (e & (((size_t)1 << pl.h) - 1)) * pl.stride;
         for (uint32_t c = 0; c < width; c++) b[c] = ((values[e] >> c) & 1u) ? plus : minus;
+    }
+    return TFHE_OK;
+}
+
+// The packing key switch on the host (include/tfhe_gpu.h): per item R = (0, (b, 0, ..)) - sum_{i,j}
+// row[base t i + base j + digit j of a_i + PREC], then out[b] += X^coef[c] R on each half.
+int tfhe_pack_tlwe(const tfhe_params *p, const uint32_t *rows, uint32_t basebit, uint32_t t, const uint32_t *in,
+                   const uint32_t *coef, size_t C, uint32_t *out_trlwe, size_t B) {
+    std::string why;
+    if (!params_ok(p, why) || !rows || !coef || (B && (!in || !out_trlwe))) return TFHE_ERR_INVALID;
+    if (check_pack_args(*p, basebit, t, coef, C)) return TFHE_ERR_INVALID;
+    const size_t N = p->N, n = p->n, base = (size_t)1 << basebit;
+    const uint32_t prec = 1u << (32 - (1 + basebit * t));
+    std::vector<uint32_t> R(2 * N);
+    for (size_t b = 0; b < B; b++) {
+        uint32_t *o = out_trlwe + b * 2 * N;
+        std::memset(o, 0, 2 * N * sizeof(uint32_t));
+        for (size_t c = 0; c < C; c++) {
+            const uint32_t *x = in + (b * C + c) * (n + 1);
+            std::fill(R.begin(), R.end(), 0u);
+            R[N] = x[n];
+            for (size_t i = 0; i < n; i++) {
+                const uint32_t abar = x[i] + prec;
+                for (uint32_t j = 0; j < t; j++) {
+                    const uint32_t d = (abar >> (32 - (j + 1) * basebit)) & (uint32_t)(base - 1);
+                    const uint32_t *row = rows + (base * t * i + base * j + d) * 2 * N;
+                    for (size_t w = 0; w < 2 * N; w++) R[w] -= row[w];
+                }
+            }
+            const size_t k = coef[c];
+            for (size_t half = 0; half < 2; half++) {
+                const uint32_t *r = R.data() + half * N;
+                uint32_t *oh = o + half * N;
+                for (size_t q = 0; q < N - k; q++) oh[q + k] += r[q];
+                for (size_t q = N - k; q < N; q++) oh[q + k - N] -= r[q];
+            }
+        }
     }
     return TFHE_OK;
 }

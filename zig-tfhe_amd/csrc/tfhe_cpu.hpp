@@ -94,6 +94,15 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
                              size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl);
 
+// ---- Packing key switch (tfhe_pack_tlwe here; tfhe_pack.cpp runs it on the device) ----
+// The shapes with the one-hot GEMM form (ks_gemm_supported, tfhe_kernels.hip): basebit 2 with
+// t 7..9, basebit 5 with t 2..3.
+bool pack_shape_ok(uint32_t basebit, uint32_t t);
+size_t pack_key_words(const tfhe_params &p, uint32_t basebit, uint32_t t);  // n * t * 2^basebit rows of 2N
+// nullptr, or what is wrong with a pack call's shape and coefficient list (C outside 1..N, a
+// coefficient >= N or listed twice)
+const char *check_pack_args(const tfhe_params &p, uint32_t basebit, uint32_t t, const uint32_t *coef, size_t C);
+
 // Device d's contiguous slice of B items over D devices: ceil(B/D) each, the
 // last non-empty one ragged, the ones after it empty.
 struct Slice {

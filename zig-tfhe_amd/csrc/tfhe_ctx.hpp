@@ -171,6 +171,7 @@ struct Device {
     // kernel-form options (tfhe_gpu_set_option) and what the last launch ran
     LaunchOpts opts{};
     int64_t circuit_pack = 1;
+    int64_t pack_scratch_mb = 256;  // TFHE_OPT_PACK_SCRATCH_MB: bound on the packing key switch's GEMM sums per chunk
     int64_t twiddle_source = TFHE_TWIDDLES_GLIBC;
     bool key_from_keygen = false;  // the resident BK was transformed with this device's tables
     double bk_absmax = 0.0;        // largest |BK spectrum component| of the resident key, reference scale

@@ -33,9 +33,10 @@ static int mul_by_key(Device &d, const uint32_t *key_lv1, const uint32_t *a, uin
 
 // TRLWELv1.encryptF64 (trlwe.zig:30-64) of R rows, row r from DefaultPrng(seeds[r]):
 // a uniform, b = gaussianTorus(f64ToTorus(mu), alpha) + a * s.  mu: R * N values, or
-// NULL for zeros.  rows receives R TRLWELv1 (a then b).
+// NULL for zeros but for coefficient 0 of row r, which is mu0[r] (mu0 NULL: zero too).
+// rows receives R TRLWELv1 (a then b).
 static int trlwe_encrypt_rows(Device &d, const uint32_t *key_lv1, const std::vector<uint64_t> &seeds, const double *mu,
-                              double alpha, uint32_t *rows) {
+                              double alpha, uint32_t *rows, const double *mu0 = nullptr) {
     const size_t N = d.P.N, R = seeds.size();
     std::vector<uint32_t> a_only(R * N), as(R * N);
     for (size_t row = 0; row < R; row++) {
@@ -43,7 +44,10 @@ static int trlwe_encrypt_rows(Device &d, const uint32_t *key_lv1, const std::vec
         uint32_t *a = rows + row * 2 * N, *b = a + N;
         for (size_t x = 0; x < N; x++) a[x] = r.u32();
         host::NormalDist nd(0.0, alpha);
-        for (size_t x = 0; x < N; x++) b[x] = host::gaussian_torus(mu ? host::f64_to_torus(mu[row * N + x]) : 0u, nd, r);
+        for (size_t x = 0; x < N; x++) {
+            const double m = mu ? mu[row * N + x] : (mu0 && x == 0) ? mu0[row] : 0.0;
+            b[x] = host::gaussian_torus(host::f64_to_torus(m), nd, r);
+        }
         std::memcpy(a_only.data() + row * N, a, N * sizeof(uint32_t));
     }
     const int rc = mul_by_key(d, key_lv1, a_only.data(), as.data(), R);
@@ -108,6 +112,47 @@ int tfhe_gpu_trlwe_decrypt_bool_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, 
         for (size_t i = 0; i < B; i++)
             for (size_t x = 0; x < N; x++) bits[i * N + x] = (int32_t)(ct[i * 2 * N + N + x] - as[i * N + x]) >= 0;
         return TFHE_OK;
+    });
+}
+
+// The packing key (include/tfhe_gpu.h): row idx = base t i + base j + k, k >= 1, encrypts the polynomial
+// whose coefficient 0 is k key_lv0[i] / 2^((j+1) basebit) (key.zig:164) from DefaultPrng(seed0 + idx); the
+// k = 0 rows are zero.  The rows to encrypt go through trlwe_encrypt_rows in runs of PACK_GEN_ROWS, each with
+// its coefficient-0 plaintext only.
+int tfhe_gpu_packing_key_gen(tfhe_gpu_ctx *c, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
+                             uint32_t basebit, uint32_t t, uint64_t seed0, uint32_t *rows) {
+    if (!c || !key_lv0 || !key_lv1 || !rows) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (!pack_shape_ok(basebit, t))
+        return fail(c, TFHE_ERR_INVALID, "packing key: (basebit, t) has no GEMM form (basebit 2: t 7..9, basebit 5: t 2..3)");
+    return on_device0(c, [&](Device &d) -> int {
+        constexpr size_t PACK_GEN_ROWS = 2048;
+        const size_t N = d.P.N, n = d.P.n, base = (size_t)1 << basebit, total = n * t * base;
+        std::memset(rows, 0, total * 2 * N * sizeof(uint32_t));
+        std::vector<uint64_t> seeds;
+        std::vector<double> mu0;
+        std::vector<size_t> at;
+        std::vector<uint32_t> run(PACK_GEN_ROWS * 2 * N);
+        auto flush = [&]() -> int {
+            if (seeds.empty()) return TFHE_OK;
+            const int rc = trlwe_encrypt_rows(d, key_lv1, seeds, nullptr, alpha, run.data(), mu0.data());
+            for (size_t r = 0; !rc && r < at.size(); r++)
+                std::memcpy(rows + at[r] * 2 * N, run.data() + r * 2 * N, 2 * N * sizeof(uint32_t));
+            seeds.clear();
+            mu0.clear();
+            at.clear();
+            return rc;
+        };
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j < t; j++)
+                for (size_t k = 1; k < base; k++) {
+                    const size_t idx = base * t * i + base * j + k;
+                    seeds.push_back(seed0 + idx);
+                    mu0.push_back(((double)k * (double)key_lv0[i]) / (double)(1u << ((j + 1) * basebit)));
+                    at.push_back(idx);
+                    if (seeds.size() == PACK_GEN_ROWS)
+                        if (const int rc = flush()) return rc;
+                }
+        return flush();
     });
 }
 

@@ -180,6 +180,24 @@ hipError_t launch_ksk_to_gemm(const KParams &P, const uint32_t *ksk, uint32_t *k
 hipError_t launch_key_switch(const KParams &P, const uint32_t *lv1, const uint32_t *ksk,
                              uint32_t *out, size_t B, hipStream_t s, const LaunchOpts &O = LaunchOpts(),
                              const char **used = nullptr, const KsGemm *G = nullptr);
+// The packing key switch (TLWELv0 -> a coefficient slot of a TRLWELv1) runs the same GEMM
+// over a key whose n * t * 2^basebit rows are TRLWELv1: 2N output words (64 tiles), n input coefficients.
+// pack_gemm_bytes: the MFMA-layout key; pack_gemm_part_bytes: the K splits' sums for `items` inputs,
+// part[z][item][2N].  launch_pack_gemm takes items <= sized_for inputs with the split count of sized_for (the
+// chunk size G.part holds pack_gemm_part_bytes of: a ragged last chunk on its own would take more splits and more
+// scratch), leaves the sums in G.part and tells the epilogue (launch_pack_rotate_acc,
+// tfhe_kernels_leveled.hip) how many splits there are and the bias every sum carries; `in` as for the
+// re-encryption (rows of n + 1 words, KS_GEMM_INPUT_SLACK readable bytes past the last).
+struct PackSums {
+    int splits = 0;
+    uint32_t bias = 0;  // CB * blocks * t * 128 * 0x01010101, as k_ks_gemm_reduce subtracts
+};
+size_t pack_gemm_bytes(const KParams &P, int t, int basebit);
+size_t pack_gemm_part_bytes(const KParams &P, size_t items, int basebit);
+hipError_t launch_pack_key_to_gemm(const KParams &P, const uint32_t *rows, uint32_t *kg, int t, int basebit,
+                                   hipStream_t s);
+hipError_t launch_pack_gemm(const KParams &P, int t, int basebit, const uint32_t *in, const KsGemm &G, size_t items,
+                            size_t sized_for, hipStream_t s, const char **used, PackSums *sums);
 // zero the k = 0 rows (never read by the reference; the kernels subtract them unconditionally)
 hipError_t launch_ksk_zero_k0(const KParams &P, uint32_t *ksk, hipStream_t s);
 // same for a key-switch-shaped key over n_in input coefficients (proxy re-encryption key)
@@ -246,6 +264,13 @@ hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const Rotat
 // of B TRLWELv1: B * C TLWELv1 of N + 1 words, TRLWE-major
 hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,
                                  hipStream_t s);
+// The packing key switch's epilogue (k_pack_rotate_acc): items item0 .. item0 + M - 1 of a batch of B * C
+// (item b C + c goes to coefficient coef[c] of out[b]; coef on the device, distinct, each < N) from the
+// GEMM's sums of those M items.  The first item of an output TRLWE starts its sum, later ones (a later
+// call's included) add to it, so a batch may go through in chunks of any size, in order.
+hipError_t launch_pack_rotate_acc(const uint32_t *in, int n_in, const uint32_t *part, const PackSums &sums,
+                                  const uint32_t *coef, size_t C, size_t item0, size_t M, uint32_t *out, hipStream_t s,
+                                  const char **used = nullptr);
 
 // ---- launcher (tfhe_kernels_lut.hip); asynchronous on `s` ---------------
 // The linear step of B LUT-circuit nodes: dst[i] = sum_{k in [off[i], off[i+1])} coef[k] * pool[src[k]]

@@ -692,19 +692,23 @@ typedef int kg_v16i __attribute__((ext_vector_type(16)));
 // s < KS = kg_ksteps the MFMA K-steps of one level of one block:
 //   basebit 2: CB = 8, KS = 1, coefficient i = 8ib + 4h + (e >> 2), k = e & 3;
 //   basebit 5: CB = 4, KS = 4, coefficient i = 4ib + s, k = 16h + e;
-// byte b of KSK[i][j][k][w = 32wt + c] − 128 (w > n or i >= n_in: 0 − 128).
+// byte b of KSK[i][j][k][w = 32wt + c] − 128 (w >= out_w or i >= n_in: 0 − 128).
+// out_w is the key's row width in words and rs its source row stride: n + 1 and
+// ks_stride for the key switch and the re-encryption, 2N and 2N (64 tiles, no
+// padding column) for the packing key, whose rows are TRLWELv1.
 __host__ __device__ __forceinline__ int kg_cb(int basebit) { return basebit == 2 ? 8 : 4; }
 __host__ __device__ __forceinline__ int kg_ksteps(int basebit) { return basebit == 2 ? 1 : 4; }
 __host__ __device__ __forceinline__ int kg_blocks(int n_in, int basebit) { return (n_in + kg_cb(basebit) - 1) / kg_cb(basebit); }
-size_t ks_gemm_bytes(const KParams &P, int n_in, int t, int basebit) {
-    const size_t w32 = (size_t)(P.n + 1 + 31) / 32;
+static size_t ks_gemm_bytes_w(int out_w, int n_in, int t, int basebit) {
+    const size_t w32 = (size_t)(out_w + 31) / 32;
     return (size_t)t * kg_blocks(n_in, basebit) * w32 * kg_ksteps(basebit) * 4 * 1024;
 }
+size_t ks_gemm_bytes(const KParams &P, int n_in, int t, int basebit) { return ks_gemm_bytes_w(P.n + 1, n_in, t, basebit); }
 __global__ void k_ksk_to_gemm(KParams P, const uint32_t *__restrict__ ksk, uint32_t *__restrict__ kg, size_t words,
-                              int n_in, int t, int basebit) {
+                              int n_in, int t, int basebit, int out_w, int row_stride) {
     const size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // one u32 = bytes e = 4q .. 4q+3
     if (x >= words) return;
-    const int w32 = (P.n + 1 + 31) / 32, nib = kg_blocks(n_in, basebit), ks = kg_ksteps(basebit);
+    const int w32 = (out_w + 31) / 32, nib = kg_blocks(n_in, basebit), ks = kg_ksteps(basebit);
     const int base = 1 << basebit;
     const int q = (int)(x & 3), lane = (int)((x >> 2) & 63), b = (int)((x >> 8) & 3);
     size_t r = x >> 10;
@@ -714,7 +718,7 @@ __global__ void k_ksk_to_gemm(KParams P, const uint32_t *__restrict__ ksk, uint3
     r /= w32;
     const int ib = (int)(r % nib), j = (int)(r / nib);
     const int h = lane >> 5, c = lane & 31, w = 32 * wt + c;
-    const size_t rs = (size_t)P.ks_stride;
+    const size_t rs = (size_t)row_stride;
     uint32_t v = 0;
 #pragma unroll
     for (int e4 = 0; e4 < 4; e4++) {
@@ -722,7 +726,7 @@ __global__ void k_ksk_to_gemm(KParams P, const uint32_t *__restrict__ ksk, uint3
         const int i = basebit == 2 ? 8 * ib + 4 * h + (e >> 2) : 4 * ib + st;
         const int k = basebit == 2 ? (e & 3) : 16 * h + e;
         const uint32_t word =
-            (w <= P.n && i < n_in) ? ksk[((size_t)(base * t) * i + (size_t)base * j + k) * rs + w] : 0u;
+            (w < out_w && i < n_in) ? ksk[((size_t)(base * t) * i + (size_t)base * j + k) * rs + w] : 0u;
         v |= (((word >> (8 * b)) & 255u) ^ 128u) << (8 * e4);  // byte − 128 as int8
     }
     kg[x] = v;
@@ -742,7 +746,8 @@ template <int T, int BASEBIT>
 __global__ __launch_bounds__(64 * KG_WAVES, 1) void k_key_switch_gemm(KParams P, const uint32_t *__restrict__ lv1,
                                                                    const uint32_t *__restrict__ kg,
                                                                    uint32_t *__restrict__ part, size_t B,
-                                                                   int ib_per_split, int n_in, int in_stride) {
+                                                                   int ib_per_split, int n_in, int in_stride,
+                                                                   int out_w) {
     constexpr int CB = BASEBIT == 2 ? 8 : 4;             // coefficients per block
     constexpr int KS = BASEBIT == 2 ? 1 : 4;             // MFMA K-steps per level per block
     constexpr int STEP_BYTES = KS * 4 * 1024;            // one level's K-steps x 4 planes of one 32-word tile
@@ -757,7 +762,7 @@ __global__ __launch_bounds__(64 * KG_WAVES, 1) void k_key_switch_gemm(KParams P,
     const int tid = threadIdx.x, lane = tid & 63;
     const int v = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = v < 4;  // waves 0-3 also issue the KSK pieces: 4 KB per instruction, 256 threads x 16 B
-    const int w32 = (P.n + 1 + 31) / 32;
+    const int w32 = (out_w + 31) / 32;  // output tiles: 22 for n + 1 = 701 words, 64 for a packing key's 2N
     const int wt = blockIdx.x;
     const int nib = kg_blocks(n_in, BASEBIT);
     const int ib_lo = blockIdx.z * ib_per_split, ib_hi = min(nib, ib_lo + ib_per_split);
@@ -887,8 +892,8 @@ __global__ __launch_bounds__(64 * KG_WAVES, 1) void k_key_switch_gemm(KParams P,
                 }
         }
     }
-    // partial sums of this K split: part[z][m][w], w < n + 1
-    const int n1 = P.n + 1;
+    // partial sums of this K split: part[z][m][w], w < out_w
+    const int n1 = out_w;
     uint32_t *pz = part + (size_t)blockIdx.z * B * n1;
     const int w = 32 * wt + c;
     const size_t m_base = m_wg + 64 * v;
@@ -1642,14 +1647,16 @@ bool ks_use_gemm(const LaunchOpts &O, int t, int basebit, size_t B, const KsGemm
 
 // The name last_kernels() reports for a key-switch instantiation, from its own
 // template arguments.
-enum KsKernel { KK_LANES, KK_RING, KK_GEMM };
+enum KsKernel { KK_LANES, KK_RING, KK_GEMM, KK_GEMM_PACK };
 template <KsKernel K, int... V>
 static const char *ks_name() {
     static const std::string name = [] {
-        std::string r = K == KK_RING ? "k_key_switch_ring<" : K == KK_GEMM ? "k_key_switch_gemm<" : "k_key_switch_lanes<";
+        std::string r = K == KK_RING ? "k_key_switch_ring<"
+                        : K == KK_GEMM || K == KK_GEMM_PACK ? "k_key_switch_gemm<"
+                                                            : "k_key_switch_lanes<";
         ((r += std::to_string(V) + ','), ...);
         r.back() = '>';
-        return K == KK_GEMM ? r + " + k_ks_gemm_reduce" : r;
+        return K == KK_GEMM ? r + " + k_ks_gemm_reduce" : r;  // the packing path's epilogue names itself
     }();
     return name.c_str();
 }
@@ -1713,13 +1720,35 @@ static bool launch_ks_lanes(const KParams &P, int t_, int basebit, const uint32_
 }
 
 // K splits of the gemm form: enough workgroups for one per CU.
-static int ks_gemm_splits(const KParams &P, size_t B, int n_in, int basebit) {
-    const size_t tiles = (size_t)(P.n + 1 + 31) / 32 * ((B + KG_ITEMS - 1) / KG_ITEMS);
+static int ks_gemm_splits(int out_w, size_t B, int n_in, int basebit) {
+    const size_t tiles = (size_t)(out_w + 31) / 32 * ((B + KG_ITEMS - 1) / KG_ITEMS);
     const size_t z = std::max<size_t>(1, device_cus() / tiles);
     return (int)std::min<size_t>(z, (size_t)kg_blocks(n_in, basebit));
 }
 size_t ks_gemm_part_bytes(const KParams &P, size_t B, int n_in, int basebit) {
-    return (size_t)ks_gemm_splits(P, B, n_in, basebit) * B * (P.n + 1) * 4;
+    return (size_t)ks_gemm_splits(P.n + 1, B, n_in, basebit) * B * (P.n + 1) * 4;
+}
+
+// The GEMM alone, over a key of out_w words per row: it leaves part[z][m][w], w < out_w, for the
+// *splits_out <= z K splits (z: the caller's ks_gemm_splits, what G.part was sized for).  PACK: the
+// packing key switch's launch, whose epilogue names itself (ks_name).
+template <bool PACK>
+static hipError_t launch_ks_gemm_part(const KParams &P, int t, int basebit, int n_in, int in_stride, int out_w, int z,
+                                      const uint32_t *in, const KsGemm &G, size_t B, hipStream_t s, const char **used,
+                                      int *splits_out) {
+    const int nib = kg_blocks(n_in, basebit);
+    const int per = (nib + z - 1) / z;
+    const int splits = (nib + per - 1) / per;
+    dim3 grid((unsigned)((out_w + 31) / 32), (unsigned)((B + KG_ITEMS - 1) / KG_ITEMS), (unsigned)splits),
+        block(64 * KG_WAVES);
+    if (!ks_with_shape<KS_GEMM>(t, basebit, [&](auto T, auto BB) {
+            hipLaunchKernelGGL((k_key_switch_gemm<T(), BB()>), grid, block, 0, s, P, in, G.kg, G.part, B, per, n_in,
+                               in_stride, out_w);
+            if (used) *used = ks_name<PACK ? KK_GEMM_PACK : KK_GEMM, T(), BB()>();
+        }))
+        return hipErrorInvalidValue;
+    *splits_out = splits;
+    return hipGetLastError();
 }
 
 // One-hot GEMM key switch of B inputs of in_stride words (n_in coefficients, then b)
@@ -1728,18 +1757,10 @@ size_t ks_gemm_part_bytes(const KParams &P, size_t B, int n_in, int basebit) {
 // input buffer needs KS_GEMM_INPUT_SLACK readable bytes past its last row.
 static hipError_t launch_ks_gemm(const KParams &P, int t, int basebit, int n_in, int in_stride, const uint32_t *in,
                                  const KsGemm &G, uint32_t *out, size_t B, hipStream_t s, const char **used) {
-    const int nib = kg_blocks(n_in, basebit);
-    const int z = ks_gemm_splits(P, B, n_in, basebit);
-    const int per = (nib + z - 1) / z;
-    const int splits = (nib + per - 1) / per;
-    dim3 grid((unsigned)((P.n + 1 + 31) / 32), (unsigned)((B + KG_ITEMS - 1) / KG_ITEMS), (unsigned)splits),
-        block(64 * KG_WAVES);
-    if (!ks_with_shape<KS_GEMM>(t, basebit, [&](auto T, auto BB) {
-            hipLaunchKernelGGL((k_key_switch_gemm<T(), BB()>), grid, block, 0, s, P, in, G.kg, G.part, B, per, n_in,
-                               in_stride);
-            if (used) *used = ks_name<KK_GEMM, T(), BB()>();
-        }))
-        return hipErrorInvalidValue;
+    int splits = 0;
+    const hipError_t e = launch_ks_gemm_part<false>(P, t, basebit, n_in, in_stride, P.n + 1,
+                                                    ks_gemm_splits(P.n + 1, B, n_in, basebit), in, G, B, s, used, &splits);
+    if (e != hipSuccess) return e;
     const size_t total = B * (size_t)(P.n + 1);
     hipLaunchKernelGGL(k_ks_gemm_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P, in, G.part, out, B,
                        splits, n_in, in_stride, t, basebit);
@@ -1760,8 +1781,30 @@ hipError_t launch_ksk_to_gemm(const KParams &P, const uint32_t *ksk, uint32_t *k
                               hipStream_t s) {
     const size_t words = ks_gemm_bytes(P, n_in, t, basebit) / 4;
     hipLaunchKernelGGL(k_ksk_to_gemm, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, P, ksk, kg, words, n_in,
-                       t, basebit);
+                       t, basebit, P.n + 1, P.ks_stride);
     return hipGetLastError();
+}
+
+// ---- The packing key switch's use of the GEMM: rows of 2N words --------------
+size_t pack_gemm_bytes(const KParams &P, int t, int basebit) { return ks_gemm_bytes_w(2 * P.N, P.n, t, basebit); }
+size_t pack_gemm_part_bytes(const KParams &P, size_t items, int basebit) {
+    return (size_t)ks_gemm_splits(2 * P.N, items, P.n, basebit) * items * 2 * P.N * 4;
+}
+hipError_t launch_pack_key_to_gemm(const KParams &P, const uint32_t *rows, uint32_t *kg, int t, int basebit,
+                                   hipStream_t s) {
+    const size_t words = pack_gemm_bytes(P, t, basebit) / 4;
+    hipLaunchKernelGGL(k_ksk_to_gemm, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, P, rows, kg, words, P.n,
+                       t, basebit, 2 * P.N, 2 * P.N);
+    return hipGetLastError();
+}
+hipError_t launch_pack_gemm(const KParams &P, int t, int basebit, const uint32_t *in, const KsGemm &G, size_t items,
+                            size_t sized_for, hipStream_t s, const char **used, PackSums *sums) {
+    if (items > sized_for) return hipErrorInvalidValue;
+    sums->bias = (uint32_t)(kg_cb(basebit) * kg_blocks(P.n, basebit) * t) * 128u * 0x01010101u;
+    // the splits of `sized_for` items, not of this launch's: fewer items would take more splits, and more
+    // scratch than pack_gemm_part_bytes(sized_for)
+    return launch_ks_gemm_part<true>(P, t, basebit, P.n, P.n + 1, 2 * P.N, ks_gemm_splits(2 * P.N, sized_for, P.n, basebit),
+                                     in, G, items, s, used, &sums->splits);
 }
 
 hipError_t launch_key_switch(const KParams &P, const uint32_t *lv1, const uint32_t *ksk, uint32_t *out,

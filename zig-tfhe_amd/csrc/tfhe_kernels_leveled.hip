@@ -292,6 +292,57 @@ __global__ __launch_bounds__(256) void k_sample_extract(const uint32_t *__restri
     if (threadIdx.x == 0) o[1024] = x[1024 + k];
 }
 
+// The packing key switch's epilogue, one pass over the GEMM's sums.  Item g = b C + c of
+// the batch has R_g = (0, (in_g.b, 0, ..., 0)) - sum_z part[z][g - item0][.] - bias in all 2N words (the
+// bias of k_ks_gemm_reduce) and goes into out[b] as X^coef[c] R_g (polyMulWithXK, trgsw.zig:442-466, on
+// each half): word p of a half takes R[p - k] for p >= k and -R[p - k + N] below.  Block = 64 consecutive
+// words of one output TRLWE; its lane-0-wave thread owns the word: it alone reads (when the TRLWE's first
+// items went through in an earlier chunk) and writes it, so there are no atomics.  The 16 waves walk the
+// TRLWE's items of this chunk c = wave, wave + 16, ... and add up through LDS (wrapping sums commute): one
+// TRLWE of 1,024 items is 32 blocks only, so the walk is what bounds it (4 waves: 0.34 ms per pack of
+// 1,024 against 0.10 ms for the key switch, profiles/pack_bench_epilogue_4waves.json).
+constexpr int PACK_ACC_WAVES = 16;
+__global__ __launch_bounds__(64 * PACK_ACC_WAVES) void k_pack_rotate_acc(
+    const uint32_t *__restrict__ in, int in_stride, int n_in, const uint32_t *__restrict__ part, int splits,
+    uint32_t bias, const uint32_t *__restrict__ coef, size_t C, size_t item0, size_t M, uint32_t *__restrict__ out) {
+    __shared__ uint32_t red[PACK_ACC_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t b = item0 / C + blockIdx.x / 32;
+    const uint32_t x = (blockIdx.x % 32) * 64 + lane;  // word of the TRLWE: half x >> 10, coefficient p
+    const uint32_t half = x >> 10, p = x & 1023u;
+    const size_t first = b * C, lo = first > item0 ? first : item0;
+    const size_t hi = first + C < item0 + M ? first + C : item0 + M;
+    uint32_t acc = 0;
+#pragma unroll 4
+    for (size_t g = lo + wave; g < hi; g += PACK_ACC_WAVES) {
+        const uint32_t k = coef[g - first];
+        const size_t m = g - item0;
+        const uint32_t q = (p - k) & 1023u;
+        uint32_t r = bias;
+        for (int z = 0; z < splits; z++) r += part[((size_t)z * M + m) * 2048 + half * 1024 + q];
+        const uint32_t v = (half && q == 0 ? in[m * (size_t)in_stride + n_in] : 0u) - r;
+        acc += p < k ? 0u - v : v;
+    }
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave) return;
+#pragma unroll
+    for (int w = 1; w < PACK_ACC_WAVES; w++) acc += red[w][lane];
+    uint32_t *o = out + b * 2048 + x;
+    *o = (lo == first ? 0u : *o) + acc;
+}
+
+hipError_t launch_pack_rotate_acc(const uint32_t *in, int n_in, const uint32_t *part, const PackSums &sums,
+                                  const uint32_t *coef, size_t C, size_t item0, size_t M, uint32_t *out, hipStream_t s,
+                                  const char **used) {
+    if (M == 0 || C == 0) return hipSuccess;
+    const size_t trlwes = (item0 + M - 1) / C - item0 / C + 1;  // output TRLWEs this chunk's items go to
+    hipLaunchKernelGGL(k_pack_rotate_acc, dim3((unsigned)(trlwes * 32)), dim3(64 * PACK_ACC_WAVES), 0, s, in, n_in + 1,
+                       n_in, part, sums.splits, sums.bias, coef, C, item0, M, out);
+    if (used) *used = "k_pack_rotate_acc";
+    return hipGetLastError();
+}
+
 template <int L>
 static const char *cmux_launch(bool shared, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
                                const CmuxBatch &b) {

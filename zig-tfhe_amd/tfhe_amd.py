@@ -24,11 +24,12 @@ LIB_PATH = os.environ.get("TFHE_GPU_LIB") or os.path.join(HERE, "lib", "libtfhe_
 # tfhe_gpu_set_option keys / values (include/tfhe_gpu.h TFHE_OPT_*, TFHE_TWIDDLES_*)
 OPTIONS = {"br_form": 1, "br_loader": 2, "ks_form": 3, "ks_narrow": 4, "ks_item_groups": 5, "ks_sel_items": 6,
            "circuit_pack": 7, "twiddles": 8, "arith": 9, "br_sync": 10, "br_spin_cap": 11, "host_pipeline": 12,
-           "circuit_split": 13, "host_staging": 17, "cmux_form": 18}
+           "circuit_split": 13, "host_staging": 17, "cmux_form": 18, "pack_scratch_mb": 19}
 READONLY_OPTIONS = {"fused_admitted": 14, "level_issue_us": 15, "key_row_rms_ppm": 16}  # tfhe_gpu_get_option only
 OPTION_DEFAULTS = {"br_form": 0, "br_loader": 1, "ks_form": 3, "ks_narrow": 0, "ks_item_groups": 0,
                    "ks_sel_items": 8, "circuit_pack": 1, "twiddles": 0, "arith": 0, "br_sync": 1, "br_spin_cap": 0,
-                   "host_pipeline": 0, "circuit_split": 0, "host_staging": 0, "cmux_form": 0}
+                   "host_pipeline": 0, "circuit_split": 0, "host_staging": 0, "cmux_form": 0,
+                   "pack_scratch_mb": 256}
 # status codes (include/tfhe_gpu.h TFHE_ERR_*)
 ERR_INVALID, ERR_HIP, ERR_NO_KEY, ERR_OOM, ERR_IO, ERR_DEVICE = -1, -2, -3, -4, -5, -6
 # 2 split, 4 pair: removed (round 4); 6 duo, 7 wide2: A/B libraries only (tools/ab/, round 5); 5 octo: L = 1
@@ -207,6 +208,13 @@ _SIGS = {
                                                u32p]),
     "tfhe_gpu_packed_lookup_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t]),
     "tfhe_gpu_packed_lookup_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
+    "tfhe_gpu_packing_key_gen": (C.c_int, [vp, u32p, u32p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, u32p]),
+    "tfhe_gpu_packing_key_load": (C.c_int, [vp, u32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "tfhe_gpu_packing_key_destroy": (None, [vp]),
+    "tfhe_gpu_pack_tlwe_batch": (C.c_int, [vp, vp, u32p, u32p, C.c_size_t, u32p, C.c_size_t]),
+    "tfhe_gpu_pack_tlwe_dev": (C.c_int, [vp, vp, vp, u32p, C.c_size_t, vp, C.c_size_t]),
+    "tfhe_pack_tlwe": (C.c_int, [C.POINTER(TfheParams), u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t, u32p,
+                                 C.c_size_t]),
     "tfhe_gpu_lut_set_load": (C.c_int, [vp, u32p, C.c_size_t, C.POINTER(vp)]),
     "tfhe_gpu_lut_set_destroy": (None, [vp]),
     "tfhe_gpu_lut_apply_batch": (C.c_int, [vp, vp, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, C.c_size_t]),
@@ -722,6 +730,34 @@ class Context:
         self.check(self.lib.tfhe_gpu_packed_lookup_dev(self.h, selectors.h, ap, addr.shape[1], width, vp(table_ptr),
                                                        vp(out_ptr), addr.shape[0]), "packed_lookup_dev")
 
+    # ---- packing key switch: TLWELv0 -> coefficient slots of TRLWELv1 ----
+    def pack_tlwe(self, key: "PackingKey", cts, coef):
+        """tfhe_gpu_pack_tlwe_batch: cts (B, C, n+1) TLWELv0 (or (C, n+1): B = 1), coef (C,) distinct coefficients
+        < N.  -> (B, 2N) TRLWELv1 whose coefficient coef[c] of row b carries the phase of cts[b, c]."""
+        coef, cp = _u32(np.atleast_1d(coef))
+        x, xp = _u32(np.asarray(cts, np.uint32).reshape(-1, max(coef.size, 1), self.n1))
+        out = np.zeros((x.shape[0], 2 * self.params.N), np.uint32)
+        self.check(self.lib.tfhe_gpu_pack_tlwe_batch(self.h, key.h, xp, cp, coef.size, out.ctypes.data_as(u32p),
+                                                     x.shape[0]), "pack_tlwe")
+        return out
+
+    def pack_tlwe_dev(self, key: "PackingKey", in_ptr, B, coef, out_ptr):
+        """tfhe_gpu_pack_tlwe_dev: the B * C TLWELv0 and the B TRLWELv1 in HBM (coef stays a host array), async."""
+        coef, cp = _u32(np.atleast_1d(coef))
+        self.check(self.lib.tfhe_gpu_pack_tlwe_dev(self.h, key.h, vp(in_ptr), cp, coef.size, vp(out_ptr), B),
+                   "pack_tlwe_dev")
+
+    def pack_table(self, key: "PackingKey", cts, k: int, width: int):
+        """The packed table of packed_lookup from 2^k * width TLWELv0 computed on the server (entry-major, then
+        bit): one pack call with B = plan.trlwes and coef[s * width + c] = s * stride + c.  -> (trlwes, 2N)."""
+        plan = packed_lookup_plan(self.params, k, width)
+        slots = 1 << plan.h
+        x = np.asarray(cts, np.uint32).reshape(-1, self.n1)
+        if x.shape[0] != (width << k):
+            raise ValueError(f"pack_table: k = {k}, width = {width} need {width << k} ciphertexts, got {x.shape[0]}")
+        coef = (np.arange(slots, dtype=np.uint32)[:, None] * plan.stride + np.arange(width, dtype=np.uint32)).reshape(-1)
+        return self.pack_tlwe(key, x.reshape(plan.trlwes, slots * width, self.n1), coef)
+
     # ---- LUT circuits: linear combination, then bootstrap with the node's own table ----
     def lut_apply(self, lut_set: "LutSet", pool, nodes):
         """tfhe_gpu_lut_apply_batch: node i = (lut, terms[, const]) computes x = sum coef * pool[src] over its
@@ -944,6 +980,65 @@ class TrgswSet:
             self.close()
         except Exception:
             pass
+
+
+class PackingKey:
+    """The packing key of Context.pack_tlwe / pack_table resident in HBM (tfhe_gpu_packing_key): rows
+    (n * t * 2^basebit, 2N) uint32, row base*t*i + base*j + k a TRLWELv1 encryption of k * key_lv0[i] /
+    2^((j+1)*basebit) at coefficient 0 (k = 0 rows zero).  Only the matrix-core layout stays on the device."""
+
+    def __init__(self, ctx: Context, rows, basebit: int, t: int):
+        self.ctx, self.h, self.basebit, self.t = ctx, vp(), basebit, t
+        r, rp = _u32(rows)
+        ctx.check(ctx.lib.tfhe_gpu_packing_key_load(ctx.h, rp, r.size, basebit, t, C.byref(self.h)), "packing_key_load")
+
+    @staticmethod
+    def default_shape(params: TfheParams):
+        """The set's own (basebit, iks_t) where the one-hot GEMM has that shape, else (2, 8)."""
+        b, t = params.basebit, params.iks_t
+        return (b, t) if (b == 2 and 7 <= t <= 9) or (b == 5 and 2 <= t <= 3) else (2, 8)
+
+    @staticmethod
+    def generate_rows(ctx: Context, sk: "SecretKey", seed0: int, alpha=None, basebit=None, t=None):
+        """tfhe_gpu_packing_key_gen: -> (rows (n * t * 2^basebit, 2N) uint32, basebit, t); row idx uses
+        DefaultPrng(seed0 + idx).  Defaults: default_shape and alpha_lv1."""
+        p = ctx.params
+        db, dt = PackingKey.default_shape(p)
+        basebit, t = db if basebit is None else basebit, dt if t is None else t
+        alpha = p.alpha_lv1 if alpha is None else alpha
+        rows = np.zeros((p.n * t << basebit, 2 * p.N), np.uint32)
+        ctx.check(ctx.lib.tfhe_gpu_packing_key_gen(ctx.h, _u32(sk.key_lv0)[1], _u32(sk.key_lv1)[1], alpha, basebit, t,
+                                                   seed0, rows.ctypes.data_as(u32p)), "packing_key_gen")
+        return rows, basebit, t
+
+    @classmethod
+    def generate(cls, ctx: Context, sk: "SecretKey", seed0: int, alpha=None, basebit=None, t=None):
+        rows, basebit, t = cls.generate_rows(ctx, sk, seed0, alpha, basebit, t)
+        return cls(ctx, rows, basebit, t)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.tfhe_gpu_packing_key_destroy(self.h)
+            self.h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_tlwe_host(params: TfheParams, rows, basebit: int, t: int, cts, coef) -> np.ndarray:
+    """tfhe_pack_tlwe (host only): the definition Context.pack_tlwe computes on the device, word for word."""
+    coef, cp = _u32(np.atleast_1d(coef))
+    x, xp = _u32(np.asarray(cts, np.uint32).reshape(-1, max(coef.size, 1), params.n + 1))
+    r, rp = _u32(rows)
+    out = np.zeros((x.shape[0], 2 * params.N), np.uint32)
+    rc = load_library().tfhe_pack_tlwe(C.byref(params), rp, basebit, t, xp, cp, coef.size, out.ctypes.data_as(u32p),
+                                       x.shape[0])
+    if rc:
+        raise TfheError(f"pack_tlwe_host: {rc}", rc)
+    return out
 
 
 class LutSet:
