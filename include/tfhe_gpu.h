@@ -37,7 +37,9 @@ extern "C" {
                                    tfhe_lut_circuit_schedule) and the packed lookup (tfhe_gpu_rotate_by_bits_*,
                                    tfhe_gpu_packed_lookup_*, tfhe_packed_lookup_plan, tfhe_lookup_table_pack_slots)
                                    and the packing key switch (tfhe_gpu_packing_key_*, tfhe_gpu_pack_tlwe_*,
-                                   tfhe_pack_tlwe, TFHE_OPT_PACK_SCRATCH_MB);
+                                   tfhe_pack_tlwe, TFHE_OPT_PACK_SCRATCH_MB) and the multi-output LUT bootstrap
+                                   (tfhe_lut_round_tlwe, tfhe_lut_interleave, tfhe_gpu_lut_apply_multi_*,
+                                   tfhe_gpu_lut_circuit_eval_multi*, tfhe_lut_circuit_schedule_multi);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -573,6 +575,63 @@ int tfhe_gpu_lut_circuit_eval_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set
  * (inputs are level 0; a node without terms is level 1), *depth (may be NULL) the largest. */
 int tfhe_lut_circuit_schedule(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                               uint32_t *levels, uint32_t *depth);
+
+/* ---- Multi-output LUT bootstrap: 2^theta tables from one blind rotation ----
+ * Several functions of one combined input (message and carry of a radix digit, < and ==, quotient and remainder) for
+ * the price of one blind rotation and theta bits of message room.  Integer-exact; with nbit = log2 N,
+ * s = 32 - (nbit + 1) + theta and 0 <= theta <= TFHE_LUT_MULTI_MAX_LOG:
+ *   round_theta(w) = (w + (1 << (s-1))) & ~((1 << s) - 1) in wrapping u32 on all n+1 words of a TLWELv0 for
+ *     theta >= 1, and the identity for theta = 0.  A rounded word is a multiple of 2^(21+theta) (N = 1024), so the
+ *     blind rotation's own mod switch (w + 2^20) >> 21 (trgsw.zig:290-333) returns exactly w >> 21, a multiple of
+ *     2^theta: the accumulator is rotated by a multiple of nu = 2^theta.
+ *   interleave: from nu test vectors tv_0 .. tv_{nu-1} (TRLWELv1, any a), on both halves h,
+ *     TV[h][q] = tv_{q mod nu}[h][q - (q mod nu)]; after a rotation by a multiple of nu, coefficient j of the
+ *     accumulator holds what tv_j holds at the rounded phase.
+ *   node: with x the node's combination exactly as tfhe_gpu_lut_apply_* defines it, output j < 2^theta is, word for
+ *     word, identityKeySwitching(sampleExtractIndex(blindRotateWithTestvec(round_theta(x), set[lut]), j)): what
+ *     tfhe_gpu_blind_rotate_batch, then tfhe_gpu_sample_extract_* with coef = 0 .. nu-1 and key_switch = 1 give.
+ *     A theta = 0 node gives exactly the words of tfhe_gpu_lut_apply_batch.
+ * Noise rule: the rounding's phase error, in positions of 2N, has sigma ~ 2^theta * sqrt((n/2 + 1) / 12) for a
+ * binary key.  A message block of Encoder.new(m) is N/m positions wide and read at its centre (generator.zig:94-112):
+ * the margin is N/(2m) positions, so each theta costs exactly one bit of m at equal margin.  UINT4 (n = 820):
+ * m = 16, theta = 0: 32 / 5.86 = 5.5 sigma (today's); m = 8, theta = 1: 64 / 11.7 = 5.5 sigma; m = 4, theta = 2 the
+ * same; m = 16, theta = 1: 2.7 sigma, wrong about once in 150 -- do not use it.  The library never sees m and does
+ * not police it. */
+#define TFHE_LUT_MULTI_MAX_LOG 3
+/* host only, no device: round_theta over B TLWELv0 (in == out is allowed); TFHE_ERR_INVALID for theta > 3 */
+int tfhe_lut_round_tlwe(const tfhe_params *params, uint32_t theta, const uint32_t *in, uint32_t *out, size_t B);
+int tfhe_lut_interleave(const tfhe_params *params, const uint32_t *testvecs /*2^theta*2N*/, uint32_t theta,
+                        uint32_t *out /*2N*/);
+/* tfhe_gpu_lut_apply_* with theta[i] per node (HOST array of B; NULL = all 0, the existing entry): out holds
+ * sum_i 2^theta[i] ciphertexts of n+1 words, node-major, node i's outputs consecutive.  A call whose thetas are all 0
+ * runs exactly what tfhe_gpu_lut_apply_* runs.  Checked before any launch: a theta > TFHE_LUT_MULTI_MAX_LOG and
+ * everything tfhe_gpu_lut_apply_* checks (TFHE_ERR_INVALID). */
+int tfhe_gpu_lut_apply_multi_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
+                                   const uint32_t *term_off /*B+1*/, const uint32_t *term_src, const int32_t *term_coef,
+                                   const uint32_t *konst /*B*/, const uint32_t *lut /*B*/, const uint32_t *theta /*B*/,
+                                   uint32_t *out, size_t B);
+int tfhe_gpu_lut_apply_multi_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const uint32_t *pool_dev, size_t P,
+                                 const uint32_t *term_off /*B+1*/, const uint32_t *term_src, const int32_t *term_coef,
+                                 const uint32_t *konst /*B*/, const uint32_t *lut /*B*/, const uint32_t *theta /*B*/,
+                                 uint32_t *out_dev, size_t B);
+/* tfhe_gpu_lut_circuit_eval* with theta[g] per node (NULL = the existing entries): node g drives the 2^theta[g] wires
+ * n_inputs + o_g + j, o_g = sum_{g' < g} 2^theta[g'], and every term wire of node g is < n_inputs + o_g.  A level
+ * with a theta > 0 runs combine-and-round, one blind rotation per node, the fan-out extraction and one key switch
+ * over the level's outputs; a level whose thetas are all 0 runs what tfhe_gpu_lut_circuit_eval runs. */
+int tfhe_gpu_lut_circuit_eval_multi(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                    const uint32_t *inputs, size_t n_nodes, const uint32_t *term_off,
+                                    const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                    const uint32_t *lut, const uint32_t *theta /*n_nodes*/, size_t n_outputs,
+                                    const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels);
+int tfhe_gpu_lut_circuit_eval_multi_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                        const uint32_t *inputs_dev, size_t n_nodes, const uint32_t *term_off,
+                                        const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                        const uint32_t *lut, const uint32_t *theta /*n_nodes*/, size_t n_outputs,
+                                        const uint32_t *out_wires, uint32_t *outputs_dev, uint32_t *levels);
+/* host only: tfhe_lut_circuit_schedule for the multi-output wire numbering (levels has n_nodes entries) */
+int tfhe_lut_circuit_schedule_multi(size_t n_inputs, size_t n_nodes, const uint32_t *term_off,
+                                    const uint32_t *term_wire, const uint32_t *theta /*n_nodes*/, uint32_t *levels,
+                                    uint32_t *depth);
 
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
 /* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,

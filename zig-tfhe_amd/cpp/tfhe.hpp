@@ -683,6 +683,25 @@ inline std::vector<Torus> lutGenerate(const tfhe_params &p, const std::vector<ui
     return tv;
 }
 
+// tfhe_lut_interleave: 1, 2, 4 or 8 test vectors -> the one a multi-output node reads (coefficient j = table j).
+inline std::vector<Torus> lutInterleave(const tfhe_params &p, const std::vector<std::vector<Torus>> &tables) {
+    uint32_t theta = 0;
+    while (((size_t)1 << theta) < tables.size()) theta++;
+    std::vector<Torus> all, tv(2 * (size_t)p.N);
+    for (const std::vector<Torus> &t : tables) all.insert(all.end(), t.begin(), t.end());
+    if (((size_t)1 << theta) != tables.size() || all.size() != tables.size() * tv.size())
+        throw Error(TFHE_ERR_INVALID, "lutInterleave: 1, 2, 4 or 8 test vectors of 2N words");
+    check(tfhe_lut_interleave(&p, all.data(), theta, tv.data()), "lutInterleave");
+    return tv;
+}
+
+// tfhe_lut_round_tlwe: round_theta of the multi-output bootstrap on every word of a TLWELv0.
+inline TLWELv0 lutRoundTlwe(const tfhe_params &p, uint32_t theta, const TLWELv0 &in) {
+    TLWELv0 out(p.n);
+    check(tfhe_lut_round_tlwe(&p, theta, in.p.data(), out.p.data(), 1), "lutRoundTlwe");
+    return out;
+}
+
 // Test vectors resident in HBM (tfhe_gpu_lut_set): T TRLWELv1 of 2N words each, the tables of a LutCircuit.
 class LutSet {
   public:
@@ -713,10 +732,14 @@ class LutCircuit {
     using Term = std::pair<Wire, int32_t>;  // (wire, coefficient)
     Wire input() {
         if (!lut_.empty()) throw Error(TFHE_ERR_INVALID, "LutCircuit: declare inputs before nodes");
+        n_wires_++;
         return n_inputs_++;
     }
-    Wire node(uint32_t lut, const std::vector<Term> &terms, Torus konst = 0) {
-        const Wire w = (Wire)(n_inputs_ + lut_.size());
+    // theta > 0: a multi-output node (lut names a lutInterleave table); it drives the 2^theta wires from the
+    // returned one on, one per interleaved table.
+    Wire node(uint32_t lut, const std::vector<Term> &terms, Torus konst = 0, uint32_t theta = 0) {
+        if (theta > TFHE_LUT_MULTI_MAX_LOG) throw Error(TFHE_ERR_INVALID, "LutCircuit: a node has 1, 2, 4 or 8 outputs");
+        const Wire w = n_wires_;
         for (const Term &t : terms) {
             if (t.first >= w) throw Error(TFHE_ERR_INVALID, "LutCircuit: node terms must read existing wires");
             wire_.push_back(t.first);
@@ -725,6 +748,9 @@ class LutCircuit {
         off_.push_back((uint32_t)wire_.size());
         konst_.push_back(konst);
         lut_.push_back(lut);
+        theta_.push_back(theta);
+        multi_ = multi_ || theta != 0;
+        n_wires_ += 1u << theta;
         return w;
     }
     void output(Wire w) { outs_.push_back(w); }
@@ -745,10 +771,27 @@ class LutCircuit {
         if (have_carry) out.push_back(carry);
         return out;
     }
-    // tfhe_lut_circuit_schedule: the level of every node; *depth (may be NULL) the largest
+    // radixAdd with one two-output node per digit: lut is lutInterleave of the (message, carry) tables, at half
+    // the message modulus radixAdd's tables may use.
+    std::vector<Wire> radixAddFused(const std::vector<Wire> &a, const std::vector<Wire> &b, uint32_t lut) {
+        std::vector<Wire> out;
+        bool have_carry = false;
+        Wire carry = 0;
+        for (size_t i = 0; i < a.size() && i < b.size(); i++) {
+            std::vector<Term> terms{{a[i], 1}, {b[i], 1}};
+            if (have_carry) terms.push_back({carry, 1});
+            const Wire msg = node(lut, terms, 0, 1);
+            out.push_back(msg);
+            carry = msg + 1;
+            have_carry = true;
+        }
+        if (have_carry) out.push_back(carry);
+        return out;
+    }
+    // tfhe_lut_circuit_schedule(_multi): the level of every node; *depth (may be NULL) the largest
     std::vector<uint32_t> schedule(uint32_t *depth = nullptr) const {
         std::vector<uint32_t> levels(lut_.size());
-        check(tfhe_lut_circuit_schedule(n_inputs_, lut_.size(), off_.data(), wire_.data(), levels.data(), depth),
+        check(tfhe_lut_circuit_schedule_multi(n_inputs_, lut_.size(), off_.data(), wire_.data(), theta(), levels.data(), depth),
               "LutCircuit.schedule");
         return levels;
     }
@@ -758,9 +801,9 @@ class LutCircuit {
         const size_t w = ck.params().n + 1;
         std::vector<Torus> in(inputs.size() * w), out(outs_.size() * w);
         for (size_t k = 0; k < inputs.size(); k++) std::copy(inputs[k].p.begin(), inputs[k].p.end(), in.begin() + k * w);
-        check(tfhe_gpu_lut_circuit_eval(ck.ctx(), set.get(), n_inputs_, in.data(), lut_.size(), off_.data(), wire_.data(),
-                                        coef_.data(), konst_.data(), lut_.data(), outs_.size(), outs_.data(), out.data(),
-                                        levels),
+        check(tfhe_gpu_lut_circuit_eval_multi(ck.ctx(), set.get(), n_inputs_, in.data(), lut_.size(), off_.data(),
+                                              wire_.data(), coef_.data(), konst_.data(), lut_.data(), theta(), outs_.size(),
+                                              outs_.data(), out.data(), levels),
               "LutCircuit.run", ck.ctx());
         std::vector<TLWELv0> r(outs_.size(), TLWELv0(ck.params().n));
         for (size_t k = 0; k < outs_.size(); k++) std::copy(out.begin() + k * w, out.begin() + (k + 1) * w, r[k].p.begin());
@@ -769,9 +812,9 @@ class LutCircuit {
     // Inputs and outputs in HBM; async on the context stream (tfhe_gpu_lut_circuit_eval_dev).  Returns the depth.
     uint32_t runDevice(const CloudKey &ck, const LutSet &set, const Torus *inputs_dev, Torus *outputs_dev) const {
         uint32_t levels = 0;
-        check(tfhe_gpu_lut_circuit_eval_dev(ck.ctx(), set.get(), n_inputs_, inputs_dev, lut_.size(), off_.data(),
-                                            wire_.data(), coef_.data(), konst_.data(), lut_.data(), outs_.size(),
-                                            outs_.data(), outputs_dev, &levels),
+        check(tfhe_gpu_lut_circuit_eval_multi_dev(ck.ctx(), set.get(), n_inputs_, inputs_dev, lut_.size(), off_.data(),
+                                                  wire_.data(), coef_.data(), konst_.data(), lut_.data(), theta(),
+                                                  outs_.size(), outs_.data(), outputs_dev, &levels),
               "LutCircuit.runDevice", ck.ctx());
         return levels;
     }
@@ -780,8 +823,11 @@ class LutCircuit {
     size_t numOutputs() const { return outs_.size(); }
 
   private:
-    uint32_t n_inputs_ = 0;
-    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, outs_;
+    // NULL without a multi-output node: the _multi entries are then the single-output ones
+    const uint32_t *theta() const { return multi_ ? theta_.data() : nullptr; }
+    uint32_t n_inputs_ = 0, n_wires_ = 0;
+    bool multi_ = false;
+    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, theta_, outs_;
     std::vector<int32_t> coef_;
 };
 

@@ -326,50 +326,77 @@ const char *check_lut_nodes(size_t B, size_t P, size_t T, const uint32_t *term_o
     return nullptr;
 }
 
+// Node g's first output wire, relative to n_inputs (n_nodes + 1 entries: the last is the wire count).
+static const char *lut_output_offsets(size_t n_nodes, const uint32_t *theta, std::vector<size_t> &o) {
+    o.assign(n_nodes + 1, 0);
+    for (size_t g = 0; g < n_nodes; g++) {
+        if (theta && theta[g] > TFHE_LUT_MULTI_MAX_LOG) return "theta > TFHE_LUT_MULTI_MAX_LOG";
+        o[g + 1] = o[g] + ((size_t)1 << (theta ? theta[g] : 0));
+    }
+    return nullptr;
+}
+
+uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta) { return theta ? 32 - (p.nbit + 1) + theta : 0; }
+
 const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
-                                std::vector<uint32_t> &level, uint32_t &depth) {
+                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta) {
     level.assign(n_nodes, 0);
     depth = 0;
     if (n_nodes == 0) return nullptr;
-    if (n_inputs + n_nodes > 0xFFFFFFFFull) return "too many wires";
+    std::vector<size_t> o;
+    if (const char *why = lut_output_offsets(n_nodes, theta, o)) return why;
+    if (n_inputs + o[n_nodes] > 0xFFFFFFFFull) return "too many wires";
     if (term_off[0] != 0) return "term_off[0] is not 0";
+    std::vector<uint32_t> node_of;  // multi-output form: the node that drives a wire
+    if (theta) node_of.resize(o[n_nodes]);
     for (size_t g = 0; g < n_nodes; g++) {
         if (term_off[g + 1] < term_off[g]) return "term_off is not monotone";
         uint32_t r = 0;
         for (size_t k = term_off[g]; k < term_off[g + 1]; k++) {
             const size_t w = term_wire[k];
-            if (w >= n_inputs + g) return "term wire is not an earlier wire";
-            if (w >= n_inputs) r = std::max(r, level[w - n_inputs]);
+            if (w >= n_inputs + o[g]) return "term wire is not an earlier wire";
+            if (w >= n_inputs) r = std::max(r, level[theta ? node_of[w - n_inputs] : w - n_inputs]);
         }
         level[g] = r + 1;
         depth = std::max(depth, level[g]);
+        if (theta) std::fill(node_of.begin() + o[g], node_of.begin() + o[g + 1], (uint32_t)g);
     }
     return nullptr;
 }
 
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
-                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl) {
-    const size_t W = n_inputs + n_nodes;
+                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl, const uint32_t *theta) {
+    std::vector<size_t> fo;  // node g's first output wire, relative to n_inputs
+    if (const char *why = lut_output_offsets(n_nodes, theta, fo)) return why;
+    const size_t W = n_inputs + fo[n_nodes];
     if (W > 0xFFFFFFFFull) return "too many wires";
-    if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth)) return why;
+    if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth, theta))
+        return why;
     for (size_t g = 0; g < n_nodes; g++)
         if (lut[g] >= T) return "table index >= the set's size";
     for (size_t o = 0; o < n_outputs; o++)
         if (out_wires[o] >= W) return "output wire out of range";
     // slots in level order (a counting sort of the nodes by level keeps node order inside a level)
     pl.first.assign((size_t)pl.depth + 1, 0);
-    for (size_t g = 0; g < n_nodes; g++) pl.first[pl.level[g]]++;                  // level lv's count at [lv]
-    for (uint32_t lv = 1; lv <= pl.depth; lv++) pl.first[lv] += pl.first[lv - 1];  // -> its end, its start at [lv - 1]
+    pl.ofirst.assign((size_t)pl.depth + 1, 0);
+    for (size_t g = 0; g < n_nodes; g++) {
+        pl.first[pl.level[g]]++;  // level lv's count at [lv]
+        pl.ofirst[pl.level[g]] += (uint32_t)(fo[g + 1] - fo[g]);
+    }
+    for (uint32_t lv = 1; lv <= pl.depth; lv++) {  // -> its end, its start at [lv - 1]
+        pl.first[lv] += pl.first[lv - 1];
+        pl.ofirst[lv] += pl.ofirst[lv - 1];
+    }
     pl.order.assign(n_nodes, 0);
     pl.slot.assign(W, 0);
     for (size_t w = 0; w < n_inputs; w++) pl.slot[w] = (uint32_t)w;
     {
-        std::vector<uint32_t> next(pl.first.begin(), pl.first.end());
+        std::vector<uint32_t> next(pl.first.begin(), pl.first.end()), onext(pl.ofirst.begin(), pl.ofirst.end());
         for (size_t g = 0; g < n_nodes; g++) {
-            const uint32_t at = next[pl.level[g] - 1]++;
+            const uint32_t lv = pl.level[g], at = next[lv - 1]++;
             pl.order[at] = (uint32_t)g;
-            pl.slot[n_inputs + g] = (uint32_t)(n_inputs + at);
+            for (size_t j = fo[g]; j < fo[g + 1]; j++) pl.slot[n_inputs + j] = (uint32_t)(n_inputs + onext[lv - 1]++);
         }
     }
     // per-level CSR descriptors over slots, concatenated in evaluation order
@@ -379,9 +406,12 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     pl.coef.clear();
     pl.konst.clear();
     pl.lut.clear();
+    pl.theta.clear();
+    pl.fan.clear();
     pl.off.reserve(n_nodes + pl.depth);
     pl.src.reserve(terms);
     pl.coef.reserve(terms);
+    pl.fan.reserve(2 * fo[n_nodes]);
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
         pl.off.push_back((uint32_t)pl.src.size());
         for (uint32_t at = pl.first[lv - 1]; at < pl.first[lv]; at++) {
@@ -393,6 +423,11 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
             pl.off.push_back((uint32_t)pl.src.size());
             pl.konst.push_back(konst[g]);
             pl.lut.push_back(lut[g]);
+            pl.theta.push_back(theta ? theta[g] : 0u);
+            for (uint32_t j = 0; j < fo[g + 1] - fo[g]; j++) {
+                pl.fan.push_back(at - pl.first[lv - 1]);
+                pl.fan.push_back(j);
+            }
         }
     }
     pl.out_slots.resize(n_outputs);
@@ -635,6 +670,38 @@ int tfhe_lut_circuit_schedule(size_t n_inputs, size_t n_nodes, const uint32_t *t
     if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d)) return TFHE_ERR_INVALID;
     std::copy(level.begin(), level.end(), levels);
     if (depth) *depth = d;
+    return TFHE_OK;
+}
+
+int tfhe_lut_circuit_schedule_multi(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                                    const uint32_t *theta, uint32_t *levels, uint32_t *depth) {
+    if (n_nodes && (!term_off || !levels || (term_off[n_nodes] && !term_wire))) return TFHE_ERR_INVALID;
+    std::vector<uint32_t> level;
+    uint32_t d = 0;
+    if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d, theta)) return TFHE_ERR_INVALID;
+    std::copy(level.begin(), level.end(), levels);
+    if (depth) *depth = d;
+    return TFHE_OK;
+}
+
+// round_theta of the multi-output LUT bootstrap (include/tfhe_gpu.h): every word to the nearest
+// multiple of 2^s, s = 32 - (log2 N + 1) + theta, in wrapping u32; theta = 0 is the identity.
+int tfhe_lut_round_tlwe(const tfhe_params *p, uint32_t theta, const uint32_t *in, uint32_t *out, size_t B) {
+    std::string why;
+    if (!p || !params_ok(p, why) || theta > TFHE_LUT_MULTI_MAX_LOG || (B && (!in || !out))) return TFHE_ERR_INVALID;
+    const uint32_t s = lut_round_shift(*p, theta);
+    const size_t words = B * ((size_t)p->n + 1);
+    for (size_t i = 0; i < words; i++) out[i] = s ? (in[i] + (1u << (s - 1))) & ~((1u << s) - 1) : in[i];
+    return TFHE_OK;
+}
+
+// TV[h][q] = tv_{q mod nu}[h][q - (q mod nu)], nu = 2^theta, on both halves.
+int tfhe_lut_interleave(const tfhe_params *p, const uint32_t *testvecs, uint32_t theta, uint32_t *out) {
+    std::string why;
+    if (!p || !params_ok(p, why) || theta > TFHE_LUT_MULTI_MAX_LOG || !testvecs || !out) return TFHE_ERR_INVALID;
+    const size_t N = p->N, nu = (size_t)1 << theta;
+    for (size_t h = 0; h < 2; h++)
+        for (size_t q = 0; q < N; q++) out[h * N + q] = testvecs[(q % nu) * 2 * N + h * N + (q - q % nu)];
     return TFHE_OK;
 }
 

@@ -70,8 +70,13 @@ const char *check_lut_nodes(size_t B, size_t P, size_t T, const uint32_t *term_o
 // ASAP levels: level[g] = 1 + the largest level of node g's term wires (inputs are
 // level 0; a node without terms is level 1).  Wire w < n_inputs is input w, node g
 // drives wire n_inputs + g and reads earlier wires only.  nullptr, or the reason.
+// Multi-output form (theta != nullptr, n_nodes entries, each <= TFHE_LUT_MULTI_MAX_LOG): node g
+// drives the 2^theta[g] wires n_inputs + o_g + j, o_g = sum_{g' < g} 2^theta[g'], and reads wires
+// below n_inputs + o_g only; a wire's level is its node's.
 const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
-                                std::vector<uint32_t> &level, uint32_t &depth);
+                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta = nullptr);
+// round_theta's shift, s = 32 - (log2 N + 1) + theta; 0 for theta = 0 (the identity, not the formula)
+uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta);
 
 // A LUT circuit's evaluation plan.  The device wire table is laid out in
 // evaluation order, inputs | nodes of level 1 | nodes of level 2 | ..., as
@@ -79,7 +84,11 @@ const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t 
 // contiguous run of slots.  Level lv (1-based) evaluates the nodes
 // order[first[lv-1] .. first[lv]); its CSR offsets are the first[lv] - first[lv-1] + 1
 // entries of `off` from first[lv-1] + lv - 1 on and index src / coef directly;
-// src holds slots, not wires.  konst / lut are per node in evaluation order.
+// src holds slots, not wires.  konst / lut / theta are per node in evaluation order.
+// Multi-output form: slot is over the n_inputs + sum 2^theta wires, and level lv's outputs are the
+// contiguous run of slots n_inputs + ofirst[lv-1] .. n_inputs + ofirst[lv), node by node in evaluation
+// order, so the level's key switch writes the wire table directly.  fan holds one (node's index in its
+// level, coefficient) pair per output slot, in slot order.  Without theta, ofirst == first.
 struct LutCircuitPlan {
     uint32_t depth = 0;
     std::vector<uint32_t> level;  // per node
@@ -89,10 +98,14 @@ struct LutCircuitPlan {
     std::vector<uint32_t> off, src, konst, lut;
     std::vector<int32_t> coef;
     std::vector<uint32_t> out_slots;
+    std::vector<uint32_t> theta;   // per node, evaluation order (all 0 without theta)
+    std::vector<uint32_t> ofirst;  // depth + 1 entries
+    std::vector<uint32_t> fan;     // 2 words per output slot
 };
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
-                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl);
+                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl,
+                             const uint32_t *theta = nullptr);
 
 // ---- Packing key switch (tfhe_pack_tlwe here; tfhe_pack.cpp runs it on the device) ----
 // The shapes with the one-hot GEMM form (ks_gemm_supported, tfhe_kernels.hip): basebit 2 with

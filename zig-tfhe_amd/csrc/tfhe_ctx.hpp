@@ -161,6 +161,8 @@ struct Device {
     DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
     DevBuf s_rot_idx, s_rot_in;       // rotation by encrypted bits: selector / exponent / gather indices; the packed lookup's tree outputs
     DevBuf s_lut_x;                  // LUT circuits: a launch's combined ciphertexts (k_lut_combine), the bootstrap's inputs
+    DevBuf s_lut_acc;                // multi-output LUT nodes: a launch's accumulators (TRLWELv1, 8 KB per node)
+    std::string lut_multi_ks;        // ... and what last_ks names after one: the fan-out extraction, then the key switch
     DevPtr<uint32_t> d_ksk_gemm;     // gemm key switch: the MFMA-layout KSK (ks_gemm_bytes), built from d_ksk
     bool ksk_gemm_ok = false;        // d_ksk_gemm matches d_ksk
     Event level_ev;                  // level-split circuits: this device's slice of a level is computed

@@ -278,5 +278,16 @@ hipError_t launch_pack_rotate_acc(const uint32_t *in, int n_in, const uint32_t *
 // pointer, off has B + 1 entries that index src / coef, and the host has checked src[k] against the pool.
 hipError_t launch_lut_combine(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,
                               const int32_t *coef, const uint32_t *konst, uint32_t *dst, size_t B, hipStream_t s);
+// The same with the multi-output bootstrap's rounding as each word is stored: shift[i] (device, B entries)
+// is 0 for none, or s: dst word = (x + (1 << (s-1))) & ~((1 << s) - 1) in wrapping u32, 1 <= s <= 31.
+hipError_t launch_lut_combine_round(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,
+                                    const int32_t *coef, const uint32_t *konst, const uint32_t *shift, uint32_t *dst,
+                                    size_t B, hipStream_t s);
+// The fan-out of a level of multi-output nodes: output o (of M) is sampleExtractIndex(acc[fan[2 o]], fan[2 o + 1])
+// (trlwe.zig:146-162), a TLWELv1 of N + 1 = 1025 words at out_lv1 + 1025 o, ready for launch_key_switch over M
+// items.  acc: the level's TRLWELv1 accumulators, 2N words per node; fan: device pairs the host has built
+// (node < the level's nodes, coefficient < N).
+hipError_t launch_lut_fanout_extract(const uint32_t *acc, const uint32_t *fan, uint32_t *out_lv1, size_t M,
+                                     hipStream_t s, const char **used = nullptr);
 
 }  // namespace tfhe

@@ -1,6 +1,8 @@
 // tfhe_kernels_lut.hip — the linear step of a LUT circuit node on the device:
 // a small integer combination of TLWELv0 ciphertexts (TLWELv0.add / neg /
-// addMul / subMul, tlwe.zig:120-240) in front of the programmable bootstrap.
+// addMul / subMul, tlwe.zig:120-240) in front of the programmable bootstrap,
+// and the two ends of a multi-output node: the rounding of the combined words
+// and the fan-out extraction of its accumulator's first coefficients.
 // Its own unit, like tfhe_kernels_leveled.hip: the bootstrap kernels' objects
 // (tfhe_kernels.o, tfhe_kernels_whole.o), which tfhe_gpu_build_id() hashes, do
 // not change with it.  Integer arithmetic only.
@@ -33,11 +35,72 @@ __global__ __launch_bounds__(LUT_COMBINE_THREADS) void k_lut_combine(
     }
 }
 
+// k_lut_combine with the multi-output bootstrap's round_theta on each word as it is stored, so
+// the rounded x costs no extra pass: shift[i] = 0 stores the word as is, s in [1, 31] stores
+// (w + (1 << (s-1))) & ~((1 << s) - 1) in wrapping u32 (0xFFFFFFFF goes to 0).  Nodes of
+// different theta share a launch.  A kernel of its own: calls without a theta launch
+// k_lut_combine as before.
+__global__ __launch_bounds__(LUT_COMBINE_THREADS) void k_lut_combine_round(
+    const uint32_t *__restrict__ pool, const uint32_t *__restrict__ off, const uint32_t *__restrict__ src,
+    const int32_t *__restrict__ coef, const uint32_t *__restrict__ konst, const uint32_t *__restrict__ shift,
+    uint32_t *__restrict__ dst, int n1) {
+    const size_t i = blockIdx.x;
+    const uint32_t k0 = off[i], k1 = off[i + 1];
+    const uint32_t kb = konst[i], sh = shift[i];
+    const uint32_t half = sh ? 1u << (sh - 1) : 0u, mask = sh ? ~((1u << sh) - 1u) : ~0u;
+    uint32_t *y = dst + i * (size_t)n1;
+    for (int j = threadIdx.x; j < n1; j += LUT_COMBINE_THREADS) {
+        uint32_t acc = j == n1 - 1 ? kb : 0u;
+        for (uint32_t k = k0; k < k1; k++) acc += (uint32_t)coef[k] * pool[(size_t)src[k] * n1 + j];
+        y[j] = (acc + half) & mask;
+    }
+}
+
+// sampleExtractIndex(acc[node], k) (trlwe.zig:146-162) for one output per workgroup, N = 1024:
+//   p[i] = a[k - i] (i <= k), -a[N + k - i] (i > k), p[N] = b[k]
+// with (node, k) = fan[2 o], fan[2 o + 1].  Index arithmetic and negations only.  Thread t of a
+// pass writes word i = t + 256 * pass, so a wave stores 64 consecutive words, and reads word
+// (k - i) mod N: the 64 consecutive words below (k - i0) mod N in descending lane order (the span
+// wraps once per output, inside one wave for k < 64), so both sides stay whole 256-byte runs per
+// wave and every word of a[] is read once.  The output's stride is 1025 words, so 4-byte
+// accesses are the widest that are aligned for every output.
+constexpr int LUT_FANOUT_THREADS = 256;
+__global__ __launch_bounds__(LUT_FANOUT_THREADS) void k_lut_fanout_extract(const uint32_t *__restrict__ acc,
+                                                                           const uint32_t *__restrict__ fan,
+                                                                           uint32_t *__restrict__ out) {
+    const size_t o = blockIdx.x;
+    const uint32_t *x = acc + (size_t)fan[2 * o] * 2048;
+    const uint32_t k = fan[2 * o + 1] & 1023u;
+    uint32_t *p = out + o * 1025;
+    for (uint32_t i = threadIdx.x; i < 1024; i += LUT_FANOUT_THREADS) {
+        const uint32_t v = x[(k - i) & 1023u];
+        p[i] = i <= k ? v : 0u - v;
+    }
+    if (threadIdx.x == 0) p[1024] = x[1024 + k];
+}
+
 hipError_t launch_lut_combine(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,
                               const int32_t *coef, const uint32_t *konst, uint32_t *dst, size_t B, hipStream_t s) {
     if (B == 0) return hipSuccess;
     hipLaunchKernelGGL(k_lut_combine, dim3((unsigned)B), dim3(LUT_COMBINE_THREADS), 0, s, pool, off, src, coef, konst,
                        dst, P.n + 1);
+    return hipGetLastError();
+}
+
+hipError_t launch_lut_combine_round(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,
+                                    const int32_t *coef, const uint32_t *konst, const uint32_t *shift, uint32_t *dst,
+                                    size_t B, hipStream_t s) {
+    if (B == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lut_combine_round, dim3((unsigned)B), dim3(LUT_COMBINE_THREADS), 0, s, pool, off, src, coef,
+                       konst, shift, dst, P.n + 1);
+    return hipGetLastError();
+}
+
+hipError_t launch_lut_fanout_extract(const uint32_t *acc, const uint32_t *fan, uint32_t *out_lv1, size_t M,
+                                     hipStream_t s, const char **used) {
+    if (M == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lut_fanout_extract, dim3((unsigned)M), dim3(LUT_FANOUT_THREADS), 0, s, acc, fan, out_lv1);
+    if (used) *used = "k_lut_fanout_extract";
     return hipGetLastError();
 }
 

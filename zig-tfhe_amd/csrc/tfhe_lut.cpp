@@ -3,7 +3,10 @@
 // with the node's own table", and the level-scheduled evaluator for DAGs of such
 // nodes.  Host code: the combination runs in tfhe_kernels_lut.hip, the bootstrap
 // is run_bootstrap_dev with a per-item table selector (KParams::tv_sel), and the
-// planner is in tfhe_cpu.cpp.  Everything here runs on the context's first device.
+// planner is in tfhe_cpu.cpp.  A multi-output node (theta > 0) rounds x in the
+// combine kernel, keeps the accumulator (RUN_TRLWE) and extracts its first 2^theta
+// coefficients in front of one key switch over the outputs.  Everything here runs on
+// the context's first device.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -63,23 +66,97 @@ static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *
     return rc ? rc : io.finish();
 }
 
+// The multi-output form of a launch of B nodes with M >= B outputs: x (rounded per node by shift[])
+// -> one accumulator per node -> the M extractions fan[] names -> one key switch into out
+// (M TLWELv0).  desc pointers are device copies; the caller has ensured s_lut_x.
+static int lut_multi_launch(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, const uint32_t *off,
+                            const uint32_t *src, const int32_t *coef, const uint32_t *konst, const uint32_t *lut,
+                            const uint32_t *shift, const uint32_t *fan, uint32_t *out, size_t B, size_t M) {
+    int rc = ensure(d, d.s_lut_acc, B * 2 * (size_t)d.P.N * sizeof(uint32_t));
+    if (!rc) rc = ensure(d, d.s_lv1, M * 1025 * 4 + KS_GEMM_INPUT_SLACK);
+    if (rc) return rc;
+    uint32_t *x = d.s_lut_x.as<uint32_t>(), *acc = d.s_lut_acc.as<uint32_t>(), *lv1 = d.s_lv1.as<uint32_t>();
+    HIPCHK(d, launch_lut_combine_round(d.K, pool, off, src, coef, konst, shift, x, B, d.stream));
+    const size_t ev_at = d.ev_used;
+    if ((rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, acc, B, RUN_TRLWE, nullptr, lut))) return rc;
+    const char *fan_name = "";
+    HIPCHK(d, launch_lut_fanout_extract(acc, fan, lv1, M, d.stream, &fan_name));
+    KsGemm G;
+    if ((rc = ks_gemm_args(d, M, G))) return rc;
+    HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, M, d.stream, d.opts, &d.last_ks, &G));
+    // last_kernels: the blind rotation, then the fan-out extraction and the key switch
+    d.lut_multi_ks = std::string(fan_name) + " + " + d.last_ks;
+    d.last_ks = d.lut_multi_ks.c_str();
+    // profiling: the launch's third event moves behind the epilogue, so (ev1, ev2) times extract + key switch
+    if (d.ev_used == ev_at + 3) HIPCHK(d, hipEventRecord(d.events[ev_at + 2], d.stream));
+    return TFHE_OK;
+}
+
+// round_theta's shift per node and the (node, coefficient) pair per output, for the nodes theta[0 .. B)
+static void multi_descriptors(const tfhe_params &P, const uint32_t *theta, size_t B, std::vector<uint32_t> &shift,
+                              std::vector<uint32_t> &fan) {
+    for (size_t i = 0; i < B; i++) {
+        shift.push_back(lut_round_shift(P, theta[i]));
+        for (uint32_t j = 0; j < (1u << theta[i]); j++) fan.push_back((uint32_t)i), fan.push_back(j);
+    }
+}
+
+// lut_apply_on for nodes of which one at least has theta > 0: out takes sum 2^theta[i] ciphertexts.
+static int lut_apply_multi_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, size_t P,
+                              const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                              const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, uint32_t *out, size_t B,
+                              bool dev) {
+    if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), terms = term_off[B];
+    std::vector<uint32_t> shift, fan;
+    multi_descriptors(d.P, theta, B, shift, fan);
+    const size_t M = fan.size() / 2;
+    DescBlob blob;
+    const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
+                 coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B),
+                 shift_at = blob.add(shift.data(), B), fan_at = blob.add(fan.data(), fan.size());
+    Io io{d, dev};
+    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
+    if (!rc && terms) rc = io.in(d.s_a, pool, P * w * 4);
+    if (!rc) rc = io.out(out, M * w * 4);
+    if (!rc) rc = ensure(d, d.s_lut_x, B * w * 4);
+    if (rc) return rc;
+    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
+    rc = lut_multi_launch(d, set, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
+                          desc + konst_at, desc + lut_at, desc + shift_at, desc + fan_at, out, B, M);
+    return rc ? rc : io.finish();
+}
+
 // A whole LUT circuit: one combine and one bootstrap launch per level into the
 // wire table (d.s_wires, in the plan's slot order), the outputs gathered at the end.
 static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
                           const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev) {
     if (n_nodes && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
-    const size_t w = tlwe0_words(d.P), W = n_inputs + n_nodes;
+    const size_t w = tlwe0_words(d.P), W = pl.slot.size();  // inputs + every node's outputs
     size_t widest = 0;
     for (uint32_t lv = 1; lv <= pl.depth; lv++) widest = std::max<size_t>(widest, pl.first[lv] - pl.first[lv - 1]);
+    // multi-output nodes anywhere: round_theta's shift per node (evaluation order) and the plan's fan-out pairs
+    const bool multi = std::any_of(pl.theta.begin(), pl.theta.end(), [](uint32_t t) { return t != 0; });
+    std::vector<uint32_t> shift;
+    if (multi)
+        for (uint32_t t : pl.theta) shift.push_back(lut_round_shift(d.P, t));
     DescBlob blob;
     const size_t off_at = blob.add(pl.off.data(), pl.off.size()), src_at = blob.add(pl.src.data(), pl.src.size()),
                  coef_at = blob.add(pl.coef.data(), pl.coef.size()), konst_at = blob.add(pl.konst.data(), n_nodes),
-                 lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs);
+                 lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs),
+                 shift_at = blob.add(shift.data(), shift.size()),
+                 fan_at = multi ? blob.add(pl.fan.data(), pl.fan.size()) : 0;
     Io io{d, dev};
     int rc = ensure(d, d.s_wires, std::max<size_t>(W, 1) * w * 4);
     // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
     if (!rc && !blob.words.empty()) rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
     if (!rc) rc = ensure(d, d.s_lut_x, std::max<size_t>(widest, 1) * w * 4);
+    if (!rc && multi) {  // the widest level's accumulators and extractions now: no level grows them mid-circuit
+        size_t widest_out = 0;
+        for (uint32_t lv = 1; lv <= pl.depth; lv++) widest_out = std::max<size_t>(widest_out, pl.ofirst[lv] - pl.ofirst[lv - 1]);
+        rc = ensure(d, d.s_lut_acc, widest * 2 * (size_t)d.P.N * sizeof(uint32_t));
+        if (!rc) rc = ensure(d, d.s_lv1, widest_out * 1025 * 4 + KS_GEMM_INPUT_SLACK);
+    }
     if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w * 4);
     if (rc) return rc;
     if (n_inputs)
@@ -88,12 +165,20 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     const uint32_t *desc = d.s_cidx.as<const uint32_t>();
     uint32_t *wires = d.s_wires.as<uint32_t>(), *x = d.s_lut_x.as<uint32_t>();
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
-        const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at;
+        const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at, oat = pl.ofirst[lv - 1], no = pl.ofirst[lv] - oat;
+        uint32_t *level_out = wires + (n_inputs + oat) * w;  // the level's outputs: one run of slots
+        if (no != nb) {  // a theta > 0 in this level
+            rc = lut_multi_launch(d, set, wires, desc + off_at + at + (lv - 1), desc + src_at,
+                                  reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at,
+                                  desc + lut_at + at, desc + shift_at + at, desc + fan_at + 2 * oat, level_out, nb, no);
+            if (rc) return rc;
+            continue;
+        }
         // reads slots below this level's first (earlier wires), writes the staging buffer
         HIPCHK(d, launch_lut_combine(d.K, wires, desc + off_at + at + (lv - 1), desc + src_at,
                                      reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at, x, nb,
                                      d.stream));
-        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, wires + (n_inputs + at) * w, nb, RUN_BOOTSTRAP, nullptr,
+        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, level_out, nb, RUN_BOOTSTRAP, nullptr,
                                desc + lut_at + at);
         if (rc) return rc;
     }
@@ -101,9 +186,10 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     return io.finish();
 }
 
+// theta: NULL for the single-output entries
 static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
                        const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst,
-                       const uint32_t *lut, uint32_t *out, size_t B, bool dev) {
+                       const uint32_t *lut, const uint32_t *theta, uint32_t *out, size_t B, bool dev) {
     if (!c || !set || (B && (!term_off || !konst || !lut || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
     if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
@@ -112,15 +198,23 @@ static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint3
     if (term_off[B] && (!term_src || !term_coef || !pool)) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (const char *why = check_lut_nodes(B, P, set->T, term_off, term_src, lut))
         return fail(c, TFHE_ERR_INVALID, std::string("LUT batch: ") + why);
+    bool multi = false;
+    for (size_t i = 0; theta && i < B; i++) {
+        if (theta[i] > TFHE_LUT_MULTI_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "LUT batch: theta > TFHE_LUT_MULTI_MAX_LOG");
+        multi |= theta[i] != 0;
+    }
+    if (multi && B > 0xFFFFFFFFull >> TFHE_LUT_MULTI_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "LUT batch: too many outputs");
     return on_device0(c, [&](Device &d) {
-        return lut_apply_on(d, *set, pool, P, term_off, term_src, term_coef, konst, lut, out, B, dev);
+        // all thetas 0: exactly the single-output path
+        return multi ? lut_apply_multi_on(d, *set, pool, P, term_off, term_src, term_coef, konst, lut, theta, out, B, dev)
+                     : lut_apply_on(d, *set, pool, P, term_off, term_src, term_coef, konst, lut, out, B, dev);
     });
 }
 
 static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
                          size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
-                         const uint32_t *konst, const uint32_t *lut, size_t n_outputs, const uint32_t *out_wires,
-                         uint32_t *outputs, uint32_t *levels, bool dev) {
+                         const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, size_t n_outputs,
+                         const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels, bool dev) {
     if (!c || !set || (n_inputs && !inputs) || (n_nodes && (!term_off || !konst || !lut)) ||
         (n_outputs && (!out_wires || !outputs)))
         return fail(c, TFHE_ERR_INVALID, "null argument");
@@ -129,7 +223,7 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
     if (n_nodes && term_off[n_nodes] && (!term_wire || !term_coef)) return fail(c, TFHE_ERR_INVALID, "null argument");
     LutCircuitPlan pl;
     if (const char *why = plan_lut_circuit(n_inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, set->T,
-                                           n_outputs, out_wires, pl))
+                                           n_outputs, out_wires, pl, theta))
         return fail(c, TFHE_ERR_INVALID, std::string("LUT circuit: ") + why);
     const int rc = on_device0(
         c, [&](Device &d) { return lut_circuit_on(d, *set, n_inputs, inputs, n_nodes, pl, n_outputs, outputs, dev); });
@@ -166,21 +260,35 @@ void tfhe_gpu_lut_set_destroy(tfhe_gpu_lut_set *set) { delete set; }
 int tfhe_gpu_lut_apply_batch(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
                              const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
                              const uint32_t *konst, const uint32_t *lut, uint32_t *out, size_t B) {
-    return apply_entry(c, set, pool, P, term_off, term_src, term_coef, konst, lut, out, B, false);
+    return apply_entry(c, set, pool, P, term_off, term_src, term_coef, konst, lut, nullptr, out, B, false);
 }
 
 int tfhe_gpu_lut_apply_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool_dev, size_t P,
                            const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
                            const uint32_t *konst, const uint32_t *lut, uint32_t *out_dev, size_t B) {
-    return apply_entry(c, set, pool_dev, P, term_off, term_src, term_coef, konst, lut, out_dev, B, true);
+    return apply_entry(c, set, pool_dev, P, term_off, term_src, term_coef, konst, lut, nullptr, out_dev, B, true);
+}
+
+int tfhe_gpu_lut_apply_multi_batch(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool, size_t P,
+                                   const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                                   const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, uint32_t *out,
+                                   size_t B) {
+    return apply_entry(c, set, pool, P, term_off, term_src, term_coef, konst, lut, theta, out, B, false);
+}
+
+int tfhe_gpu_lut_apply_multi_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint32_t *pool_dev, size_t P,
+                                 const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                                 const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, uint32_t *out_dev,
+                                 size_t B) {
+    return apply_entry(c, set, pool_dev, P, term_off, term_src, term_coef, konst, lut, theta, out_dev, B, true);
 }
 
 int tfhe_gpu_lut_circuit_eval(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
                               size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                               const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t n_outputs,
                               const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels) {
-    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, n_outputs,
-                         out_wires, outputs, levels, false);
+    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, nullptr,
+                         n_outputs, out_wires, outputs, levels, false);
 }
 
 int tfhe_gpu_lut_circuit_eval_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs,
@@ -188,8 +296,26 @@ int tfhe_gpu_lut_circuit_eval_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, 
                                   const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
                                   const uint32_t *lut, size_t n_outputs, const uint32_t *out_wires,
                                   uint32_t *outputs_dev, uint32_t *levels) {
-    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, n_outputs,
-                         out_wires, outputs_dev, levels, true);
+    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, nullptr,
+                         n_outputs, out_wires, outputs_dev, levels, true);
+}
+
+int tfhe_gpu_lut_circuit_eval_multi(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                    const uint32_t *inputs, size_t n_nodes, const uint32_t *term_off,
+                                    const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                    const uint32_t *lut, const uint32_t *theta, size_t n_outputs,
+                                    const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels) {
+    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, theta, n_outputs,
+                         out_wires, outputs, levels, false);
+}
+
+int tfhe_gpu_lut_circuit_eval_multi_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs,
+                                        const uint32_t *inputs_dev, size_t n_nodes, const uint32_t *term_off,
+                                        const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                        const uint32_t *lut, const uint32_t *theta, size_t n_outputs,
+                                        const uint32_t *out_wires, uint32_t *outputs_dev, uint32_t *levels) {
+    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, theta,
+                         n_outputs, out_wires, outputs_dev, levels, true);
 }
 
 }  // extern "C"

@@ -224,6 +224,18 @@ _SIGS = {
     "tfhe_gpu_lut_circuit_eval_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p,
                                                 C.c_size_t, u32p, vp, C.POINTER(C.c_uint32)]),
     "tfhe_lut_circuit_schedule": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, C.POINTER(C.c_uint32)]),
+    "tfhe_lut_round_tlwe": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, u32p, u32p, C.c_size_t]),
+    "tfhe_lut_interleave": (C.c_int, [C.POINTER(TfheParams), u32p, C.c_uint32, u32p]),
+    "tfhe_gpu_lut_apply_multi_batch": (C.c_int, [vp, vp, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, u32p,
+                                                 C.c_size_t]),
+    "tfhe_gpu_lut_apply_multi_dev": (C.c_int, [vp, vp, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, vp,
+                                               C.c_size_t]),
+    "tfhe_gpu_lut_circuit_eval_multi": (C.c_int, [vp, vp, C.c_size_t, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p,
+                                                  u32p, C.c_size_t, u32p, u32p, C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_lut_circuit_eval_multi_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, u32p, u32p, i32p, u32p,
+                                                      u32p, u32p, C.c_size_t, u32p, vp, C.POINTER(C.c_uint32)]),
+    "tfhe_lut_circuit_schedule_multi": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, u32p,
+                                                  C.POINTER(C.c_uint32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -777,6 +789,49 @@ class Context:
         self.check(self.lib.tfhe_gpu_lut_apply_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), vp(out_ptr), d.B),
                    "lut_apply_dev")
 
+    def lut_apply_multi(self, lut_set: "LutSet", pool, nodes, theta=None):
+        """tfhe_gpu_lut_apply_multi_batch: lut_apply with theta[i] per node (None: all 0); node i gives the 2^theta[i]
+        outputs of its interleaved table lut_set[lut] (lut_interleave) from one blind rotation of the rounded x.
+        pool (P, n+1) -> (sum 2^theta, n+1), node-major."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        th, thp = _theta(theta, d.B)
+        out = np.zeros((d.B if th is None else int((1 << th.astype(np.uint64)).sum()), self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_apply_multi_batch(self.h, lut_set.h, pp, pool.shape[0], *d.pointers(), thp,
+                                                           out.ctypes.data_as(u32p), d.B), "lut_apply_multi")
+        return out
+
+    def lut_apply_multi_dev(self, lut_set: "LutSet", pool_ptr, P, nodes, theta, out_ptr):
+        """tfhe_gpu_lut_apply_multi_dev: the pool and the sum 2^theta outputs in HBM, async on the context stream."""
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        self.check(self.lib.tfhe_gpu_lut_apply_multi_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), thp,
+                                                         vp(out_ptr), d.B), "lut_apply_multi_dev")
+
+    def lut_circuit_eval_multi(self, lut_set: "LutSet", inputs, nodes, theta, out_wires):
+        """tfhe_gpu_lut_circuit_eval_multi: node g drives 2^theta[g] consecutive wires -> (outputs, depth)."""
+        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        ow, owp = _u32(out_wires)
+        out = np.zeros((ow.size, self.n1), np.uint32)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_multi(self.h, lut_set.h, inputs.shape[0], ip, d.B, *d.pointers(),
+                                                            thp, ow.size, owp, out.ctypes.data_as(u32p),
+                                                            C.byref(depth)), "lut_circuit_eval_multi")
+        return out, depth.value
+
+    def lut_circuit_eval_multi_dev(self, lut_set: "LutSet", inputs_ptr, n_inputs, nodes, theta, out_wires, outputs_ptr):
+        """tfhe_gpu_lut_circuit_eval_multi_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        ow, owp = _u32(out_wires)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_multi_dev(self.h, lut_set.h, n_inputs, vp(inputs_ptr), d.B,
+                                                                *d.pointers(), thp, ow.size, owp, vp(outputs_ptr),
+                                                                C.byref(depth)), "lut_circuit_eval_multi_dev")
+        return depth.value
+
     def lut_circuit_eval(self, lut_set: "LutSet", inputs, nodes, out_wires):
         """tfhe_gpu_lut_circuit_eval: nodes as in lut_apply with wires for sources -> (outputs, depth)."""
         inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
@@ -1041,6 +1096,43 @@ def pack_tlwe_host(params: TfheParams, rows, basebit: int, t: int, cts, coef) ->
     return out
 
 
+LUT_MULTI_MAX_LOG = 3
+
+
+def _theta(theta, B):
+    """theta per node for the C ABI: (array or None, pointer or NULL)."""
+    if theta is None:
+        return None, None
+    th = np.ascontiguousarray(theta, np.uint32).reshape(-1)
+    if th.size != B:
+        raise ValueError(f"theta needs one entry per node ({B}), got {th.size}")
+    return th, th.ctypes.data_as(u32p)
+
+
+def lut_round_tlwe(params: TfheParams, theta: int, cts) -> np.ndarray:
+    """tfhe_lut_round_tlwe (host only): round_theta of the multi-output bootstrap on every word, (B, n+1) u32."""
+    x, xp = _u32(np.asarray(cts, np.uint32).reshape(-1, params.n + 1))
+    out = np.zeros_like(x)
+    rc = load_library().tfhe_lut_round_tlwe(C.byref(params), theta, xp, out.ctypes.data_as(u32p), x.shape[0])
+    if rc:
+        raise TfheError(f"lut_round_tlwe: {rc}", rc)
+    return out
+
+
+def lut_interleave(params: TfheParams, tables) -> np.ndarray:
+    """tfhe_lut_interleave (host only): 1, 2, 4 or 8 test vectors ((nu, 2N) u32) -> the one whose coefficient j,
+    after a rotation by a multiple of nu, holds table j's value."""
+    t, tp = _u32(np.asarray(tables, np.uint32).reshape(-1, 2 * params.N))
+    nu = t.shape[0]
+    if nu not in (1, 2, 4, 8):
+        raise ValueError(f"lut_interleave takes 1, 2, 4 or 8 tables, got {nu}")
+    out = np.zeros(2 * params.N, np.uint32)
+    rc = load_library().tfhe_lut_interleave(C.byref(params), tp, nu.bit_length() - 1, out.ctypes.data_as(u32p))
+    if rc:
+        raise TfheError(f"lut_interleave: {rc}", rc)
+    return out
+
+
 class LutSet:
     """T test vectors ((T, 2N) u32 TRLWELv1, e.g. lut_generate's) resident in HBM (tfhe_gpu_lut_set): the
     tables of Context.lut_apply and LutCircuit, addressed by index."""
@@ -1113,21 +1205,34 @@ class LutCircuit:
     def __init__(self):
         self.n_inputs = 0
         self.nodes = []  # (lut, terms, const)
+        self.theta = []  # per node: log2 of its output count
+        self.n_wires = 0
         self.outputs = []
 
     def input(self) -> int:
         if self.nodes:
             raise ValueError("declare every input before the first node")
         self.n_inputs += 1
+        self.n_wires += 1
         return self.n_inputs - 1
 
-    def node(self, lut: int, terms=(), const: int = 0) -> int:
-        w = self.n_inputs + len(self.nodes)
+    def node(self, lut: int, terms=(), const: int = 0, outputs: int = 1):
+        """-> the node's wire; with outputs = 2, 4 or 8 (a multi-output node: lut is a lut_interleave table, the
+        input is rounded to log2(outputs) fewer bits) the list of its wires, one per interleaved table."""
+        if outputs not in (1, 2, 4, 8):
+            raise ValueError("a node has 1, 2, 4 or 8 outputs")
+        w = self.n_wires
         terms = [(int(s), int(c)) for s, c in terms]
         if any(not 0 <= s < w for s, _ in terms):
             raise ValueError("node terms must read existing wires")
         self.nodes.append((int(lut), terms, int(const)))
-        return w
+        self.theta.append(outputs.bit_length() - 1)
+        self.n_wires += outputs
+        return w if outputs == 1 else list(range(w, w + outputs))
+
+    @property
+    def multi(self) -> bool:
+        return any(self.theta)
 
     def output(self, *wires):
         self.outputs.extend(wires)
@@ -1142,6 +1247,16 @@ class LutCircuit:
             carry = self.node(carry_lut, terms)
         return out + [carry]
 
+    def radix_add_fused(self, a_digits, b_digits, lut: int):
+        """radix_add with one two-output node per digit: lut is lut_interleave of the (message, carry) tables, at
+        half the message modulus radix_add's tables may use (one bit of room pays for the second output)."""
+        out, carry = [], None
+        for a, b in zip(a_digits, b_digits):
+            terms = [(a, 1), (b, 1)] + ([(carry, 1)] if carry is not None else [])
+            msg, carry = self.node(lut, terms, outputs=2)
+            out.append(msg)
+        return out + [carry]
+
     def packed(self) -> LutNodes:
         return pack_lut_nodes(self.nodes)
 
@@ -1151,8 +1266,13 @@ class LutCircuit:
         d = self.packed()
         levels = np.zeros(max(d.B, 1), np.uint32)
         depth = C.c_uint32(0)
-        rc = lib.tfhe_lut_circuit_schedule(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
-                                           d.src.ctypes.data_as(u32p), levels.ctypes.data_as(u32p), C.byref(depth))
+        if self.multi:
+            rc = lib.tfhe_lut_circuit_schedule_multi(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
+                                                     d.src.ctypes.data_as(u32p), _theta(self.theta, d.B)[1],
+                                                     levels.ctypes.data_as(u32p), C.byref(depth))
+        else:
+            rc = lib.tfhe_lut_circuit_schedule(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
+                                               d.src.ctypes.data_as(u32p), levels.ctypes.data_as(u32p), C.byref(depth))
         if rc:
             raise TfheError(f"lut_circuit_schedule: status {rc}", rc)
         return levels[:d.B], depth.value
@@ -1161,10 +1281,16 @@ class LutCircuit:
         inputs = np.asarray(inputs, np.uint32).reshape(-1, ctx.params.n + 1)
         if inputs.shape[0] != self.n_inputs:
             raise ValueError(f"circuit has {self.n_inputs} inputs, got {inputs.shape[0]}")
+        if self.multi:
+            return ctx.lut_circuit_eval_multi(lut_set, inputs, self.packed(), self.theta,
+                                              np.array(self.outputs, np.uint32))
         return ctx.lut_circuit_eval(lut_set, inputs, self.packed(), np.array(self.outputs, np.uint32))
 
     def run_dev(self, ctx: "Context", lut_set: LutSet, inputs_ptr, outputs_ptr):
         """Inputs (n_inputs TLWELv0) and outputs in HBM; returns the bootstrap depth."""
+        if self.multi:
+            return ctx.lut_circuit_eval_multi_dev(lut_set, inputs_ptr, self.n_inputs, self.packed(), self.theta,
+                                                  np.array(self.outputs, np.uint32), outputs_ptr)
         return ctx.lut_circuit_eval_dev(lut_set, inputs_ptr, self.n_inputs, self.packed(),
                                         np.array(self.outputs, np.uint32), outputs_ptr)
 
