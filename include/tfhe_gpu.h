@@ -39,7 +39,8 @@ extern "C" {
                                    and the packing key switch (tfhe_gpu_packing_key_*, tfhe_gpu_pack_tlwe_*,
                                    tfhe_pack_tlwe, TFHE_OPT_PACK_SCRATCH_MB) and the multi-output LUT bootstrap
                                    (tfhe_lut_round_tlwe, tfhe_lut_interleave, tfhe_gpu_lut_apply_multi_*,
-                                   tfhe_gpu_lut_circuit_eval_multi*, tfhe_lut_circuit_schedule_multi);
+                                   tfhe_gpu_lut_circuit_eval_multi*, tfhe_lut_circuit_schedule_multi) and the
+                                   packed scatter-add (tfhe_gpu_packed_scatter_add_*, TFHE_OPT_SCATTER_SCRATCH_MB);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -226,9 +227,13 @@ enum {
                                      a level has >= 4 pairs per query, workgroups of 4 CMUXes that stage their
                                      shared selector's rows in LDS once.  Same words either way;
                                      tfhe_gpu_last_kernels names what the last lookup ran */
-    TFHE_OPT_PACK_SCRATCH_MB = 19 /* packing key switch: bound in MB on the context scratch that holds a chunk's
+    TFHE_OPT_PACK_SCRATCH_MB = 19,/* packing key switch: bound in MB on the context scratch that holds a chunk's
                                      GEMM sums, 1..256 (default 256).  Same words at any value; tests lower it to
                                      run a small batch in several chunks */
+    TFHE_OPT_SCATTER_SCRATCH_MB = 20 /* packed scatter-add: bound in MB on the context scratch that holds a chunk's
+                                     leaves, 1..256 (default 256): max(1, bound / (2^v * 8 KB)) queries per chunk.
+                                     Same words at any value; tests lower it to run a small batch in several
+                                     chunks */
 };
 enum { TFHE_STAGING_PAGEABLE = 0, TFHE_STAGING_PINNED = 1 };  /* TFHE_OPT_HOST_STAGING */
 /* TFHE_ARITH_AUTO (default): at the L=3 / Bg=2^6 sets the blind rotation
@@ -483,6 +488,31 @@ int tfhe_gpu_packed_lookup_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *se
                                  uint32_t *out_trlwe /*Q*2N*/, size_t Q);
 int tfhe_gpu_packed_lookup_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
                                uint32_t k, uint32_t width, const uint32_t *table_dev, uint32_t *out_dev, size_t Q);
+/* Packed scatter-add, the write beside the packed lookup: table (shape and address bits as above) takes Q
+ * TRLWELv1 delta[q], each moved to the slot its address names and added there.  With d = delta[q]:
+ *   rotate: for j = 0 .. h-1 in this order, d <- trgsw.cmux(d, X^(stride * 2^j) * d, set[addr[q*k + j]]), i.e.
+ *           tfhe_gpu_rotate_by_bits_* with rot[j] = stride << j, the inverse of the lookup's rotation;
+ *   demux:  level l = 0 .. v-1 runs under address bit k-1-l (most significant first); level 0 has the one node
+ *           d; node i of level l with value x has the children 2i + 1 = hi = externalProductWithFft(selector, x)
+ *           (trgsw.zig:111-154, the words of tfhe_gpu_external_product_batch) and 2i = lo = x - hi; leaf i of
+ *           level v belongs to table TRLWE i: leaf address_q >> h carries d, every other leaf noise only;
+ *   add:    table[i] += the sum over q of leaf i of query q.
+ * Every add and subtraction is a wrapping u32 one on all 2N words, so the order of the sum, the chunking of the
+ * queries and the launch shape change no word.  The phase of coefficients 0 .. width-1 of entry address_q grows by
+ * the phase of coefficients 0 .. width-1 of delta[q]; queries with the same address all add.  h + (2^v - 1)
+ * external products per query; width > N/2 gives stride = N, h = 0: the scatter into a table of whole TRLWEs.
+ * Runs on the context's first device and needs no cloud key.  k >= 1, 1 <= width <= N, v <= 12, every addr[] < the
+ * set's size (TFHE_ERR_INVALID otherwise, before any upload or launch); Q = 0 leaves the table as it is.  addr is a
+ * HOST array in both variants; the _dev one takes delta and the table in HBM, updates the table in place, is
+ * asynchronous on the context stream and refuses a multi-device context.  delta must not overlap table.  Queries
+ * run in chunks whose leaves (2^v TRLWELv1 per query) stay within TFHE_OPT_SCATTER_SCRATCH_MB of context scratch
+ * (+ half of it for the level before). */
+int tfhe_gpu_packed_scatter_add_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
+                                      uint32_t k, uint32_t width, const uint32_t *delta /*Q*2N*/,
+                                      uint32_t *table /*2^v*2N, in and out*/, size_t Q);
+int tfhe_gpu_packed_scatter_add_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
+                                    uint32_t k, uint32_t width, const uint32_t *delta_dev,
+                                    uint32_t *table_dev /*in place*/, size_t Q);
 /* sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (host, each < N) of each of B TRLWELv1,
  * TRLWE-major; key_switch != 0 adds identityKeySwitching (trgsw.zig:471-502; TFHE_ERR_NO_KEY without a cloud
  * key): out = B*C*(N+1) or B*C*(n+1) words, ordinary TLWELv1 / TLWELv0 (gate inputs). */

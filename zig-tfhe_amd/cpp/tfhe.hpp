@@ -12,7 +12,8 @@
 //   trlwe.zig         -> tfhe::TRLWELv1 (encryptF64 / encryptBool / decryptBool, sampleExtractIndex)
 //   trgsw.zig         -> tfhe::TRGSWLv1FFT::encryptTorus (encryptTorus + TRGSWLv1FFT.new), tfhe::cmux, tfhe::rotateByBits,
 //                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits),
-//                        tfhe::PackingKey / tfhe::packTlwe (identityKeySwitching's arithmetic with TRLWE rows)
+//                        tfhe::PackingKey / tfhe::packTlwe (identityKeySwitching's arithmetic with TRLWE rows),
+//                        tfhe::packedScatterAdd / tfhe::packedWrite (writes into a tfhe::PackedTableLookup)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
 #pragma once
@@ -487,6 +488,46 @@ inline std::vector<TRLWELv1> packTlwe(const CloudKey &ck, const PackingKey &key,
     std::vector<TRLWELv1> r(B);
     for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * W, out.begin() + (b + 1) * W, r[b].p.begin());
     return r;
+}
+
+// tfhe_gpu_packed_scatter_add_batch, the write beside PackedTableLookup::lookup: delta[q] is rotated to the slot of
+// entry address_q (addr as in lookup), routed by the demultiplexer tree to that entry's TRLWE and added to t.table
+// there (wrapping u32): the entry's coefficients 0 .. width-1 grow by delta[q]'s; queries with one address all add.
+inline void packedScatterAdd(const CloudKey &ck, const TrgswSet &set, const std::vector<uint32_t> &addr,
+                             const std::vector<TRLWELv1> &delta, PackedTableLookup &t) {
+    const size_t Q = delta.size(), w = 2 * (size_t)ck.params().N;
+    if (t.k == 0 || addr.size() != Q * t.k) throw Error(TFHE_ERR_INVALID, "packedScatterAdd: k selectors per delta");
+    if (t.table.size() != (size_t)t.plan.trlwes * w) throw Error(TFHE_ERR_INVALID, "packedScatterAdd: a table of plan.trlwes TRLWEs");
+    std::vector<Torus> d(Q * w);
+    for (size_t q = 0; q < Q; q++) std::copy(delta[q].p.begin(), delta[q].p.end(), d.begin() + q * w);
+    check(tfhe_gpu_packed_scatter_add_batch(ck.ctx(), set.get(), addr.data(), t.k, t.width, d.data(), t.table.data(), Q),
+          "packed_scatter_add", ck.ctx());
+}
+
+// Sets entry address_q of t to in[q * width + c] (bit c; fresh +-1/8 TLWELv0), from existing calls around
+// packedScatterAdd: lookup, extractBits with the key switch, the plain bootstrap of the old bits (fresh +-1/8),
+// delta = new - old' on all n + 1 words, packTlwe into coefficients 0 .. width-1, packedScatterAdd.  The addresses of
+// one call must be distinct for set semantics (the library cannot see them).  Every write adds noise to every entry, so
+// a table is refreshed after a number of writes by extraction, bootstrap and fromCiphertexts.
+inline void packedWrite(const CloudKey &ck, const TrgswSet &set, const PackingKey &key, const std::vector<uint32_t> &addr,
+                        const std::vector<TLWELv0> &in, PackedTableLookup &t) {
+    const size_t W = t.width, n1 = ck.params().n + 1;
+    if (W == 0 || in.size() % W || t.k == 0 || addr.size() != in.size() / W * t.k)
+        throw Error(TFHE_ERR_INVALID, "packedWrite: width ciphertexts and k selectors per write");
+    const size_t Q = in.size() / W;
+    std::vector<uint32_t> coef(W);
+    for (uint32_t c = 0; c < W; c++) coef[c] = c;
+    const std::vector<TRLWELv1> read = t.lookup(ck, set, addr);
+    std::vector<Torus> old(Q * W * n1), fresh(Q * W * n1);
+    for (size_t q = 0; q < Q; q++) {
+        const std::vector<TLWELv0> bits = TableLookup::extractBits(ck, read[q], coef);
+        for (size_t c = 0; c < W; c++) std::copy(bits[c].p.begin(), bits[c].p.end(), old.begin() + (q * W + c) * n1);
+    }
+    check(tfhe_gpu_bootstrap_batch(ck.ctx(), old.data(), fresh.data(), Q * W), "bootstrap", ck.ctx());
+    std::vector<TLWELv0> delta(Q * W, TLWELv0(ck.params().n));
+    for (size_t i = 0; i < Q * W; i++)
+        for (size_t x = 0; x < n1; x++) delta[i].p[x] = in[i].p[x] - fresh[i * n1 + x];
+    packedScatterAdd(ck, set, addr, packTlwe(ck, key, delta, coef), t);
 }
 
 // reencryptTLWELv0 (proxy_reenc.zig:267-306) on the GPU: the key is uploaded once to HBM; a

@@ -160,6 +160,7 @@ struct Device {
     DevBuf s_kspart;                 // gemm key switch: the K splits' partial sums
     DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
     DevBuf s_rot_idx, s_rot_in;       // rotation by encrypted bits: selector / exponent / gather indices; the packed lookup's tree outputs
+    DevBuf s_sc_a, s_sc_b, s_sc_idx;  // packed scatter-add: the demux tree's ping-pong levels (s_sc_a: the leaves), its address bits
     DevBuf s_lut_x;                  // LUT circuits: a launch's combined ciphertexts (k_lut_combine), the bootstrap's inputs
     DevBuf s_lut_acc;                // multi-output LUT nodes: a launch's accumulators (TRLWELv1, 8 KB per node)
     std::string lut_multi_ks;        // ... and what last_ks names after one: the fan-out extraction, then the key switch
@@ -174,6 +175,7 @@ struct Device {
     LaunchOpts opts{};
     int64_t circuit_pack = 1;
     int64_t pack_scratch_mb = 256;  // TFHE_OPT_PACK_SCRATCH_MB: bound on the packing key switch's GEMM sums per chunk
+    int64_t scatter_scratch_mb = 256;  // TFHE_OPT_SCATTER_SCRATCH_MB: bound on the packed scatter-add's leaves per chunk
     int64_t twiddle_source = TFHE_TWIDDLES_GLIBC;
     bool key_from_keygen = false;  // the resident BK was transformed with this device's tables
     double bk_absmax = 0.0;        // largest |BK spectrum component| of the resident key, reference scale

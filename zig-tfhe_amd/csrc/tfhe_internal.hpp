@@ -260,6 +260,25 @@ struct RotateBatch {
 };
 hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const RotateBatch &b, hipStream_t s,
                                const char **used = nullptr);
+// One level of the demultiplexer tree (k_demux / k_demux_shared), device pointers: parent g reads
+// x = src[g] and writes hi = ExtProd(selector, x) to out[2g + 1] and lo = x - hi to out[2g], under
+// selector sel[(g >> level) * sel_stride]: the 2^level parents of a query share the level's
+// selector, sel points at that bit of the first query's address and sel_stride is the number of
+// address bits per query.  out must not overlap src.
+struct DemuxBatch {
+    const double *sel_rows = nullptr;
+    const uint32_t *sel = nullptr;
+    uint32_t level = 0, sel_stride = 0;
+    const uint32_t *src = nullptr;
+    uint32_t *out = nullptr;
+    size_t B = 0;
+};
+// shared: the workgroup form, for levels of at least CMUX_SHARED_ITEMS parents per query (level >= 2).
+hipError_t launch_demux(const KParams &P, const DevTables &T, const DemuxBatch &b, bool shared, hipStream_t s,
+                        const char **used = nullptr);
+// table[i][w] += sum over q < nq of leaves[(q * trlwes + i) * 2N + w] in wrapping u32 (k_scatter_reduce),
+// device pointers; leaves must not overlap table.
+hipError_t launch_scatter_reduce(const uint32_t *leaves, size_t nq, size_t trlwes, uint32_t *table, hipStream_t s);
 // sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (device, each < N) of each
 // of B TRLWELv1: B * C TLWELv1 of N + 1 words, TRLWE-major
 hipError_t launch_sample_extract(const uint32_t *trlwe, const uint32_t *coef, size_t C, uint32_t *out_lv1, size_t B,

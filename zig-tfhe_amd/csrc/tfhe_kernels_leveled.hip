@@ -279,6 +279,140 @@ __global__ __launch_bounds__(64 * CMUX_WAVES) void k_rotate_chain(KParams P, Dev
     }
 }
 
+// One level of the demultiplexer tree (the packed scatter-add), the mirror of a
+// CMUX level: parent g with value x = src[g] has the children
+//   out[2g + 1] = hi = ExtProd(selector, x)   (externalProductWithFft, trgsw.zig:111-154)
+//   out[2g]     = lo = x - hi                 (wrapping u32 on all 2N words)
+// so x goes on to the child the selector names and noise to the other.  One wavefront per parent
+// in k_cmux's lane layout; tmp = x + offset stays in registers and the accumulators start from
+// zero, so inverse_and_add's `acc += ExtProd` leaves hi in them.  x is read again after the
+// transforms for lo (its address behind an opaque asm: hipcc otherwise keeps the first read's 32
+// registers across them).  The pairs go through ext_pairs_chain, ext_pairs_global with each
+// pair's sums completed at the pair: with ext_pairs_global hipcc defers them here as it does in
+// k_rotate_chain's loop (256 + 256 registers and 924 B of scratch per lane at L = 3 against
+// 256 + 38 and none).  The 2^level parents of a query share the level's selector,
+// sel[(g >> level) * sel_stride].  Waves past B return before they read or write anything;
+// nothing below is a workgroup barrier.
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_demux(KParams P, DevTables TT,
+                                                           const double2 *__restrict__ sel_rows,
+                                                           const uint32_t *__restrict__ sel, uint32_t level,
+                                                           uint32_t sel_stride, const uint32_t *__restrict__ src,
+                                                           uint32_t *__restrict__ out, size_t B) {
+    __shared__ C2 s_x[CMUX_WAVES][2 * 512];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), t = threadIdx.x & 63;
+    const size_t g = (size_t)blockIdx.x * CMUX_WAVES + w;
+    if (g >= B) return;
+    const uint32_t *x = src + g * 2048;
+    const double2 *row = sel_rows + (size_t)sel[(g >> level) * sel_stride] * (2 * L * 1024);
+    RegTw T;
+    T.init(TT.tw, t);
+    C2 twl[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+    uint32_t tA[16], tB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        tA[m] = x[t + 64 * m] + P.offset;
+        tB[m] = x[1024 + t + 64 * m] + P.offset;
+    }
+    C2 fa[8], fb[8];
+    ext_pairs_chain<L>(tA, tB, row, P.bgbit, T, twl, s_x[w], t, fa, fb);
+    uint32_t hiA[16], hiB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) hiA[m] = hiB[m] = 0;
+    uint32_t near = NEAR_NONE;
+    inverse_and_add<false, 1>(fa, fb, s_x[w], T, twl, t, hiA, hiB, near);
+    const uint32_t *xr = x;
+    asm volatile("" : "+s"(xr)::"memory");
+    uint32_t *lo = out + g * 4096, *hi = lo + 2048;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        hi[t + 64 * m] = hiA[m];
+        hi[1024 + t + 64 * m] = hiB[m];
+        lo[t + 64 * m] = xr[t + 64 * m] - hiA[m];
+        lo[1024 + t + 64 * m] = xr[1024 + t + 64 * m] - hiB[m];
+    }
+}
+
+// The workgroup form of a demux level, as k_cmux_shared is of a CMUX level: the 4 waves' parents
+// g0 .. g0 + 3 (g0 = 4 * blockIdx.x) belong to one query (levels of at least 4 parents per
+// query, level >= 2) and so share their selector, whose row pairs are staged in LDS once for
+// all four (ext_pairs_shared).  launch_demux refuses a B that is not a multiple of 4.
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_demux_shared(KParams P, DevTables TT,
+                                                                  const double2 *__restrict__ sel_rows,
+                                                                  const uint32_t *__restrict__ sel, uint32_t level,
+                                                                  uint32_t sel_stride,
+                                                                  const uint32_t *__restrict__ src,
+                                                                  uint32_t *__restrict__ out, size_t B) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[CS_LDS_BK + CMUX_WAVES * 2 * 512 * 16];
+    double2 *s_bk = reinterpret_cast<double2 *>(smem);
+    const int tid = threadIdx.x, t = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    C2 *s_x = reinterpret_cast<C2 *>(smem + CS_LDS_BK) + w * 2 * 512;
+    const size_t g0 = (size_t)blockIdx.x * CMUX_WAVES, g = g0 + w;  // g < B: B is a multiple of 4 (launch_demux)
+    const double2 *row = sel_rows + (size_t)sel[(g0 >> level) * sel_stride] * (2 * L * 1024);
+    RegTw T;
+    T.init(TT.tw, t);
+    C2 twl[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+    const uint32_t *x = src + g * 2048;
+    uint32_t tA[16], tB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        tA[m] = x[t + 64 * m] + P.offset;
+        tB[m] = x[1024 + t + 64 * m] + P.offset;
+    }
+    C2 fa[8], fb[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        fa[q] = c2(0.0, 0.0);
+        fb[q] = c2(0.0, 0.0);
+    }
+    ext_pairs_shared<L>(tA, tB, row, P.bgbit, T, twl, s_x, t, tid, s_bk, fa, fb);
+    uint32_t hiA[16], hiB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) hiA[m] = hiB[m] = 0;
+    uint32_t near = NEAR_NONE;
+    inverse_and_add<false, 1>(fa, fb, s_x, T, twl, t, hiA, hiB, near);
+    const uint32_t *xr = x;
+    asm volatile("" : "+s"(xr)::"memory");
+    uint32_t *lo = out + g * 4096, *hi = lo + 2048;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        hi[t + 64 * m] = hiA[m];
+        hi[1024 + t + 64 * m] = hiB[m];
+        lo[t + 64 * m] = xr[t + 64 * m] - hiA[m];
+        lo[1024 + t + 64 * m] = xr[1024 + t + 64 * m] - hiB[m];
+    }
+}
+
+// The scatter-add's sum: table[i][w] += sum over q < nq of leaves[(q * trlwes + i) * 2N + w] in
+// wrapping u32.  Block = 64 consecutive words of the table, whose lane-0-wave thread alone reads
+// and writes the word: no atomics, and integer adds commute, so the split of the queries over
+// the 16 waves (q = wave, wave + 16, ...; joined through LDS as in k_pack_rotate_acc) changes no
+// word.  One thread per word would leave a table of few TRLWEs on a handful of CUs (v = 1: 64
+// waves walking all the queries).
+constexpr int SCATTER_WAVES = 16;
+__global__ __launch_bounds__(64 * SCATTER_WAVES) void k_scatter_reduce(const uint32_t *__restrict__ leaves, size_t nq,
+                                                                       size_t trlwes, uint32_t *__restrict__ table) {
+    __shared__ uint32_t red[SCATTER_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t x = (size_t)blockIdx.x * 64 + lane;  // word of the table: TRLWE x >> 11 (the grid covers it exactly)
+    const size_t stride = trlwes * 2048;
+    uint32_t acc = 0;
+#pragma unroll 4
+    for (size_t q = wave; q < nq; q += SCATTER_WAVES) acc += leaves[q * stride + x];
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave) return;
+#pragma unroll
+    for (int w = 1; w < SCATTER_WAVES; w++) acc += red[w][lane];
+    table[x] += acc;
+}
+
 // sampleExtractIndex(trlwe, k) (trlwe.zig:146-162) for k < N = 1024: block
 // b * C + c extracts coefficient coef[c] of TRLWE b into TLWELv1 b * C + c
 // (1025 words): p[i] = a[k - i] (i <= k), -a[N + k - i] (i > k), p[N] = b[k].
@@ -392,6 +526,43 @@ hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const Rotat
     default: return hipErrorInvalidValue;
     }
     if (used) *used = name;
+    return hipGetLastError();
+}
+
+template <int L>
+static const char *demux_launch(bool shared, dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
+                                const DemuxBatch &b) {
+    const double2 *rows = reinterpret_cast<const double2 *>(b.sel_rows);
+    if (shared) {
+        hipLaunchKernelGGL(k_demux_shared<L>, grid, block, 0, s, P, T, rows, b.sel, b.level, b.sel_stride, b.src, b.out, b.B);
+        return L == 1 ? "k_demux_shared<1>" : L == 2 ? "k_demux_shared<2>" : "k_demux_shared<3>";
+    }
+    hipLaunchKernelGGL(k_demux<L>, grid, block, 0, s, P, T, rows, b.sel, b.level, b.sel_stride, b.src, b.out, b.B);
+    return L == 1 ? "k_demux<1>" : L == 2 ? "k_demux<2>" : "k_demux<3>";
+}
+
+hipError_t launch_demux(const KParams &P, const DevTables &T, const DemuxBatch &b, bool shared, hipStream_t s,
+                        const char **used) {
+    if (b.B == 0) return hipSuccess;
+    // the workgroup form's 4 parents must belong to one query
+    if (shared && (b.B % CMUX_WAVES != 0 || ((size_t)1 << b.level) < CMUX_SHARED_ITEMS)) return hipErrorInvalidValue;
+    if (b.level > 31) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((b.B + CMUX_WAVES - 1) / CMUX_WAVES)), block(64 * CMUX_WAVES);
+    const char *name = "";
+    switch (P.L) {
+    case 1: name = demux_launch<1>(shared, grid, block, s, P, T, b); break;
+    case 2: name = demux_launch<2>(shared, grid, block, s, P, T, b); break;
+    case 3: name = demux_launch<3>(shared, grid, block, s, P, T, b); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (used) *used = name;
+    return hipGetLastError();
+}
+
+hipError_t launch_scatter_reduce(const uint32_t *leaves, size_t nq, size_t trlwes, uint32_t *table, hipStream_t s) {
+    if (nq == 0 || trlwes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_scatter_reduce, dim3((unsigned)(trlwes * 32)), dim3(64 * SCATTER_WAVES), 0, s, leaves, nq, trlwes,
+                       table);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // tfhe_leveled.cpp — the leveled half of the C ABI (include/tfhe_gpu.h):
 // resident selector sets, CMUX, table lookup by a CMUX tree, rotation by
-// encrypted bits and the packed lookup built on both, and sample extraction at
+// encrypted bits and the packed lookup built on both, the packed scatter-add
+// (rotation, demultiplexer tree, sum), and sample extraction at
 // any coefficient (TRLWE / TRGSW encryption is in tfhe_encrypt.cpp).  Host code;
 // the arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
 // tfhe_kernels.hip.  Everything here runs on the context's first device and,
@@ -203,6 +204,74 @@ static int packed_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint
     return io.finish();
 }
 
+// The packed scatter-add (include/tfhe_gpu.h): one k_rotate_chain launch over all Q deltas under address bits
+// 0 .. h - 1 (rot[j] = stride << j, into context scratch), then per chunk of queries the demux tree under bits
+// k - 1 .. h, one launch per level, and one k_scatter_reduce that adds the chunk's leaves into the table.  Level l
+// (2^l parents per query) writes s_sc_a when v - 1 - l is even, so the leaves (2^v TRLWELv1 per query) end up in
+// s_sc_a and s_sc_b holds at most half as much; a chunk is as many queries as keep the leaves within
+// TFHE_OPT_SCATTER_SCRATCH_MB.  v = 0: the rotation's outputs (h = 0 as well: the deltas) are the leaves.
+// The address bits h .. k - 1 of all queries go up once; a level's parents find their selector in them.
+static int packed_scatter_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
+                             const tfhe_packed_plan &pl, const uint32_t *delta, uint32_t *table, size_t Q, bool dev) {
+    const uint32_t h = pl.h, v = pl.v;
+    const size_t leaves = (size_t)1 << v;
+    const size_t chunk = std::min(Q, std::max<size_t>(1, ((size_t)d.scatter_scratch_mb << 20) / (leaves * TRLWE_BYTES)));
+    Io io{d, dev};
+    const uint32_t *staged = table;
+    int rc = io.in(d.s_a, staged, leaves * TRLWE_BYTES);
+    if (!dev) {  // the table is this call's output as well: finish() copies the scratch copy back
+        io.host_out = table;
+        io.staged_out = staged;
+        io.out_bytes = leaves * TRLWE_BYTES;
+        table = d.s_a.as<uint32_t>();
+    }
+    if (!rc) rc = io.in(d.s_b, delta, Q * TRLWE_BYTES);
+    if (!rc && h) rc = ensure(d, d.s_rot_in, Q * TRLWE_BYTES);
+    if (!rc && v) rc = ensure(d, d.s_sc_a, chunk * leaves * TRLWE_BYTES);
+    if (!rc && v > 1) rc = ensure(d, d.s_sc_b, chunk * (leaves / 2) * TRLWE_BYTES);
+    if (rc) return rc;
+    d.last_br = d.last_ks = "";
+    if (h) {
+        std::vector<uint32_t> lo(Q * h), rot(h);
+        for (size_t q = 0; q < Q; q++) std::copy(addr + q * k, addr + q * k + h, lo.begin() + q * h);
+        for (uint32_t j = 0; j < h; j++) rot[j] = pl.stride << j;
+        rc = rotate_launch_on(d, set, lo.data(), rot.data(), h, delta, nullptr, d.s_rot_in.as<uint32_t>(), Q, &d.last_br);
+        if (rc) return rc;
+        delta = d.s_rot_in.as<const uint32_t>();
+    }
+    if (v) {
+        std::vector<uint32_t> hi(Q * v);
+        for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.begin() + q * v);
+        if ((rc = h2d(d, d.s_sc_idx, hi.data(), hi.size() * sizeof(uint32_t)))) return rc;
+    }
+    const uint32_t *bits = d.s_sc_idx.as<const uint32_t>();
+    const KParams K = leveled_params(d);
+    const DevTables T = tables(d);
+    for (size_t q0 = 0; q0 < Q; q0 += chunk) {
+        const size_t nq = std::min(chunk, Q - q0);
+        const uint32_t *prev = delta + q0 * 2048;
+        for (uint32_t l = 0; l < v; l++) {
+            DemuxBatch b;
+            b.sel_rows = set.rows;
+            b.sel = bits + q0 * v + (v - 1 - l);
+            b.level = l;
+            b.sel_stride = v;
+            b.src = prev;
+            b.out = ((v - 1 - l) & 1) ? d.s_sc_b.as<uint32_t>() : d.s_sc_a.as<uint32_t>();
+            b.B = nq << l;
+            // the workgroup form where a query has at least 4 parents, as in table_lookup_on
+            const bool shared = d.opts.cmux_form != 1 && ((size_t)1 << l) >= CMUX_SHARED_ITEMS;
+            const char *name = "";
+            HIPCHK(d, launch_demux(K, T, b, shared, d.stream, &name));
+            // last_kernels: the chain if there is one, then the first demux level's form
+            if (q0 == 0 && l == 0) (h ? d.last_ks : d.last_br) = name;
+            prev = b.out;
+        }
+        HIPCHK(d, launch_scatter_reduce(prev, nq, leaves, table, d.stream));
+    }
+    return io.finish();
+}
+
 static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *coef, size_t C, bool key_switch,
                              uint32_t *out, size_t B, bool dev) {
     if (key_switch && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
@@ -342,6 +411,31 @@ int tfhe_gpu_packed_lookup_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set,
 int tfhe_gpu_packed_lookup_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
                                uint32_t width, const uint32_t *table_dev, uint32_t *out_dev, size_t Q) {
     return packed_entry(c, set, addr, k, width, table_dev, out_dev, Q, true);
+}
+
+static int scatter_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k, uint32_t width,
+                         const uint32_t *delta, uint32_t *table, size_t Q, bool dev) {
+    if (!c || !set || !table || (Q && (!addr || !delta))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    tfhe_packed_plan pl;
+    if (tfhe_packed_lookup_plan(&c->P, k, width, &pl) != TFHE_OK)
+        return fail(c, TFHE_ERR_INVALID, "packed scatter-add: width outside 1..N, k = 0, or more than 12 address bits left to the tree");
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
+    if (Q > 0xFFFFFFFFull >> pl.v || Q > 0xFFFFFFFFull / k) return fail(c, TFHE_ERR_INVALID, "packed scatter-add: too many queries");
+    for (size_t i = 0; i < Q * k; i++)
+        if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");
+    if (Q == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return packed_scatter_on(d, *set, addr, k, pl, delta, table, Q, dev); });
+}
+
+int tfhe_gpu_packed_scatter_add_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                                      uint32_t width, const uint32_t *delta, uint32_t *table, size_t Q) {
+    return scatter_entry(c, set, addr, k, width, delta, table, Q, false);
+}
+
+int tfhe_gpu_packed_scatter_add_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                                    uint32_t width, const uint32_t *delta_dev, uint32_t *table_dev, size_t Q) {
+    return scatter_entry(c, set, addr, k, width, delta_dev, table_dev, Q, true);
 }
 
 static int extract_entry(tfhe_gpu_ctx *c, const uint32_t *trlwe, const uint32_t *coef, size_t C, int key_switch,

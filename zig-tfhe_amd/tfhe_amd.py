@@ -24,12 +24,13 @@ LIB_PATH = os.environ.get("TFHE_GPU_LIB") or os.path.join(HERE, "lib", "libtfhe_
 # tfhe_gpu_set_option keys / values (include/tfhe_gpu.h TFHE_OPT_*, TFHE_TWIDDLES_*)
 OPTIONS = {"br_form": 1, "br_loader": 2, "ks_form": 3, "ks_narrow": 4, "ks_item_groups": 5, "ks_sel_items": 6,
            "circuit_pack": 7, "twiddles": 8, "arith": 9, "br_sync": 10, "br_spin_cap": 11, "host_pipeline": 12,
-           "circuit_split": 13, "host_staging": 17, "cmux_form": 18, "pack_scratch_mb": 19}
+           "circuit_split": 13, "host_staging": 17, "cmux_form": 18, "pack_scratch_mb": 19,
+           "scatter_scratch_mb": 20}
 READONLY_OPTIONS = {"fused_admitted": 14, "level_issue_us": 15, "key_row_rms_ppm": 16}  # tfhe_gpu_get_option only
 OPTION_DEFAULTS = {"br_form": 0, "br_loader": 1, "ks_form": 3, "ks_narrow": 0, "ks_item_groups": 0,
                    "ks_sel_items": 8, "circuit_pack": 1, "twiddles": 0, "arith": 0, "br_sync": 1, "br_spin_cap": 0,
                    "host_pipeline": 0, "circuit_split": 0, "host_staging": 0, "cmux_form": 0,
-                   "pack_scratch_mb": 256}
+                   "pack_scratch_mb": 256, "scatter_scratch_mb": 256}
 # status codes (include/tfhe_gpu.h TFHE_ERR_*)
 ERR_INVALID, ERR_HIP, ERR_NO_KEY, ERR_OOM, ERR_IO, ERR_DEVICE = -1, -2, -3, -4, -5, -6
 # 2 split, 4 pair: removed (round 4); 6 duo, 7 wide2: A/B libraries only (tools/ab/, round 5); 5 octo: L = 1
@@ -208,6 +209,8 @@ _SIGS = {
                                                u32p]),
     "tfhe_gpu_packed_lookup_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t]),
     "tfhe_gpu_packed_lookup_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
+    "tfhe_gpu_packed_scatter_add_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_packed_scatter_add_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
     "tfhe_gpu_packing_key_gen": (C.c_int, [vp, u32p, u32p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, u32p]),
     "tfhe_gpu_packing_key_load": (C.c_int, [vp, u32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "tfhe_gpu_packing_key_destroy": (None, [vp]),
@@ -741,6 +744,67 @@ class Context:
         addr, ap = _u32(np.atleast_2d(addr))
         self.check(self.lib.tfhe_gpu_packed_lookup_dev(self.h, selectors.h, ap, addr.shape[1], width, vp(table_ptr),
                                                        vp(out_ptr), addr.shape[0]), "packed_lookup_dev")
+
+    def packed_scatter_add(self, selectors: "TrgswSet", addr, width: int, deltas, table):
+        """tfhe_gpu_packed_scatter_add_batch, the write beside packed_lookup: deltas (Q, 2N) TRLWELv1, addr (Q, k)
+        selector indices, bit 0 first; delta q is rotated to the slot of entry address_q, routed by the demux tree to
+        that entry's TRLWE and added there (wrapping u32), so the phase of the entry's coefficients 0 .. width-1
+        grows by that of delta q's; queries with one address all add.  -> the new table (2^v, 2N); `table` itself
+        is not changed."""
+        table, _ = _u32(np.atleast_2d(table))
+        addr, ap = _u32(np.atleast_2d(addr))
+        k = addr.shape[1]
+        plan = packed_lookup_plan(self.params, k, width)
+        if table.shape[0] != plan.trlwes:
+            raise ValueError(f"packed_scatter_add: k = {k}, width = {width} need a table of {plan.trlwes} TRLWEs, "
+                             f"got {table.shape[0]}")
+        deltas, dp = _u32(np.asarray(deltas, np.uint32).reshape(addr.shape[0], 2 * self.params.N))
+        out = table.copy()
+        self.check(self.lib.tfhe_gpu_packed_scatter_add_batch(self.h, selectors.h, ap, k, width, dp,
+                                                              out.ctypes.data_as(u32p), addr.shape[0]),
+                   "packed_scatter_add")
+        return out
+
+    def packed_scatter_add_dev(self, selectors: "TrgswSet", addr, width: int, delta_ptr, table_ptr, table_trlwes=None):
+        """tfhe_gpu_packed_scatter_add_dev: the Q deltas and the packed table in HBM, the table updated in place,
+        async on the context stream; the deltas must not overlap the table.  table_ptr: a device address with
+        table_trlwes, the number of TRLWELv1 behind it, or a tensor (data_ptr / numel), whose size is then checked
+        like packed_scatter_add's table."""
+        addr, ap = _u32(np.atleast_2d(addr))
+        k = addr.shape[1]
+        plan = packed_lookup_plan(self.params, k, width)
+        if hasattr(table_ptr, "data_ptr"):
+            table_trlwes, table_ptr = table_ptr.numel() * table_ptr.element_size() // (8 * self.params.N), table_ptr.data_ptr()
+        if hasattr(delta_ptr, "data_ptr"):
+            delta_ptr = delta_ptr.data_ptr()
+        if table_trlwes is not None and table_trlwes != plan.trlwes:
+            raise ValueError(f"packed_scatter_add_dev: k = {k}, width = {width} need a table of {plan.trlwes} TRLWEs, "
+                             f"got {table_trlwes}")
+        self.check(self.lib.tfhe_gpu_packed_scatter_add_dev(self.h, selectors.h, ap, k, width, vp(delta_ptr),
+                                                            vp(table_ptr), addr.shape[0]), "packed_scatter_add_dev")
+
+    def packed_write(self, selectors: "TrgswSet", key: "PackingKey", addr, width: int, new_cts, table):
+        """Set entry address_q of a packed table to new_cts[q] ((Q, width, n+1) TLWELv0, fresh +-1/8 per bit), from
+        existing calls around packed_scatter_add; needs the cloud key and a packing key.  -> the new table.
+          1. packed_lookup at the addresses;
+          2. sample_extract at coefficients 0 .. width-1 with the key switch: the entries' old bits;
+          3. their plain bootstrap (tfhe_gpu_bootstrap_batch): old', fresh +-1/8;
+          4. delta = new - old' on all n+1 words: 0 or +-1/4 per bit;
+          5. pack_tlwe of each query's deltas into coefficients 0 .. width-1;
+          6. packed_scatter_add.
+        The addresses of one call must be distinct for set semantics: the library cannot see them, and two writes to
+        one entry would both subtract the old value.  Every write adds noise to every entry of the table (the demux
+        tree leaves noise in the leaves it does not address, and the packed delta has noise in every coefficient), so
+        a table is refreshed after a number of writes by sample_extract, bootstrap and pack_table."""
+        addr = np.ascontiguousarray(np.atleast_2d(addr), np.uint32)
+        Q = addr.shape[0]
+        new = np.asarray(new_cts, np.uint32).reshape(Q, width, self.n1)
+        coef = np.arange(width, dtype=np.uint32)
+        read = self.packed_lookup(selectors, addr, width, table)
+        old = self.sample_extract(read, coef, key_switch=True)
+        fresh = self.bootstrap_batch(old.reshape(Q * width, self.n1)).reshape(Q, width, self.n1)
+        delta = self.pack_tlwe(key, new - fresh, coef)
+        return self.packed_scatter_add(selectors, addr, width, delta, table)
 
     # ---- packing key switch: TLWELv0 -> coefficient slots of TRLWELv1 ----
     def pack_tlwe(self, key: "PackingKey", cts, coef):
