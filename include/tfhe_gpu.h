@@ -40,7 +40,9 @@ extern "C" {
                                    tfhe_pack_tlwe, TFHE_OPT_PACK_SCRATCH_MB) and the multi-output LUT bootstrap
                                    (tfhe_lut_round_tlwe, tfhe_lut_interleave, tfhe_gpu_lut_apply_multi_*,
                                    tfhe_gpu_lut_circuit_eval_multi*, tfhe_lut_circuit_schedule_multi) and the
-                                   packed scatter-add (tfhe_gpu_packed_scatter_add_*, TFHE_OPT_SCATTER_SCRATCH_MB);
+                                   packed scatter-add (tfhe_gpu_packed_scatter_add_*, TFHE_OPT_SCATTER_SCRATCH_MB)
+                                   and the bivariate LUT bootstrap (tfhe_lut_spread, tfhe_gpu_lut_spread_*,
+                                   tfhe_gpu_bootstrap_lut_each_*, tfhe_gpu_lut_apply2_*);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -563,7 +565,8 @@ int  tfhe_pack_tlwe(const tfhe_params *params, const uint32_t *rows, uint32_t ba
                     const uint32_t *coef, size_t C, uint32_t *out_trlwe, size_t B);
 
 /* ---- LUT circuits: per-item tables and linear combinations on the device ----
- * The unit of work of multi-bit arithmetic (radix digits, comparisons, bivariate functions through a + m*b): a small
+ * The unit of work of multi-bit arithmetic (radix digits, comparisons, bivariate functions through a + m*b; two
+ * full-width digits: "Bivariate LUT bootstrap" below): a small
  * integer combination of ciphertexts, then a programmable bootstrap whose table is chosen per item.  Node i over a
  * pool of P TLWELv0 computes, in wrapping u32 arithmetic on all n+1 words (TLWELv0.add / neg / addMul / subMul,
  * tlwe.zig:120-240; term_coef is an int32 used as a Torus word in two's complement),
@@ -662,6 +665,63 @@ int tfhe_gpu_lut_circuit_eval_multi_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_se
 int tfhe_lut_circuit_schedule_multi(size_t n_inputs, size_t n_nodes, const uint32_t *term_off,
                                     const uint32_t *term_wire, const uint32_t *theta /*n_nodes*/, uint32_t *levels,
                                     uint32_t *depth);
+
+/* ---- Bivariate LUT bootstrap: a test vector built on the device per item ----
+ * Any function f(x, y) of two digits at the full message modulus m of the parameter set (UINT4: 4 + 4 bits in), where
+ * a + m*b spends half of the message room: the tree-based functional bootstrap (Guimaraes, Borin, Aranha, "Revisiting
+ * the functional bootstrap in TFHE").  y goes through the m tables f(i, .), the m results are packed into the
+ * coefficient slots of one TRLWELv1, the slots are spread into a test vector in the generator's layout, and x is
+ * bootstrapped with that encrypted test vector: m + 1 blind rotations per output digit.  Integer-exact from its second
+ * step on; with w = N/m, off = N/(2m), mulxk = polyMulWithXK (trgsw.zig:442-466) and wrapping u32 arithmetic:
+ *   spread: on each half h of a TRLWELv1 separately,
+ *       S[h] = sum_{j=0}^{w-1} mulxk(in[h], j)     (the negacyclic window sum of width w)
+ *       out[h] = mulxk(S[h], rot)
+ *     with 1 <= w <= N and 0 <= rot <= 2N (it knows nothing of m).  For in.a = 0, in.b[x*w] = Encoder.encode(f(x)),
+ *     the other coefficients 0 and rot = 2N - off, out is exactly Generator.generateLookupTableAssign's table
+ *     (lut/generator.zig:85-135), the words of tfhe_lut_generate.  w = 1, rot = 0 is the identity.
+ *   each: output i of tfhe_gpu_bootstrap_lut_each_* is, word for word, what tfhe_gpu_bootstrap_lut_batch returns for
+ *     in[i] with the test vector testvecs[i] (any a): the per-item instantiations of the blind rotation that a LUT
+ *     set runs, reading one TRLWELv1 per item from the caller's buffer.
+ *   node b of tfhe_gpu_lut_apply2_*, over a pool of P TLWELv0 and a set of F*m tables, set[fn*m + i] = the table of
+ *     y -> f_fn(i, y):
+ *       1. g[b][i] = the tfhe_gpu_lut_apply_* output of the one-term node (pool[y_src[b]], coefficient 1, konst 0,
+ *          lut = fn[b]*m + i), for i < m;
+ *       2. P_b = tfhe_pack_tlwe(g[b][0 .. m), coef[i] = i*w, C = m);
+ *       3. TV_b = spread(P_b, w, 2N - off);
+ *       4. out[b] = the tfhe_gpu_bootstrap_lut_each_* output for pool[x_src[b]] with TV_b,
+ *     so out[b] decrypts to f_fn(x, y).  Everything stays in HBM; the nodes run in chunks whose m intermediate
+ *     ciphertexts per node and whose GEMM sums stay within TFHE_OPT_PACK_SCRATCH_MB, and chunking changes no word.
+ * Noise rule (the library does not police it): the error of TV_b at the coefficient that is read is the level-1
+ * output's own noise, plus the pack's digit rounding, variance ~ (n/2) * 2^(-2*basebit*t) / 12, plus
+ * w*m*n*t*alpha_rows^2 from the packing key's rows over the summed window (N*n*t of them: w per slot, m slots).  With
+ * the packing key's default alpha (alpha_lv1) the last term vanishes at the UINT sets (2^-52 rounds to nothing in a
+ * 32-bit torus), and at UINT4 with the default pack shape (5, 3) the rounding term is sigma ~ 2e-4 against a
+ * half-spacing of 1/64 ~ 1.6e-2.  A packing key generated with alpha_lv0 instead would put sigma near 4e-3, a quarter
+ * of the half-spacing: unsafe, do not use one here.  Measured figures: DESIGN.md §4.9c.
+ * Checked before any launch or upload (TFHE_ERR_INVALID): w = 0, w > N, rot > 2N; m not a power of two, m < 2 or
+ * 2m > N; a set size that is no multiple of m; an fn[b]*m + m beyond the set; a source >= P; a set or a key of
+ * another context; a null argument.  TFHE_ERR_NO_KEY without a cloud key (spread needs none); B = 0 is TFHE_OK.  All
+ * of these run on the context's first device; fn / x_src / y_src are HOST arrays in both variants; the _dev ones take
+ * the ciphertexts in HBM, are asynchronous on the context stream and refuse a multi-device context.  spread may run
+ * in place (out == in). */
+/* host only, no device: the definition of spread over B TRLWELv1 (in == out is allowed) */
+int tfhe_lut_spread(const tfhe_params *params, const uint32_t *in /*B*2N*/, uint32_t w, uint32_t rot,
+                    uint32_t *out /*B*2N*/, size_t B);
+int tfhe_gpu_lut_spread_batch(tfhe_gpu_ctx *ctx, const uint32_t *in /*B*2N*/, uint32_t w, uint32_t rot,
+                              uint32_t *out /*B*2N*/, size_t B);
+int tfhe_gpu_lut_spread_dev(tfhe_gpu_ctx *ctx, const uint32_t *in_dev, uint32_t w, uint32_t rot, uint32_t *out_dev,
+                            size_t B);
+int tfhe_gpu_bootstrap_lut_each_batch(tfhe_gpu_ctx *ctx, const uint32_t *in /*B*(n+1)*/,
+                                      const uint32_t *testvecs /*B*2N*/, uint32_t *out /*B*(n+1)*/, size_t B);
+int tfhe_gpu_bootstrap_lut_each_dev(tfhe_gpu_ctx *ctx, const uint32_t *in_dev, const uint32_t *testvecs_dev,
+                                    uint32_t *out_dev, size_t B);
+int tfhe_gpu_lut_apply2_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                              uint32_t m, const uint32_t *pool, size_t P, const uint32_t *fn /*B*/,
+                              const uint32_t *x_src /*B*/, const uint32_t *y_src /*B*/, uint32_t *out /*B*(n+1)*/,
+                              size_t B);
+int tfhe_gpu_lut_apply2_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                            uint32_t m, const uint32_t *pool_dev, size_t P, const uint32_t *fn /*B*/,
+                            const uint32_t *x_src /*B*/, const uint32_t *y_src /*B*/, uint32_t *out_dev, size_t B);
 
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
 /* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,

@@ -14,6 +14,10 @@
 //                        tfhe::TrgswSet and tfhe::TableLookup (a table addressed by TRGSW-encrypted bits),
 //                        tfhe::PackingKey / tfhe::packTlwe (identityKeySwitching's arithmetic with TRLWE rows),
 //                        tfhe::packedScatterAdd / tfhe::packedWrite (writes into a tfhe::PackedTableLookup)
+//   lut/generator.zig -> tfhe::lutGenerate, tfhe::LutSet / tfhe::LutCircuit (per-item tables), tfhe::lutInterleave
+//                        (several tables from one blind rotation), tfhe::lutGenerate2 / tfhe::lutApply2 /
+//                        tfhe::lutSpread / tfhe::bootstrapLutEach (functions of two digits: a test vector
+//                        packed and spread on the device per item)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
 #pragma once
@@ -764,6 +768,65 @@ class LutSet {
     std::shared_ptr<tfhe_gpu_lut_set> set_;
     size_t size_ = 0;
 };
+
+// ---- Bivariate LUT bootstrap (include/tfhe_gpu.h): f(x, y) of two m-ary digits at the set's full m ----
+// The m level-1 tables of f given as f_table[x * m + y]: table i = lutGenerate of y -> f(i, y).  The tables of
+// F functions, one after the other, make the LutSet of lutApply2.
+inline std::vector<std::vector<Torus>> lutGenerate2(const tfhe_params &p, uint32_t m, const std::vector<uint32_t> &f_table) {
+    if (m == 0 || f_table.size() != (size_t)m * m) throw Error(TFHE_ERR_INVALID, "lutGenerate2: m * m values");
+    std::vector<std::vector<Torus>> tables;
+    for (uint32_t i = 0; i < m; i++)
+        tables.push_back(lutGenerate(p, std::vector<uint32_t>(f_table.begin() + (size_t)i * m, f_table.begin() + (size_t)(i + 1) * m)));
+    return tables;
+}
+
+// tfhe_gpu_lut_spread_batch: the window sum of width w on each half, times X^rot; w = N/m, rot = 2N - N/(2m)
+// turns values at the slots x * w into the generator's test vector.
+inline std::vector<TRLWELv1> lutSpread(const CloudKey &ck, const std::vector<TRLWELv1> &in, uint32_t w, uint32_t rot) {
+    const size_t B = in.size(), W = 2 * (size_t)ck.params().N;
+    std::vector<Torus> x(B * W), out(B * W);
+    for (size_t b = 0; b < B; b++) std::copy(in[b].p.begin(), in[b].p.end(), x.begin() + b * W);
+    check(tfhe_gpu_lut_spread_batch(ck.ctx(), x.data(), w, rot, out.data(), B), "lut_spread", ck.ctx());
+    std::vector<TRLWELv1> r(B);
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * W, out.begin() + (b + 1) * W, r[b].p.begin());
+    return r;
+}
+
+// tfhe_gpu_bootstrap_lut_each_batch: item i is bootstrapped with its own test vector testvecs[i] (any a).
+inline std::vector<TLWELv0> bootstrapLutEach(const CloudKey &ck, const std::vector<TLWELv0> &in,
+                                             const std::vector<TRLWELv1> &testvecs) {
+    const size_t B = in.size(), w = ck.params().n + 1, W = 2 * (size_t)ck.params().N;
+    if (testvecs.size() != B) throw Error(TFHE_ERR_INVALID, "bootstrapLutEach: one test vector per input");
+    std::vector<Torus> x(B * w), tv(B * W), out(B * w);
+    for (size_t b = 0; b < B; b++) {
+        std::copy(in[b].p.begin(), in[b].p.end(), x.begin() + b * w);
+        std::copy(testvecs[b].p.begin(), testvecs[b].p.end(), tv.begin() + b * W);
+    }
+    check(tfhe_gpu_bootstrap_lut_each_batch(ck.ctx(), x.data(), tv.data(), out.data(), B), "bootstrap_lut_each", ck.ctx());
+    std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
+    return r;
+}
+
+// tfhe_gpu_lut_apply2_batch: node b computes f_fn(pool[x_src], pool[y_src]) with the tables set[fn * m + i]
+// (lutGenerate2): m level-1 bootstraps of y, the pack, the spread, one bootstrap of x.
+struct Lut2Node {
+    uint32_t fn, x_src, y_src;
+};
+inline std::vector<TLWELv0> lutApply2(const CloudKey &ck, const LutSet &set, const PackingKey &key, uint32_t m,
+                                      const std::vector<TLWELv0> &pool, const std::vector<Lut2Node> &nodes) {
+    const size_t B = nodes.size(), w = ck.params().n + 1;
+    std::vector<Torus> x(pool.size() * w), out(B * w);
+    std::vector<uint32_t> fn, xs, ys;
+    for (size_t k = 0; k < pool.size(); k++) std::copy(pool[k].p.begin(), pool[k].p.end(), x.begin() + k * w);
+    for (const Lut2Node &nd : nodes) fn.push_back(nd.fn), xs.push_back(nd.x_src), ys.push_back(nd.y_src);
+    check(tfhe_gpu_lut_apply2_batch(ck.ctx(), set.get(), key.get(), m, x.data(), pool.size(), fn.data(), xs.data(), ys.data(),
+                                    out.data(), B),
+          "lut_apply2", ck.ctx());
+    std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
+    return r;
+}
 
 // Level-scheduled LUT circuit (tfhe_gpu_lut_circuit_eval): a node is an integer combination of earlier
 // wires (TLWELv0.add / addMul / subMul, tlwe.zig:120-240), then a programmable bootstrap with its own table.

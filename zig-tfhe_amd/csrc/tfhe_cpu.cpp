@@ -705,6 +705,32 @@ int tfhe_lut_interleave(const tfhe_params *p, const uint32_t *testvecs, uint32_t
     return TFHE_OK;
 }
 
+// spread of the bivariate LUT bootstrap (include/tfhe_gpu.h), term by term as it is defined: on each
+// half, S = sum_{j<w} polyMulWithXK(in, j) (trgsw.zig:442-466), then out = polyMulWithXK(S, rot).
+int tfhe_lut_spread(const tfhe_params *p, const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B) {
+    std::string why;
+    if (!p || !params_ok(p, why) || w == 0 || w > p->N || rot > 2 * p->N || (B && (!in || !out))) return TFHE_ERR_INVALID;
+    const size_t N = p->N;
+    std::vector<uint32_t> S(N);
+    for (size_t h = 0; h < 2 * B; h++) {
+        const uint32_t *x = in + h * N;
+        uint32_t *y = out + h * N;
+        for (size_t i = 0; i < N; i++) {
+            uint32_t acc = 0;
+            for (size_t j = 0; j < w; j++) acc += j <= i ? x[i - j] : 0u - x[N + i - j];
+            S[i] = acc;
+        }
+        if (rot < N) {
+            for (size_t i = 0; i < N - rot; i++) y[i + rot] = S[i];
+            for (size_t i = N - rot; i < N; i++) y[i + rot - N] = 0u - S[i];
+        } else {
+            for (size_t i = 0; i < 2 * N - rot; i++) y[i + rot - N] = 0u - S[i];
+            for (size_t i = 2 * N - rot; i < N; i++) y[i - (2 * N - rot)] = S[i];
+        }
+    }
+    return TFHE_OK;
+}
+
 // ---- host-side TLWELv0 helpers ------------------------------------------
 int tfhe_encrypt_bool_batch(const tfhe_params *p, const uint32_t *key, const uint8_t *bits, uint64_t seed0,
                             uint32_t *out, size_t B) {

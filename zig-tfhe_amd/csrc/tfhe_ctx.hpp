@@ -216,6 +216,15 @@ struct tfhe_gpu_ctx {
     int64_t level_issue_us = 0;      // host time the last level-split circuit spent issuing (TFHE_OPT_LEVEL_ISSUE_US)
 };
 
+// A packing key resident on one device: the MFMA layout of its rows only (pack_gemm_bytes).  Loaded and
+// run by tfhe_pack.cpp; the bivariate LUT bootstrap (tfhe_lut.cpp) packs with it too.
+struct tfhe_gpu_packing_key {
+    const tfhe_gpu_ctx *ctx = nullptr;  // the context that loaded it (identity only, never dereferenced)
+    tfhe_params P{};
+    uint32_t basebit = 0, t = 0;
+    tfhe::DevPtr<uint32_t> key_gemm;
+};
+
 namespace tfhe {
 
 inline int fail(tfhe_gpu_ctx *c, int code, const std::string &msg) {
@@ -353,6 +362,14 @@ struct Io {
         return host_out ? d2h_sync(d, host_out, staged_out, out_bytes) : sync_check(d);
     }
 };
+
+// ---- tfhe_pack.cpp, for tfhe_lut.cpp --------------------------------------------
+// Items per chunk of a pack of `items` inputs: what keeps the GEMM sums within TFHE_OPT_PACK_SCRATCH_MB.
+size_t pack_chunk_items(const Device &d, size_t items, int basebit);
+// The pack's launches over device buffers, async: x = B * C TLWELv0 with 2 * KS_GEMM_INPUT_SLACK readable
+// bytes past the last, coef = C device words, out = B TRLWELv1; chunked by pack_chunk_items.
+int pack_launch(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *x, const uint32_t *coef_dev, size_t C,
+                uint32_t *out, size_t B);
 
 // ---- tfhe_multi.cpp, for tfhe_gpu.cpp ------------------------------------------
 int enable_peer_access(const std::vector<int> &devs, std::string &why);

@@ -308,5 +308,9 @@ hipError_t launch_lut_combine_round(const KParams &P, const uint32_t *pool, cons
 // (node < the level's nodes, coefficient < N).
 hipError_t launch_lut_fanout_extract(const uint32_t *acc, const uint32_t *fan, uint32_t *out_lv1, size_t M,
                                      hipStream_t s, const char **used = nullptr);
+// spread of the bivariate LUT bootstrap (k_lut_spread) over B TRLWELv1 of 2N words: the window sum of width
+// w (1 <= w <= N) on each half, rotated by X^rot (rot <= 2N); N = 1024; out may be in.
+hipError_t launch_lut_spread(const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B, hipStream_t s,
+                             const char **used = nullptr);
 
 }  // namespace tfhe

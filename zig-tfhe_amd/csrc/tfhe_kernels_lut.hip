@@ -2,7 +2,8 @@
 // a small integer combination of TLWELv0 ciphertexts (TLWELv0.add / neg /
 // addMul / subMul, tlwe.zig:120-240) in front of the programmable bootstrap,
 // and the two ends of a multi-output node: the rounding of the combined words
-// and the fan-out extraction of its accumulator's first coefficients.
+// and the fan-out extraction of its accumulator's first coefficients; and the
+// spread of the bivariate bootstrap: coefficient slots -> a test vector.
 // Its own unit, like tfhe_kernels_leveled.hip: the bootstrap kernels' objects
 // (tfhe_kernels.o, tfhe_kernels_whole.o), which tfhe_gpu_build_id() hashes, do
 // not change with it.  Integer arithmetic only.
@@ -77,6 +78,58 @@ __global__ __launch_bounds__(LUT_FANOUT_THREADS) void k_lut_fanout_extract(const
         p[i] = i <= k ? v : 0u - v;
     }
     if (threadIdx.x == 0) p[1024] = x[1024 + k];
+}
+
+// spread of the bivariate LUT bootstrap (include/tfhe_gpu.h) on one half (N = 1024 words) per workgroup:
+//   S[i] = sum_{j<w} +-x[(i - j) mod N], negated where i - j wraps (the sum of polyMulWithXK(x, j)), and
+//   y = polyMulWithXK(S, rot)  (trgsw.zig:442-466).
+// With the inclusive prefix sums E of x and T = E[N-1], in wrapping u32 (so the differences are exact),
+//   S[i] = E[i] - E[i - w] for i >= w, and E[i] - (T - E[N + i - w]) for i < w
+// (the second form at i = w - 1 is E[i]): two LDS reads per output whatever w is.  The half is staged in LDS
+// by 4-byte loads (a caller's TRLWE need not be 16-byte aligned); thread t then owns words 4t .. 4t+3: its
+// own running sums, a shuffle scan of the 64 lane totals, the 4 wave totals through LDS, and E back over
+// the same words (each thread overwrites only what it alone read).  Output word o reads S at
+// (o - rot) mod N, negated when the rotation wraps an odd number of times, so a wave stores 64 consecutive
+// words and reads 64 consecutive (mod N) LDS words twice.  Every read of x comes before the barrier in front
+// of the stores: out may be in.  1 <= w <= N and rot <= 2N are the host's checks; N + i - w stays in [i, N).
+constexpr int LUT_SPREAD_THREADS = 256;
+__global__ __launch_bounds__(LUT_SPREAD_THREADS) void k_lut_spread(const uint32_t *in, uint32_t *out,
+                                                                   uint32_t w, uint32_t rot) {
+    __shared__ __attribute__((aligned(16))) uint32_t E[1024];
+    __shared__ uint32_t wave_total[LUT_SPREAD_THREADS / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t *x = in + (size_t)blockIdx.x * 1024;
+    uint32_t *y = out + (size_t)blockIdx.x * 1024;
+    for (uint32_t i = t; i < 1024; i += LUT_SPREAD_THREADS) E[i] = x[i];
+    __syncthreads();
+    uint4 v = reinterpret_cast<const uint4 *>(E)[t];
+    v.y += v.x, v.z += v.y, v.w += v.z;
+    uint32_t inc = v.w;  // inclusive scan of the lanes' totals
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(inc, d);
+        if (lane >= (uint32_t)d) inc += up;
+    }
+    if (lane == 63) wave_total[wave] = inc;
+    __syncthreads();
+    uint32_t base = inc - v.w;
+    for (uint32_t k = 0; k < wave; k++) base += wave_total[k];
+    v.x += base, v.y += base, v.z += base, v.w += base;
+    reinterpret_cast<uint4 *>(E)[t] = v;
+    __syncthreads();
+    const uint32_t T = E[1023];
+    for (uint32_t o = t; o < 1024; o += LUT_SPREAD_THREADS) {
+        const uint32_t q = o + 2048u - rot, i = q & 1023u;  // q in [0, 3N): wraps = 2 - q / N
+        const uint32_t s = i >= w ? E[i] - E[i - w] : E[i] - (T - E[1024 + i - w]);
+        y[o] = (q >> 10) & 1u ? 0u - s : s;
+    }
+}
+
+hipError_t launch_lut_spread(const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B, hipStream_t s,
+                             const char **used) {
+    if (B == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_lut_spread, dim3((unsigned)(2 * B)), dim3(LUT_SPREAD_THREADS), 0, s, in, out, w, rot);
+    if (used) *used = "k_lut_spread";
+    return hipGetLastError();
 }
 
 hipError_t launch_lut_combine(const KParams &P, const uint32_t *pool, const uint32_t *off, const uint32_t *src,

@@ -5,8 +5,10 @@
 // is run_bootstrap_dev with a per-item table selector (KParams::tv_sel), and the
 // planner is in tfhe_cpu.cpp.  A multi-output node (theta > 0) rounds x in the
 // combine kernel, keeps the accumulator (RUN_TRLWE) and extracts its first 2^theta
-// coefficients in front of one key switch over the outputs.  Everything here runs on
-// the context's first device.
+// coefficients in front of one key switch over the outputs.  The bivariate node
+// (lut_apply2_on) chains level 1, the pack (pack_launch, tfhe_pack.cpp), the spread
+// (k_lut_spread) and a bootstrap whose per-item selector is the identity over the
+// chunk's own test vectors.  Everything here runs on the context's first device.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -231,9 +233,155 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
     return rc;
 }
 
+// ---- Bivariate LUT bootstrap (include/tfhe_gpu.h): spread, a test vector per item, the fused node ----
+
+static int spread_entry(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B, bool dev) {
+    if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (w == 0 || w > c->P.N || rot > 2 * c->P.N) return fail(c, TFHE_ERR_INVALID, "spread: w outside 1..N or rot > 2N");
+    if (B > 0x7FFFFFFFull) return fail(c, TFHE_ERR_INVALID, "spread: too many items");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        const size_t bytes = B * 2 * (size_t)d.P.N * sizeof(uint32_t);
+        Io io{d, dev};
+        int rc = io.in(d.s_tv, in, bytes);
+        if (!rc) rc = io.out(out, bytes);
+        if (rc) return rc;
+        d.last_br = d.last_ks = "";
+        HIPCHK(d, launch_lut_spread(in, w, rot, out, B, d.stream, &d.last_br));
+        return io.finish();
+    });
+}
+
+// The selector of a bootstrap whose item g reads testvecs + g * 2N: 0 .. B-1, appended to a call's descriptors.
+static size_t add_iota(DescBlob &blob, size_t B) {
+    const size_t at = blob.words.size();
+    for (size_t i = 0; i < B; i++) blob.words.push_back((uint32_t)i);
+    return at;
+}
+
+static int each_entry(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvecs, uint32_t *out, size_t B, bool dev) {
+    if (!c || (B && (!in || !testvecs || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (B > 0xFFFFFFFFull / 2048) return fail(c, TFHE_ERR_INVALID, "bootstrap_lut_each: too many items");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+        const size_t w = tlwe0_words(d.P);
+        DescBlob blob;
+        add_iota(blob, B);
+        Io io{d, dev};
+        int rc = h2d(d, d.s_cidx, blob.words.data(), B * sizeof(uint32_t));
+        if (!rc) rc = io.in(d.s_a, in, B * w * 4);
+        if (!rc) rc = io.in(d.s_tv, testvecs, B * 2 * (size_t)d.P.N * sizeof(uint32_t));
+        if (!rc) rc = io.out(out, B * w * 4);
+        if (rc) return rc;
+        rc = run_bootstrap_dev(d, nullptr, in, nullptr, testvecs, out, B, RUN_BOOTSTRAP, nullptr,
+                               d.s_cidx.as<const uint32_t>());
+        return rc ? rc : io.finish();
+    });
+}
+
+// B bivariate nodes (checked arguments): per chunk of nodes, level 1 (m one-term nodes each, table fn*m + i),
+// the pack into slots i*w, the spread in place, and level 2 with the chunk's test vectors.  The chunk is the
+// pack's own (pack_chunk_items) in whole nodes, so the intermediates (m TLWELv0 in and out of level 1 per node,
+// less than the sums of m items) stay within the same bound; every step is per item, so chunking changes no word.
+static int lut_apply2_on(Device &d, const tfhe_gpu_lut_set &set, const tfhe_gpu_packing_key &pk, uint32_t m,
+                         const uint32_t *pool, size_t P, const uint32_t *fn, const uint32_t *x_src, const uint32_t *y_src,
+                         uint32_t *out, size_t B, bool dev) {
+    if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), N = d.P.N, items = B * m;
+    const uint32_t slot = (uint32_t)(N / m), rot = (uint32_t)(2 * N - N / (2 * m));
+    const size_t nodes = std::min(B, std::max<size_t>(1, pack_chunk_items(d, items, (int)pk.basebit) / m));
+    // descriptors: level 1 has one term per item (term k of item k: pool[y_src[b]], coefficient 1), level 2
+    // one per node; ones / zeros / iota serve both (level 1 is the longer)
+    std::vector<uint32_t> src1(items), lut1(items), ones(items, 1u), zeros(items, 0u), coef(m);
+    for (size_t b = 0; b < B; b++)
+        for (uint32_t i = 0; i < m; i++) src1[b * m + i] = y_src[b], lut1[b * m + i] = fn[b] * m + i;
+    for (uint32_t i = 0; i < m; i++) coef[i] = i * slot;
+    DescBlob blob;
+    const size_t iota_at = add_iota(blob, items + 1), src1_at = blob.add(src1.data(), items),
+                 lut1_at = blob.add(lut1.data(), items), ones_at = blob.add(ones.data(), items),
+                 zeros_at = blob.add(zeros.data(), items), src2_at = blob.add(x_src, B), coef_at = blob.add(coef.data(), m);
+    Io io{d, dev};
+    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
+    if (!rc) rc = io.in(d.s_a, pool, P * w * 4);
+    if (!rc) rc = io.out(out, B * w * 4);
+    if (!rc) rc = ensure(d, d.s_lut_x, nodes * m * w * 4);
+    if (!rc) rc = ensure(d, d.s_b, nodes * m * w * 4 + 2 * KS_GEMM_INPUT_SLACK);  // the pack's inputs: its GEMM's slack
+    if (!rc) rc = ensure(d, d.s_lut_acc, nodes * 2 * N * sizeof(uint32_t));
+    if (rc) return rc;
+    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
+    const uint32_t *iota = desc + iota_at, *zeros_d = desc + zeros_at;
+    const int32_t *ones_d = reinterpret_cast<const int32_t *>(desc + ones_at);
+    uint32_t *x = d.s_lut_x.as<uint32_t>(), *g = d.s_b.as<uint32_t>(), *tv = d.s_lut_acc.as<uint32_t>();
+    for (size_t b0 = 0; b0 < B; b0 += nodes) {
+        const size_t nb = std::min(nodes, B - b0), ni = nb * m;
+        // term_off = iota from 0 with src advanced to the chunk: item k of the chunk has the one term k
+        HIPCHK(d, launch_lut_combine(d.K, pool, iota, desc + src1_at + b0 * m, ones_d, zeros_d, x, ni, d.stream));
+        if ((rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, g, ni, RUN_BOOTSTRAP, nullptr,
+                                    desc + lut1_at + b0 * m)))
+            return rc;
+        if ((rc = pack_launch(d, pk, g, desc + coef_at, m, tv, nb))) return rc;
+        HIPCHK(d, launch_lut_spread(tv, slot, rot, tv, nb, d.stream));
+        HIPCHK(d, launch_lut_combine(d.K, pool, iota, desc + src2_at + b0, ones_d, zeros_d, x, nb, d.stream));
+        if ((rc = run_bootstrap_dev(d, nullptr, x, nullptr, tv, out + b0 * w, nb, RUN_BOOTSTRAP, nullptr, iota))) return rc;
+    }
+    return io.finish();
+}
+
+static int apply2_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk, uint32_t m,
+                        const uint32_t *pool, size_t P, const uint32_t *fn, const uint32_t *x_src, const uint32_t *y_src,
+                        uint32_t *out, size_t B, bool dev) {
+    if (!c || !set || !pk || (B && (!pool || !fn || !x_src || !y_src || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
+    if (const int rc = set_mismatch(c, pk, "packing key")) return rc;
+    if (m < 2 || (m & (m - 1)) || 2 * (uint64_t)m > c->P.N)
+        return fail(c, TFHE_ERR_INVALID, "lut_apply2: m must be a power of two with 2 <= m and 2m <= N");
+    if (set->T % m) return fail(c, TFHE_ERR_INVALID, "lut_apply2: the set's size is not a multiple of m");
+    if (B == 0) return TFHE_OK;
+    if (B > 0xFFFFFFFFull / m - 1 || P > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "lut_apply2: too many nodes or ciphertexts");
+    for (size_t b = 0; b < B; b++) {
+        if (fn[b] >= set->T / m) return fail(c, TFHE_ERR_INVALID, "lut_apply2: fn * m + m exceeds the set");
+        if (x_src[b] >= P || y_src[b] >= P) return fail(c, TFHE_ERR_INVALID, "lut_apply2: a source is not in the pool");
+    }
+    return on_device0(c, [&](Device &d) { return lut_apply2_on(d, *set, *pk, m, pool, P, fn, x_src, y_src, out, B, dev); });
+}
+
 }  // namespace tfhe
 
 extern "C" {
+
+int tfhe_gpu_lut_spread_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B) {
+    return spread_entry(c, in, w, rot, out, B, false);
+}
+
+int tfhe_gpu_lut_spread_dev(tfhe_gpu_ctx *c, const uint32_t *in_dev, uint32_t w, uint32_t rot, uint32_t *out_dev, size_t B) {
+    return spread_entry(c, in_dev, w, rot, out_dev, B, true);
+}
+
+int tfhe_gpu_bootstrap_lut_each_batch(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvecs, uint32_t *out,
+                                      size_t B) {
+    return each_entry(c, in, testvecs, out, B, false);
+}
+
+int tfhe_gpu_bootstrap_lut_each_dev(tfhe_gpu_ctx *c, const uint32_t *in_dev, const uint32_t *testvecs_dev,
+                                    uint32_t *out_dev, size_t B) {
+    return each_entry(c, in_dev, testvecs_dev, out_dev, B, true);
+}
+
+int tfhe_gpu_lut_apply2_batch(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk, uint32_t m,
+                              const uint32_t *pool, size_t P, const uint32_t *fn, const uint32_t *x_src,
+                              const uint32_t *y_src, uint32_t *out, size_t B) {
+    return apply2_entry(c, set, pk, m, pool, P, fn, x_src, y_src, out, B, false);
+}
+
+int tfhe_gpu_lut_apply2_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk, uint32_t m,
+                            const uint32_t *pool_dev, size_t P, const uint32_t *fn, const uint32_t *x_src,
+                            const uint32_t *y_src, uint32_t *out_dev, size_t B) {
+    return apply2_entry(c, set, pk, m, pool_dev, P, fn, x_src, y_src, out_dev, B, true);
+}
 
 int tfhe_gpu_lut_set_load(tfhe_gpu_ctx *c, const uint32_t *testvecs, size_t T, tfhe_gpu_lut_set **out) {
     if (out) *out = nullptr;

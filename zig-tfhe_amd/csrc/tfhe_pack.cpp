@@ -13,25 +13,39 @@
 
 using namespace tfhe;
 
-// A packing key resident on one device: the MFMA layout of its rows only (pack_gemm_bytes).
-struct tfhe_gpu_packing_key {
-    const tfhe_gpu_ctx *ctx = nullptr;  // the context that loaded it (identity only, never dereferenced)
-    tfhe_params P{};
-    uint32_t basebit = 0, t = 0;
-    DevPtr<uint32_t> key_gemm;
-};
-
 namespace tfhe {
 
 // Items per chunk: as many as keep the K splits' sums (pack_gemm_part_bytes; fewer items take
 // more splits, at most 4 of 2N words each) within the scratch bound, and at least one.  Every
 // chunk of the call, a shorter last one included, runs with this chunk size's split count
 // (launch_pack_gemm), so none needs more scratch than the first.
-static size_t pack_chunk_items(const Device &d, size_t items, int basebit) {
+size_t pack_chunk_items(const Device &d, size_t items, int basebit) {
     const size_t cap = (size_t)d.pack_scratch_mb << 20;
     size_t chunk = std::min(items, std::max<size_t>(1, cap / (2 * d.P.N * sizeof(uint32_t))));
     while (chunk > 1 && pack_gemm_part_bytes(d.K, chunk, basebit) > cap) chunk = (chunk + 1) / 2;
     return chunk;
+}
+
+// The launches of a pack over device buffers (tfhe_ctx.hpp): per chunk the GEMM, then the epilogue.
+int pack_launch(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *x0, const uint32_t *coef_dev, size_t C,
+                uint32_t *out, size_t B) {
+    const size_t items = B * C, w = tlwe0_words(d.P);
+    const int basebit = (int)key.basebit, t = (int)key.t;
+    const size_t chunk = pack_chunk_items(d, items, basebit);
+    if (const int rc = ensure(d, d.s_kspart, pack_gemm_part_bytes(d.K, chunk, basebit))) return rc;
+    KsGemm G;
+    G.kg = key.key_gemm;
+    G.part = d.s_kspart.as<uint32_t>();
+    d.last_br = d.last_ks = "";
+    for (size_t item0 = 0; item0 < items; item0 += chunk) {
+        const size_t M = std::min(chunk, items - item0);
+        const uint32_t *x = x0 + item0 * w;
+        PackSums sums;
+        // last_kernels: the GEMM instantiation, then the epilogue
+        HIPCHK(d, launch_pack_gemm(d.K, t, basebit, x, G, M, chunk, d.stream, &d.last_br, &sums));
+        HIPCHK(d, launch_pack_rotate_acc(x, (int)d.P.n, G.part, sums, coef_dev, C, item0, M, out, d.stream, &d.last_ks));
+    }
+    return TFHE_OK;
 }
 
 // in: B * C TLWELv0, out: B TRLWELv1; host (dev = false: staged, synchronous) or device.  The
@@ -39,8 +53,7 @@ static size_t pack_chunk_items(const Device &d, size_t items, int basebit) {
 // whole-block reads need past the last row.
 static int pack_on(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *in, const uint32_t *coef, size_t C,
                    uint32_t *out, size_t B, bool dev) {
-    const size_t items = B * C, w = tlwe0_words(d.P), in_bytes = items * w * sizeof(uint32_t);
-    const int basebit = (int)key.basebit, t = (int)key.t;
+    const size_t in_bytes = B * C * tlwe0_words(d.P) * sizeof(uint32_t);
     Io io{d, dev};
     // the last block of 8 coefficients may reach 6 words past the last row's n + 1 (n = 8q + 1)
     int rc = ensure(d, d.s_a, in_bytes + 2 * KS_GEMM_INPUT_SLACK);
@@ -49,22 +62,8 @@ static int pack_on(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *i
     if (rc) return rc;
     if (dev) HIPCHK(d, hipMemcpyAsync(d.s_a.p, in, in_bytes, hipMemcpyDeviceToDevice, d.stream));
     else if ((rc = h2d(d, d.s_a, in, in_bytes))) return rc;
-    const size_t chunk = pack_chunk_items(d, items, basebit);
-    if ((rc = ensure(d, d.s_kspart, pack_gemm_part_bytes(d.K, chunk, basebit)))) return rc;
-    KsGemm G;
-    G.kg = key.key_gemm;
-    G.part = d.s_kspart.as<uint32_t>();
-    d.last_br = d.last_ks = "";
-    for (size_t item0 = 0; item0 < items; item0 += chunk) {
-        const size_t M = std::min(chunk, items - item0);
-        const uint32_t *x = d.s_a.as<const uint32_t>() + item0 * w;
-        PackSums sums;
-        // last_kernels: the GEMM instantiation, then the epilogue
-        HIPCHK(d, launch_pack_gemm(d.K, t, basebit, x, G, M, chunk, d.stream, &d.last_br, &sums));
-        HIPCHK(d, launch_pack_rotate_acc(x, (int)d.P.n, G.part, sums, d.s_cidx.as<const uint32_t>(), C, item0, M, out,
-                                         d.stream, &d.last_ks));
-    }
-    return io.finish();
+    rc = pack_launch(d, key, d.s_a.as<const uint32_t>(), d.s_cidx.as<const uint32_t>(), C, out, B);
+    return rc ? rc : io.finish();
 }
 
 }  // namespace tfhe

@@ -239,6 +239,14 @@ _SIGS = {
                                                       u32p, u32p, C.c_size_t, u32p, vp, C.POINTER(C.c_uint32)]),
     "tfhe_lut_circuit_schedule_multi": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, u32p,
                                                   C.POINTER(C.c_uint32)]),
+    "tfhe_lut_spread": (C.c_int, [C.POINTER(TfheParams), u32p, C.c_uint32, C.c_uint32, u32p, C.c_size_t]),
+    "tfhe_gpu_lut_spread_batch": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, u32p, C.c_size_t]),
+    "tfhe_gpu_lut_spread_dev": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t]),
+    "tfhe_gpu_bootstrap_lut_each_batch": (C.c_int, [vp, u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_bootstrap_lut_each_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
+    "tfhe_gpu_lut_apply2_batch": (C.c_int, [vp, vp, vp, C.c_uint32, u32p, C.c_size_t, u32p, u32p, u32p, u32p,
+                                            C.c_size_t]),
+    "tfhe_gpu_lut_apply2_dev": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_size_t, u32p, u32p, u32p, vp, C.c_size_t]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -872,6 +880,58 @@ class Context:
         self.check(self.lib.tfhe_gpu_lut_apply_multi_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), thp,
                                                          vp(out_ptr), d.B), "lut_apply_multi_dev")
 
+    # ---- bivariate LUT bootstrap: spread, a test vector per item, the fused node ----
+    def lut_spread(self, trlwes, w: int, rot: int):
+        """tfhe_gpu_lut_spread_batch: (B, 2N) TRLWELv1 -> (B, 2N): on each half the negacyclic window sum of width w,
+        multiplied by X^rot (lut_spread_host is the definition).  w = N/m, rot = 2N - N/(2m) turns slots x*w into the
+        generator's test vector."""
+        x, xp = _u32(np.asarray(trlwes, np.uint32).reshape(-1, 2 * self.params.N))
+        out = np.zeros_like(x)
+        self.check(self.lib.tfhe_gpu_lut_spread_batch(self.h, xp, w, rot, out.ctypes.data_as(u32p), x.shape[0]),
+                   "lut_spread")
+        return out
+
+    def lut_spread_dev(self, in_ptr, w: int, rot: int, out_ptr, B):
+        """tfhe_gpu_lut_spread_dev: the B TRLWELv1 in HBM (out_ptr may be in_ptr), async on the context stream."""
+        self.check(self.lib.tfhe_gpu_lut_spread_dev(self.h, vp(in_ptr), w, rot, vp(out_ptr), B), "lut_spread_dev")
+
+    def bootstrap_lut_each(self, cts, testvecs):
+        """tfhe_gpu_bootstrap_lut_each_batch: bootstrap_lut_batch with one test vector per item: cts (B, n+1),
+        testvecs (B, 2N) TRLWELv1 (any a) -> (B, n+1)."""
+        cts, cp = _u32(np.asarray(cts, np.uint32).reshape(-1, self.n1))
+        tv, tvp = _u32(np.asarray(testvecs, np.uint32).reshape(-1, 2 * self.params.N))
+        if tv.shape[0] != cts.shape[0]:
+            raise ValueError(f"bootstrap_lut_each: {cts.shape[0]} ciphertexts need as many test vectors, got {tv.shape[0]}")
+        out = np.zeros_like(cts)
+        self.check(self.lib.tfhe_gpu_bootstrap_lut_each_batch(self.h, cp, tvp, out.ctypes.data_as(u32p), cts.shape[0]),
+                   "bootstrap_lut_each")
+        return out
+
+    def bootstrap_lut_each_dev(self, in_ptr, tv_ptr, out_ptr, B):
+        """tfhe_gpu_bootstrap_lut_each_dev: inputs, the B test vectors and outputs in HBM, async."""
+        self.check(self.lib.tfhe_gpu_bootstrap_lut_each_dev(self.h, vp(in_ptr), vp(tv_ptr), vp(out_ptr), B),
+                   "bootstrap_lut_each_dev")
+
+    def lut_apply2(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, pool, nodes):
+        """tfhe_gpu_lut_apply2_batch: node b = (fn, x_src, y_src) computes f_fn(pool[x_src], pool[y_src]) for two
+        m-ary digits, lut_set = lut_generate2 tables of F functions ((F * m, 2N)): m level-1 bootstraps of y, the
+        pack, the spread, one bootstrap of x with the packed test vector.  pool (P, n+1) -> (B, n+1)."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        fn, xs, ys = _apply2_nodes(nodes)
+        out = np.zeros((fn.size, self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_apply2_batch(self.h, lut_set.h, packing_key.h, m, pp, pool.shape[0],
+                                                      fn.ctypes.data_as(u32p), xs.ctypes.data_as(u32p),
+                                                      ys.ctypes.data_as(u32p), out.ctypes.data_as(u32p), fn.size),
+                   "lut_apply2")
+        return out
+
+    def lut_apply2_dev(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, pool_ptr, P, nodes, out_ptr):
+        """tfhe_gpu_lut_apply2_dev: the pool and the B outputs in HBM (the nodes stay a host description), async."""
+        fn, xs, ys = _apply2_nodes(nodes)
+        self.check(self.lib.tfhe_gpu_lut_apply2_dev(self.h, lut_set.h, packing_key.h, m, vp(pool_ptr), P,
+                                                    fn.ctypes.data_as(u32p), xs.ctypes.data_as(u32p),
+                                                    ys.ctypes.data_as(u32p), vp(out_ptr), fn.size), "lut_apply2_dev")
+
     def lut_circuit_eval_multi(self, lut_set: "LutSet", inputs, nodes, theta, out_wires):
         """tfhe_gpu_lut_circuit_eval_multi: node g drives 2^theta[g] consecutive wires -> (outputs, depth)."""
         inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
@@ -1197,6 +1257,28 @@ def lut_interleave(params: TfheParams, tables) -> np.ndarray:
     return out
 
 
+def lut_spread_host(params: TfheParams, trlwes, w: int, rot: int) -> np.ndarray:
+    """tfhe_lut_spread (host only): the definition Context.lut_spread computes on the device, word for word."""
+    x, xp = _u32(np.asarray(trlwes, np.uint32).reshape(-1, 2 * params.N))
+    out = np.zeros_like(x)
+    rc = load_library().tfhe_lut_spread(C.byref(params), xp, w, rot, out.ctypes.data_as(u32p), x.shape[0])
+    if rc:
+        raise TfheError(f"lut_spread_host: {rc}", rc)
+    return out
+
+
+def _apply2_nodes(nodes):
+    """nodes of Context.lut_apply2: (fn, x_src, y_src) arrays, or a sequence of such triples -> three u32 arrays."""
+    if isinstance(nodes, tuple) and len(nodes) == 3 and all(np.ndim(a) == 1 for a in nodes):
+        cols = [np.ascontiguousarray(a, np.uint32) for a in nodes]
+    else:
+        t = np.asarray(list(nodes), np.uint32).reshape(-1, 3)
+        cols = [np.ascontiguousarray(t[:, j]) for j in range(3)]
+    if not (cols[0].size == cols[1].size == cols[2].size):
+        raise ValueError("lut_apply2: fn, x_src and y_src need one entry per node each")
+    return cols
+
+
 class LutSet:
     """T test vectors ((T, 2N) u32 TRLWELv1, e.g. lut_generate's) resident in HBM (tfhe_gpu_lut_set): the
     tables of Context.lut_apply and LutCircuit, addressed by index."""
@@ -1430,6 +1512,12 @@ def lut_generate(params: TfheParams, m: int, f) -> np.ndarray:
     if rc:
         raise TfheError(f"lut_generate: {rc}")
     return tv
+
+
+def lut_generate2(params: TfheParams, m: int, f) -> np.ndarray:
+    """The m level-1 tables of a bivariate f(x, y) for Context.lut_apply2: row i = lut_generate of y -> f(i, y),
+    (m, 2N) u32.  The tables of F functions stacked ((F * m, 2N)) make the call's LutSet."""
+    return np.stack([lut_generate(params, m, lambda y, i=i: f(i, y)) for i in range(m)])
 
 
 class Encoder:
