@@ -420,7 +420,10 @@ DEV void ex2_read(C2 *d, const C2 *xb, int t) {
 // overwrites, and one wave's LDS operations execute in order.
 // hipcc's one s_waitcnt per consumed LDS read lets each butterfly start as soon
 // as its own operand lands; one explicit wait per read group measured slower
-// (6.10-6.11 vs 6.07 ms, profiles/r04_ab_x2_waits.txt).  Exchange 2 in
+// (6.10-6.11 vs 6.07 ms, profiles/r04_ab_x2_waits.txt).  T.pass_b issued before
+// ex1_write(d[1]), so that pass B's first butterfly does not wait for that store
+// burst, measured slower as well (5.98-6.08 vs 5.95 ms,
+// profiles/ab_lds_read_groups.txt).  Exchange 2 in
 // registers here measured slower too (7.75 vs 7.52 ms, profiles/r02_ab_exchange2.txt).
 template <bool INV, bool ONEBUF = false, bool FU = false, class TW>
 DEV void fft512_x2(C2 (*d)[8], C2 *xb, const TW &T, int t) {
@@ -962,17 +965,36 @@ DEV void load_digits_pair0_regs(C2 (*d)[8], const uint32_t *tA, const uint32_t *
 // fields: one v_bfe_i32 per digit as before, and no tmp round trip through LDS
 // (32 ds_write_b32 + 48 ds_read_b32 per step fewer; 6.25-6.32 -> 6.12-6.18 ms,
 // profiles/r04_ab_tmp_regs.txt).
+// tw[q] = twist factor of coefficient t + 64 br3(q), read by the caller as one
+// group (read_twist8) ahead of this call: hipcc otherwise reads them two at a
+// time, each pair four instructions before its first use (four exposed LDS
+// latencies per row pair).  The 64 digit extractions and conversions, which need
+// no factor, issue first and cover the reads; the empty asm pins the converted
+// values there (a scheduling fence alone does not: instruction selection places
+// pure arithmetic at its use).  Same operations and operands in every f64
+// instruction; 5.98 -> 5.86 ms per 1,024 gates (profiles/ab_lds_read_groups.txt).
+DEV void read_twist8(C2 *tw, const C2 *twist_t) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) tw[q] = twist_t[64 * br3(q)];
+}
 template <bool FU>
-DEV void load_digits_pair_tbx(C2 (*d)[8], const uint32_t *tbx, int rp, int bgbit, const C2 *twist_t) {
+DEV void load_digits_pair_tbx(C2 (*d)[8], const uint32_t *tbx, int rp, int bgbit, const C2 *tw) {
     const int off0 = rp == 1 ? 0 : 32 - 2 * bgbit, off1 = rp == 1 ? 32 - bgbit : 32 - 3 * bgbit;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         const int m = br3(q);
-        const C2 w = twist_t[64 * m];
-        d[0][q] = twist_in<FU>((double)(int32_t)__builtin_amdgcn_sbfe(tbx[m], off0, bgbit),
-                               (double)(int32_t)__builtin_amdgcn_sbfe(tbx[m + 8], off0, bgbit), w);
-        d[1][q] = twist_in<FU>((double)(int32_t)__builtin_amdgcn_sbfe(tbx[m], off1, bgbit),
-                               (double)(int32_t)__builtin_amdgcn_sbfe(tbx[m + 8], off1, bgbit), w);
+        d[0][q] = c2((double)(int32_t)__builtin_amdgcn_sbfe(tbx[m], off0, bgbit),
+                     (double)(int32_t)__builtin_amdgcn_sbfe(tbx[m + 8], off0, bgbit));
+        d[1][q] = c2((double)(int32_t)__builtin_amdgcn_sbfe(tbx[m], off1, bgbit),
+                     (double)(int32_t)__builtin_amdgcn_sbfe(tbx[m + 8], off1, bgbit));
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) asm volatile("" : "+v"(d[0][q].x), "+v"(d[0][q].y), "+v"(d[1][q].x), "+v"(d[1][q].y));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        d[0][q] = twist_in<FU>(d[0][q].x, d[0][q].y, tw[q]);
+        d[1][q] = twist_in<FU>(d[1][q].x, d[1][q].y, tw[q]);
     }
 }
 
@@ -1058,9 +1080,12 @@ DEV void br_pairs(const uint32_t *s_tmp, int bgbit, const LdsTw &T, const C2 *tw
         pp.mark(1);
         if (L > 1 && rp == 0)  // UINT4 (L = 1): 1.4 % slower, LDS kept
             load_digits_pair0_regs<FU>(d, tA, tB, L, bgbit, tw0);
-        else if (L == 3)
-            load_digits_pair_tbx<FU>(d, tbx, rp, bgbit, twist_t);
-        else
+        else if (L == 3) {
+            C2 tw[8];
+            read_twist8(tw, twist_t);
+            __builtin_amdgcn_sched_barrier(0);
+            load_digits_pair_tbx<FU>(d, tbx, rp, bgbit, tw);
+        } else
             load_digits_pair_lds<FU>(d, s_tmp, 2 * rp, L, bgbit, twist_t, t);
         fft512_x2<false, true, FU>(d, xb, T, t);
         pp.mark(2);

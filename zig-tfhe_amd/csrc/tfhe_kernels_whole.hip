@@ -74,18 +74,43 @@ DEV void gather_rot_one(uint32_t base, int t, int at, uint32_t *xb, uint32_t *v)
 
 // Inverse transform of ONE accumulated spectrum (fft1024), untwist, guarded
 // conversion and the CMUX add into acc (lane-local); exchange 1 through xb,
-// exchange 2 in registers (the single-transform fft512).
+// exchange 2 in registers.  The single-transform fft512<1, true> written out, so
+// that the 8 untwist factors are read as one group ahead of pass C, whose
+// butterflies cover them: behind pass C hipcc reads them two at a time, each
+// pair three instructions before its use, and this wave has no second transform
+// to fill the waits.  The empty asm pins pass C behind the reads (instruction
+// selection places pure arithmetic freely across a scheduling fence).  Measured
+// the same way and not kept: the pass-B twiddles ahead of exchange 1's stores
+// (slower), the pass-C twiddles ahead of exchange 2 (slower alone, level with
+// this when combined with it); profiles/ab_lds_read_groups.txt.
 template <bool FU, bool EX2LDS = false>
 DEV void inverse_one(const C2 *f, C2 *xb, const LdsTw &T, const C2 *twist_t, int t, uint32_t *acc, uint32_t &near) {
-    C2 e[1][8];
+    C2 e[1][8], tu[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) e[0][q] = f[br3(q)];
-    fft512<1, true, FU, LdsTw, EX2LDS>(e, xb, T, t);
+    passA<true, FU>(e[0], T.a);
+    exchange1<1>(e, xb, t);
+    {
+        C2 w[7];
+        T.pass_b(w, t);
+        passBC<true, FU>(e[0], w);
+    }
+    exchange2<1, EX2LDS>(e, xb, t);
+    {
+        C2 w[7];
+        T.pass_c(w, t);
+#pragma unroll
+        for (int q = 0; q < 8; q++) tu[q] = twist_t[64 * q];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 8; q++) asm volatile("" : "+v"(e[0][q].x), "+v"(e[0][q].y));
+        passBC<true, FU>(e[0], w);
+    }
     uint32_t nq[2] = {NEAR_NONE, NEAR_NONE};
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         double re, im;
-        untwist_out<false, FU>(e[0][q], twist_t[64 * q], re, im);
+        untwist_out<false, FU>(e[0][q], tu[q], re, im);
         acc[q] += to_torus<true, FU>(re, nq[0]);
         acc[q + 8] += to_torus<true, FU>(im, nq[1]);
     }
@@ -294,6 +319,11 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
                 pp.mark(1);
                 load_digits_pair0_regs<FU>(d, tA, nullptr, L, P.bgbit, tw0);  // rows 0, 1: a's levels 0, 1
             } else {
+                // the pair's twist factors as one read group: ahead of the tB wait (pair 1) and of the digit
+                // conversions, which cover its latency (load_digits_pair_tbx)
+                C2 twn[8];
+                read_twist8(twn, twist_t);
+                __builtin_amdgcn_sched_barrier(0);
                 if (rp == 1) {  // tB(i) from the loader, packed with a's level 2 (load_digits_pair_tbx)
                     pp.mark(4);
                     spin_short(tb_ready + gi, (uint32_t)i + 1u, spin_cap, fail);
@@ -304,7 +334,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
                                  (Y32[1024 + t + 64 * m] & ~((1u << P.bgbit) - 1u));
                 }
                 pp.mark(5);
-                load_digits_pair_tbx<FU>(d, tbx, rp, P.bgbit, twist_t);
+                load_digits_pair_tbx<FU>(d, tbx, rp, P.bgbit, twn);
             }
             fft512_x2<false, true, FU>(d, X, T, t);
             const uint32_t k = (uint32_t)(L * i + rp);
