@@ -87,6 +87,7 @@ def test_spread_dev_and_in_place(oracle):
         want = tfhe_amd.lut_spread_host(c.params, x, w, rot)
         t_in = to_dev(x)
         t_out = torch.full((3, 2 * N), -1, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()  # the fill runs on torch's stream, the spread on the context's: unordered otherwise
         c.lut_spread_dev(t_in.data_ptr(), w, rot, t_out.data_ptr(), 3)
         c.lut_spread_dev(t_in.data_ptr(), w, rot, t_in.data_ptr(), 3)  # in place
         c.sync()

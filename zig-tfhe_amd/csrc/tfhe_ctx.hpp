@@ -1,8 +1,9 @@
 // tfhe_ctx.hpp — the two types behind the C handle and what the host units
 // share: Device (everything that belongs to one GPU) and tfhe_gpu_ctx (the
 // handle: one Device or several), the owners of their HIP resources, error
-// reporting, a call's host-or-device buffers (Io), and the functions the host
-// units call in each other.  Not installed.
+// reporting, a call's scratch frame (Frame), descriptor upload (DescBlob) and
+// host-or-device buffers (Io), and the functions the host units call in each
+// other.  Not installed.
 #pragma once
 
 #include "tfhe_gpu.h"
@@ -21,6 +22,7 @@
 
 #include "tfhe_cpu.hpp"
 #include "tfhe_internal.hpp"
+#include "tfhe_scratch.hpp"
 
 namespace tfhe {
 
@@ -58,14 +60,8 @@ using HostPtr = Owned<T *, hipHostFree>;  // pinned
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 
-struct DevBuf {  // device scratch, grown on demand (ensure)
-    DevPtr<void> p;
-    size_t bytes = 0;
-    template <class T>
-    T *as() const {
-        return static_cast<T *>((void *)p);
-    }
-};
+static_assert(Scratch::KS_INPUT_SLACK == KS_GEMM_INPUT_SLACK, "the scratch arena's key-switch input slack is the GEMM's");
+
 struct PinBuf {  // pinned host buffer, grown on demand (ensure_pinned)
     HostPtr<char> p;
     size_t bytes = 0;
@@ -153,17 +149,11 @@ struct Device {
     DevPtr<double> d_bk;            // device layout, n*2L*512 double4
     DevPtr<uint32_t> d_ksk;         // reference rows padded to K.ks_stride words (ksk_dev_bytes)
     size_t bk_bytes = 0, ksk_bytes = 0;
-    // scratch, grown on demand
-    DevBuf s_a, s_b, s_out, s_lv1, s_ops, s_tv, s_tmp;
-    DevBuf s_wires, s_cidx, s_cops;  // circuit evaluator: wire table, gather indices, op codes
-    DevBuf s_ties;                   // near-tie flags (KParams::tie_flags), one byte per item, zero between launches
-    DevBuf s_kspart;                 // gemm key switch: the K splits' partial sums
-    DevBuf s_lk_a, s_lk_b, s_lk_idx;  // table lookup: the CMUX tree's ping-pong levels, its selector / gather indices
-    DevBuf s_rot_idx, s_rot_in;       // rotation by encrypted bits: selector / exponent / gather indices; the packed lookup's tree outputs
-    DevBuf s_sc_a, s_sc_b, s_sc_idx;  // packed scatter-add: the demux tree's ping-pong levels (s_sc_a: the leaves), its address bits
-    DevBuf s_lut_x;                  // LUT circuits: a launch's combined ciphertexts (k_lut_combine), the bootstrap's inputs
-    DevBuf s_lut_acc;                // multi-output LUT nodes: a launch's accumulators (TRLWELv1, 8 KB per node)
-    std::string lut_multi_ks;        // ... and what last_ks names after one: the fan-out extraction, then the key switch
+    // scratch: the calls' stack of frames (tfhe_scratch.hpp; Frame below), and the one buffer that persists
+    Scratch scratch;
+    DevPtr<uint8_t> s_ties;  // near-tie flags (KParams::tie_flags), one byte per item, zero between launches:
+    size_t ties_cap = 0;     // only a new buffer is memset, so they cannot live in a frame (ensure_tie_flags)
+    std::string lut_multi_ks;        // multi-output LUT nodes: what last_ks names after one: the fan-out extraction, then the key switch
     DevPtr<uint32_t> d_ksk_gemm;     // gemm key switch: the MFMA-layout KSK (ks_gemm_bytes), built from d_ksk
     bool ksk_gemm_ok = false;        // d_ksk_gemm matches d_ksk
     Event level_ev;                  // level-split circuits: this device's slice of a level is computed
@@ -307,10 +297,53 @@ enum RunKind : int {
 };
 
 // ---- tfhe_gpu.cpp, for the other host units --------------------------------------
-int ensure(Device &d, DevBuf &b, size_t bytes);                       // device scratch of at least `bytes`
-int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes);       // host -> `buf`, async on the device's stream
+int h2d_copy(Device &d, void *dst, const void *src, size_t bytes);    // host -> device memory, async on the device's stream
+
+// A frame of one device's scratch (tfhe_scratch.hpp).  Every entry point's _on function opens the call's
+// outermost one, and whatever has temporaries of its own (a bootstrap launch, a level, a chunk) a nested
+// one.  A slice is its taker's until the frame closes.  Reuse after that is safe because everything a call
+// launches is on the device's stream, or on the pipeline's streams, which the call joins before it returns.
+struct Frame : Scratch::Frame {
+    Device &d;
+    explicit Frame(Device &dv) : Scratch::Frame(dv.scratch), d(dv) {}
+    // host -> a new slice, async on the device's stream: the device copy, or NULL (rc())
+    template <class T>
+    const T *h2d(const T *src, size_t n_bytes) {
+        void *p = bytes(n_bytes);
+        if (!p) return nullptr;
+        if (const int rc = h2d_copy(d, p, src, n_bytes)) return fail(rc), nullptr;
+        return static_cast<const T *>(p);
+    }
+};
+
+// Descriptor arrays of one call, concatenated into one upload (u32 words; signed
+// coefficients keep their bits): where each starts in the device copy.
+struct DescBlob {
+    std::vector<uint32_t> words;
+    size_t add(const void *p, size_t count) {
+        const size_t at = reserve(count);
+        if (count) std::memcpy(words.data() + at, p, count * sizeof(uint32_t));
+        return at;
+    }
+    size_t add_bytes(const void *p, size_t count) {  // padded to words
+        const size_t at = reserve((count + 3) / 4);
+        if (count) std::memcpy(words.data() + at, p, count);
+        return at;
+    }
+    size_t reserve(size_t count) {  // zeros, for the caller to fill
+        const size_t at = words.size();
+        words.resize(at + count);
+        return at;
+    }
+    // The device copy in a slice of f (NULL: f.rc()).  The blob is pageable: hipMemcpyAsync stages it
+    // before it returns, so the blob may go while the copy is still in flight (a _dev call does not sync).
+    const uint32_t *upload(Frame &f) const {
+        return words.empty() ? f.take<uint32_t>(1) : f.h2d(words.data(), words.size() * sizeof(uint32_t));
+    }
+};
+
 DevTables tables(const Device &d);
-int ks_gemm_args(Device &d, size_t B, KsGemm &G);                     // the gemm key switch's buffers for B items
+int ks_gemm_args(Frame &f, size_t B, KsGemm &G);                      // the gemm key switch's buffers for B items
 int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint32_t *tv_b);
 int upload_ksk(Device &d, const uint32_t *ksk);                       // host KSK (reference layout) -> device KSK, async
 int key_loaded(Device &d, bool from_keygen);                          // the end of every key load on device 0: admission
@@ -319,55 +352,64 @@ int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const ui
                       uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr, const uint32_t *tv_sel = nullptr);
 int sync_check(Device &d);
 int d2h_sync(Device &d, void *dst, const void *src, size_t bytes);
-int upload_plan(Device &d, const CircuitPlan &pl, size_t W, size_t n_inputs, const uint32_t *inputs, size_t n_outputs,
+// A circuit plan on one device, in slices of f: the wire table with the inputs, the gather indices and the op codes.
+struct PlanBufs {
+    uint32_t *wires = nullptr;
+    const uint32_t *idx = nullptr;
+    const uint8_t *ops = nullptr;
+};
+int upload_plan(Frame &f, const CircuitPlan &pl, size_t W, size_t n_inputs, const uint32_t *inputs, PlanBufs &pb,
                 bool inputs_on_device = false);
 int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t n_gates, const uint8_t *ops,
                      const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
-                     uint32_t *outputs, uint32_t *levels_out, bool dev = false);
+                     uint32_t *outputs, uint32_t *depth_out, bool dev = false);
 
 // The buffers of one call on one device.  Host buffers (dev = false) are staged through the
-// device's scratch: in() uploads one and out() reserves room for one, each leaving its
-// pointer at the scratch copy for the launches that follow, and finish() copies the output
-// back and waits.  Device pointers (dev = true) stay as they are, and nothing is waited for.
+// call's frame: in() uploads one, out() takes room for one and inout() does both for a buffer
+// the call updates, each leaving its pointer at the slice for the launches that follow, and
+// finish() copies the output back and waits.  Device pointers (dev = true) stay as they are,
+// and nothing is waited for.
 struct Io {
-    Device &d;
+    Frame &f;
     bool dev;
-    void *host_out = nullptr;  // out(): the caller's buffer, its scratch copy and size
+    void *host_out = nullptr;  // out() / inout(): the caller's buffer, its slice and size
     const void *staged_out = nullptr;
     size_t out_bytes = 0;
 
     template <class T>
-    int in(DevBuf &buf, const T *&p, size_t bytes) {
-        if (dev) return TFHE_OK;
-        const int rc = h2d(d, buf, p, bytes);
-        p = buf.as<const T>();
-        return rc;
-    }
-    template <class T>
-    int out(T *&p, size_t bytes, DevBuf &buf) {
-        if (dev) return TFHE_OK;
-        const int rc = ensure(d, buf, bytes);
-        host_out = p;
-        out_bytes = bytes;
-        staged_out = p = buf.as<T>();
-        return rc;
+    int in(const T *&p, size_t bytes) {
+        if (!dev) p = f.h2d(p, bytes);
+        return f.rc();
     }
     template <class T>
     int out(T *&p, size_t bytes) {
-        return out(p, bytes, d.s_out);
+        return dev ? f.rc() : staged(p, bytes, f.bytes(bytes));
+    }
+    template <class T>
+    int inout(T *&p, size_t bytes) {
+        return dev ? f.rc() : staged(p, bytes, const_cast<T *>(f.h2d(p, bytes)));
     }
     // The host call waits: for its output, or without one for the work and the error word.
     int finish() {
         if (dev) return TFHE_OK;
-        return host_out ? d2h_sync(d, host_out, staged_out, out_bytes) : sync_check(d);
+        return host_out ? d2h_sync(f.d, host_out, staged_out, out_bytes) : sync_check(f.d);
+    }
+
+  private:
+    template <class T>
+    int staged(T *&p, size_t bytes, void *slice) {
+        host_out = p;
+        out_bytes = bytes;
+        staged_out = p = static_cast<T *>(slice);
+        return f.rc();
     }
 };
 
 // ---- tfhe_pack.cpp, for tfhe_lut.cpp --------------------------------------------
 // Items per chunk of a pack of `items` inputs: what keeps the GEMM sums within TFHE_OPT_PACK_SCRATCH_MB.
 size_t pack_chunk_items(const Device &d, size_t items, int basebit);
-// The pack's launches over device buffers, async: x = B * C TLWELv0 with 2 * KS_GEMM_INPUT_SLACK readable
-// bytes past the last, coef = C device words, out = B TRLWELv1; chunked by pack_chunk_items.
+// The pack's launches over device buffers, async: x = B * C TLWELv0 from Frame::ks_input(.., pack) for its
+// readable bytes past the last, coef = C device words, out = B TRLWELv1; chunked by pack_chunk_items.
 int pack_launch(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *x, const uint32_t *coef_dev, size_t C,
                 uint32_t *out, size_t B);
 
@@ -377,6 +419,6 @@ int broadcast_key(tfhe_gpu_ctx *c);
 void destroy_comms(tfhe_gpu_ctx *c);
 int circuit_eval_multi(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t *inputs, size_t n_gates, const uint8_t *ops,
                        const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
-                       uint32_t *outputs, uint32_t *levels_out);
+                       uint32_t *outputs, uint32_t *depth_out);
 
 }  // namespace tfhe

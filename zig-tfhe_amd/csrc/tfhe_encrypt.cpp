@@ -22,9 +22,10 @@ namespace tfhe {
 // as = a * s (k_poly_mul) for R polynomials a and the key s: host buffers, synchronous.
 static int mul_by_key(Device &d, const uint32_t *key_lv1, const uint32_t *a, uint32_t *as, size_t R) {
     const size_t N = d.P.N;
-    Io io{d, /*dev*/ false};
-    int rc = io.in(d.s_b, key_lv1, N * sizeof(uint32_t));
-    if (!rc) rc = io.in(d.s_a, a, R * N * sizeof(uint32_t));
+    Frame f(d);
+    Io io{f, /*dev*/ false};
+    int rc = io.in(key_lv1, N * sizeof(uint32_t));
+    if (!rc) rc = io.in(a, R * N * sizeof(uint32_t));
     if (!rc) rc = io.out(as, R * N * sizeof(uint32_t));
     if (rc) return rc;
     HIPCHK(d, launch_poly_mul(tables(d), a, key_lv1, 0, as, R, d.stream));
@@ -62,10 +63,11 @@ static int trlwe_encrypt_rows(Device &d, const uint32_t *key_lv1, const std::vec
 // S TRGSWLv1 encryptTorus (trgsw.zig:35-71) of the plaintexts mu, TRLWE row r of the
 // S * 2L from DefaultPrng(seeds[r]): 2L TRLWE encryptions of zero each, the gadget on a[0]
 // of row l and b[0] of row L + l.  Then TRGSWLv1FFT.new (trgsw.zig:81-91), the ifft of every
-// a and b polynomial: the S * 2L * 2 spectra are left in d.s_tmp (reference BK layout),
-// queued on the device's stream.
-static int trgsw_spectra(Device &d, const uint32_t *key_lv1, const std::vector<uint64_t> &seeds, const uint32_t *mu,
+// a and b polynomial: the S * 2L * 2 spectra are left in a slice of the caller's frame, *spectra
+// (reference BK layout), queued on the device's stream.
+static int trgsw_spectra(Frame &f, double **spectra, const uint32_t *key_lv1, const std::vector<uint64_t> &seeds, const uint32_t *mu,
                          double alpha) {
+    Device &d = f.d;
     const size_t N = d.P.N, L = d.P.L, R = seeds.size(), S = R / (2 * L);
     std::vector<uint32_t> rows(R * 2 * N);
     int rc = trlwe_encrypt_rows(d, key_lv1, seeds, nullptr, alpha, rows.data());
@@ -77,10 +79,10 @@ static int trgsw_spectra(Device &d, const uint32_t *key_lv1, const std::vector<u
             rows[(s * 2 * L + L + l) * 2 * N + N] += mu[s] * h;
         }
     // hipMemcpyAsync stages a pageable source before it returns (upload_plan): rows may go
-    rc = h2d(d, d.s_a, rows.data(), rows.size() * sizeof(uint32_t));
-    if (!rc) rc = ensure(d, d.s_tmp, R * 2 * N * sizeof(double));
-    if (rc) return rc;
-    HIPCHK(d, launch_fft_forward(tables(d), d.s_a.as<const uint32_t>(), d.s_tmp.as<double>(), R * 2, d.stream));
+    *spectra = f.take<double>(R * 2 * N);
+    const uint32_t *rows_dev = f.h2d(rows.data(), rows.size() * sizeof(uint32_t));
+    if (f.rc()) return f.rc();
+    HIPCHK(d, launch_fft_forward(tables(d), rows_dev, *spectra, R * 2, d.stream));
     return TFHE_OK;
 }
 
@@ -168,8 +170,10 @@ int tfhe_gpu_trgsw_encrypt_batch(tfhe_gpu_ctx *c, const uint32_t *key_lv1, const
             host::Rng master(seed0 + s);
             for (size_t r = 0; r < 2 * L; r++) seeds[s * 2 * L + r] = master.next();
         }
-        const int rc = trgsw_spectra(d, key_lv1, seeds, mu, alpha);
-        return rc ? rc : d2h_sync(d, out_fft, d.s_tmp.p, R * 2 * d.P.N * sizeof(double));
+        Frame f(d);
+        double *spectra = nullptr;
+        const int rc = trgsw_spectra(f, &spectra, key_lv1, seeds, mu, alpha);
+        return rc ? rc : d2h_sync(d, out_fft, spectra, R * 2 * d.P.N * sizeof(double));
     });
 }
 
@@ -197,7 +201,9 @@ int tfhe_gpu_keygen(tfhe_gpu_ctx *c, uint64_t secret_seed, uint64_t cloud_seed, 
         const size_t R = bk_rows(p);  // n*2L TRLWE rows
         std::vector<uint64_t> seeds(R);
         for (uint64_t &s : seeds) s = master.next();
-        int rc = trgsw_spectra(d, key_lv1, seeds, key_lv0, p.alpha_bsk);
+        Frame f(d);  // the BK spectra, until the stream has been waited for
+        double *spectra = nullptr;
+        int rc = trgsw_spectra(f, &spectra, key_lv1, seeds, key_lv0, p.alpha_bsk);
         if (rc) return rc;
         std::vector<uint32_t> tv(2 * N);
         for (uint32_t x = 0; x < N; x++) {  // genTestvec (key.zig:134-145)
@@ -206,11 +212,11 @@ int tfhe_gpu_keygen(tfhe_gpu_ctx *c, uint64_t secret_seed, uint64_t cloud_seed, 
         }
         rc = set_key_common(d, decomposition_offset(p), tv.data(), tv.data() + N);
         if (rc) return rc;
-        HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), d.d_bk, R, d.stream));
+        HIPCHK(d, launch_bk_permute(d.K, spectra, d.d_bk, R, d.stream));
         rc = upload_ksk(d, ksk.data());
         if (rc) return rc;
         if (bsk_out)
-            HIPCHK(d, hipMemcpyAsync(bsk_out, d.s_tmp.p, R * 2 * N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+            HIPCHK(d, hipMemcpyAsync(bsk_out, spectra, R * 2 * N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
         HIPCHK(d, hipStreamSynchronize(d.stream));
         if (ksk_out) std::memcpy(ksk_out, ksk.data(), ksk.size() * sizeof(uint32_t));
         return key_loaded(d, /*from_keygen*/ true);

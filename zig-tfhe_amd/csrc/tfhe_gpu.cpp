@@ -32,14 +32,20 @@ static int create_fail(int code, const std::string &msg) {
     return code;
 }
 
-int ensure(Device &d, DevBuf &b, size_t bytes) {
-    if (b.bytes >= bytes) return TFHE_OK;
-    b.bytes = 0;
-    size_t want = std::max<size_t>(bytes, 4096);
-    hipError_t e = hipMalloc(b.p.make(d.device), want);  // the old buffer is freed first
-    if (e != hipSuccess) return fail(d, TFHE_ERR_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    b.bytes = want;
-    return TFHE_OK;
+// The scratch arena's allocator (tfhe_scratch.hpp), user = the Device: a failed take is TFHE_ERR_OOM with
+// this message.  hipFree waits for the device, so blocks may go while a _dev call's kernels still run.
+static void *scratch_alloc(void *user, size_t bytes) {
+    Device &d = *static_cast<Device *>(user);
+    void *p = nullptr;
+    hipError_t e = hipSetDevice(d.device);
+    if (e == hipSuccess) e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) return p;
+    d.err = std::string("hipMalloc: ") + hipGetErrorString(e);
+    return nullptr;
+}
+static void scratch_free(void *user, void *p) {
+    (void)hipSetDevice(static_cast<Device *>(user)->device);
+    (void)hipFree(p);
 }
 
 DevTables tables(const Device &d) {
@@ -85,7 +91,8 @@ int set_key_common(Device &d, uint32_t offset, const uint32_t *tv_a, const uint3
 // (ks_use_gemm): the MFMA-layout KSK, rebuilt on the stream after a key change,
 // and the partial sums.  G stays empty for the other forms (launch_key_switch
 // ignores it).
-int ks_gemm_args(Device &d, size_t B, KsGemm &G) {
+int ks_gemm_args(Frame &f, size_t B, KsGemm &G) {
+    Device &d = f.d;
     G = KsGemm();
     if (!ks_use_gemm(d.opts, d.K.iks_t, d.K.basebit, B, nullptr)) return TFHE_OK;
     if (!d.d_ksk_gemm) {
@@ -96,20 +103,21 @@ int ks_gemm_args(Device &d, size_t B, KsGemm &G) {
         HIPCHK(d, launch_ksk_to_gemm(d.K, d.d_ksk, d.d_ksk_gemm, 1024, d.K.iks_t, d.K.basebit, d.stream));
         d.ksk_gemm_ok = true;
     }
-    int rc = ensure(d, d.s_kspart, ks_gemm_part_bytes(d.K, B, 1024, d.K.basebit));
-    if (rc) return rc;
     G.kg = d.d_ksk_gemm;
-    G.part = d.s_kspart.as<uint32_t>();
-    return TFHE_OK;
+    G.part = static_cast<uint32_t *>(f.bytes(ks_gemm_part_bytes(d.K, B, 1024, d.K.basebit)));
+    return f.rc();
 }
 
 // Near-tie flags (KParams::tie_flags) for B items.  The flags are all zero between
 // launches, so only a new buffer is zeroed (on the device's stream).
 static int ensure_tie_flags(Device &d, size_t B) {
-    if (d.s_ties.bytes >= B) return TFHE_OK;
-    int rc = ensure(d, d.s_ties, B);
-    if (rc) return rc;
-    HIPCHK(d, hipMemsetAsync(d.s_ties.p, 0, d.s_ties.bytes, d.stream));
+    if (d.ties_cap >= B) return TFHE_OK;
+    d.ties_cap = 0;
+    const size_t want = std::max<size_t>(B, 4096);
+    const hipError_t e = hipMalloc((void **)d.s_ties.make(d.device), want);  // the old flags are freed first
+    if (e != hipSuccess) return fail(d, TFHE_ERR_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    d.ties_cap = want;
+    HIPCHK(d, hipMemsetAsync(d.s_ties, 0, want, d.stream));
     return TFHE_OK;
 }
 
@@ -121,13 +129,14 @@ int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const ui
     const int out_mode = kind == RUN_BOOTSTRAP ? BR_OUT_LV1 : kind == RUN_TRLWE ? BR_OUT_TRLWE : BR_OUT_LV0_EXTRACT2;
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     if (B == 0) return TFHE_OK;
-    int rc = ensure(d, d.s_lv1, B * 1025 * sizeof(uint32_t));
+    Frame f(d);  // the extracted TLWELv1 between the two launches, and the key switch's sums
+    uint32_t *lv1 = key_switch ? f.ks_input<uint32_t>(B * 1025) : out;
+    int rc = f.rc();
     if (!rc) rc = ensure_tie_flags(d, B);
     if (rc) return rc;
     KParams K = d.K;
-    K.tie_flags = d.s_ties.as<uint8_t>();
+    K.tie_flags = d.s_ties;
     K.tv_sel = tv_sel;  // LUT circuits: B table indices into testvec_dev (device), or NULL
-    uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : out;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (d.profiling) {
         while (d.events.size() < d.ev_used + 3) {
@@ -146,7 +155,7 @@ int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const ui
     d.last_ks = "";
     if (key_switch) {
         KsGemm G;
-        if ((rc = ks_gemm_args(d, B, G))) return rc;
+        if ((rc = ks_gemm_args(f, B, G))) return rc;
         HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, B, d.stream, d.opts, &d.last_ks, &G));
     }
     if (ev[2]) HIPCHK(d, hipEventRecord(ev[2], d.stream));
@@ -166,18 +175,16 @@ static int ensure_pinned(Device &d, PinBuf &b, size_t bytes, size_t floor = 0) {
 }
 constexpr size_t STAGE_FLOOR = (size_t)1 << 20;  // the staging arenas start at 1 MiB
 
-// Host -> device into `buf`.  Pageable: one hipMemcpyAsync from the caller's buffer.  Staged
+// Host -> device memory at `dst`.  Pageable: one hipMemcpyAsync from the caller's buffer.  Staged
 // (TFHE_OPT_HOST_STAGING): a host memcpy into this device's pinned arena, then the DMA from
 // there, so concurrent devices' copies do not go through the runtime's pageable staging
 // (for hosts where those serialise across host threads; on the MI355X box they do not and
 // pageable copies are faster).  The arena is reused from
 // offset 0 after every synchronisation of the stream (d2h_sync); when it is full the stream
 // is synchronised first, so no copy in flight ever reads overwritten bytes.
-int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes) {
-    int rc = ensure(d, buf, bytes);
-    if (rc) return rc;
+int h2d_copy(Device &d, void *dst, const void *src, size_t bytes) {
     if (!staged(d) || !bytes) {
-        HIPCHK(d, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, d.stream));
+        HIPCHK(d, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d.stream));
         return TFHE_OK;
     }
     const size_t need = (bytes + 255) & ~(size_t)255;
@@ -185,13 +192,13 @@ int h2d(Device &d, DevBuf &buf, const void *src, size_t bytes) {
         HIPCHK(d, hipStreamSynchronize(d.stream));
         d.stage_used = 0;
         if (need > d.stage_in.bytes) {  // grow (doubling) only when one copy does not fit the empty arena
-            rc = ensure_pinned(d, d.stage_in, std::max(need, 2 * d.stage_in.bytes), STAGE_FLOOR);
+            const int rc = ensure_pinned(d, d.stage_in, std::max(need, 2 * d.stage_in.bytes), STAGE_FLOOR);
             if (rc) return rc;
         }
     }
     char *p = d.stage_in.p + d.stage_used;
     std::memcpy(p, src, bytes);
-    HIPCHK(d, hipMemcpyAsync(buf.p, p, bytes, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(d, hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, d.stream));
     d.stage_used += need;
     return TFHE_OK;
 }
@@ -377,6 +384,7 @@ static int init_device(Device &d, const tfhe_params &p, int device) {
     if (e != hipSuccess) return hip_fail(d, e, "device error word");
     std::memset(d.h_err, 0, 64);
     d.K.err = d.d_err;
+    d.scratch.set_allocator({scratch_alloc, scratch_free, &d});  // a context's devices stay where they are (tfhe_gpu_ctx::dev)
     return build_tables(d, TFHE_TWIDDLES_GLIBC);
 }
 
@@ -492,9 +500,10 @@ int tfhe_gpu_load_cloud_key(tfhe_gpu_ctx *c, uint32_t offset, const uint32_t *tv
     const int rc = on_device0(c, [&](Device &d) -> int {
         int rc = set_key_common(d, offset, tv_a, tv_b);
         if (rc) return rc;
-        rc = h2d(d, d.s_tmp, bsk, bsk_len * sizeof(double));
-        if (rc) return rc;
-        HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), d.d_bk, rows, d.stream));
+        Frame f(d);
+        const double *staged_bk = f.h2d(bsk, bsk_len * sizeof(double));
+        if (f.rc()) return f.rc();
+        HIPCHK(d, launch_bk_permute(d.K, staged_bk, d.d_bk, rows, d.stream));
         rc = upload_ksk(d, ksk);
         if (rc) return rc;
         HIPCHK(d, launch_ksk_zero_k0(d.K, d.d_ksk, d.stream));  // reference leaves k=0 rows undefined
@@ -549,15 +558,16 @@ int tfhe_gpu_export_cloud_key(tfhe_gpu_ctx *c, uint32_t *offset, uint32_t *tv_a,
     if (!c->dev[0].has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
     return on_device0(c, [&](Device &d) -> int {
         const size_t N = d.P.N;
+        Frame f(d);  // open until the stream has been waited for
         if (offset) *offset = d.offset;
         if (tv_a) std::memcpy(tv_a, d.testvec.data(), N * sizeof(uint32_t));
         if (tv_b) std::memcpy(tv_b, d.testvec.data() + N, N * sizeof(uint32_t));
         if (bsk) {
             const size_t rows = bk_rows(d.P), bytes = rows * 2 * N * sizeof(double);
-            int rc = ensure(d, d.s_tmp, bytes);
-            if (rc) return rc;
-            HIPCHK(d, launch_bk_unpermute(d.K, d.d_bk, d.s_tmp.as<double>(), rows, d.stream));
-            HIPCHK(d, hipMemcpyAsync(bsk, d.s_tmp.p, bytes, hipMemcpyDeviceToHost, d.stream));
+            double *staged_bk = static_cast<double *>(f.bytes(bytes));
+            if (f.rc()) return f.rc();
+            HIPCHK(d, launch_bk_unpermute(d.K, d.d_bk, staged_bk, rows, d.stream));
+            HIPCHK(d, hipMemcpyAsync(bsk, staged_bk, bytes, hipMemcpyDeviceToHost, d.stream));
         }
         if (ksk) {
             const size_t w = d.P.n + 1;
@@ -606,20 +616,21 @@ namespace tfhe {
 // D2H on its stream, so chunk k+1's copies run while chunks <= k compute and
 // the S streams' kernels share the CUs.  Each worker then waits for its stream
 // and copies its chunks' outputs to the caller.  ops / b / tv_dev may be NULL.
-static int pipelined_bootstrap(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b,
+static int pipelined_bootstrap(Frame &f, const uint8_t *ops, const uint32_t *a, const uint32_t *b,
                         const uint32_t *tv_dev, uint32_t *out, size_t B) {
+    Device &d = f.d;
     const size_t w = tlwe0_words(d.P), wb = w * 4, chunk = device_cus();
     const size_t nch = (B + chunk - 1) / chunk;
     const int S = (int)std::min<size_t>(PIPE_STREAMS, nch);
     // staging layout per item: op byte region, then a, then b (all chunks contiguous)
-    const size_t ops_bytes = ops ? (B + 15) / 16 * 16 : 0, a_bytes = B * wb, b_bytes = b ? B * wb : 0;
-    int rc = ensure_pinned(d, d.pin_in, ops_bytes + a_bytes + b_bytes);
+    const size_t op_bytes = ops ? (B + 15) / 16 * 16 : 0, a_bytes = B * wb, b_bytes = b ? B * wb : 0;
+    int rc = ensure_pinned(d, d.pin_in, op_bytes + a_bytes + b_bytes);
     if (!rc) rc = ensure_pinned(d, d.pin_out, B * wb);
-    if (!rc && ops) rc = ensure(d, d.s_ops, B);
-    if (!rc) rc = ensure(d, d.s_a, B * wb);
-    if (!rc && b) rc = ensure(d, d.s_b, B * wb);
-    if (!rc) rc = ensure(d, d.s_out, B * wb);
-    if (!rc) rc = ensure(d, d.s_lv1, B * 1025 * sizeof(uint32_t));
+    // every slice now: the workers never touch the frame
+    uint8_t *d_ops = ops ? f.take<uint8_t>(B) : nullptr;
+    uint32_t *d_a = f.take<uint32_t>(B * w), *d_b = b ? f.take<uint32_t>(B * w) : nullptr, *d_out = f.take<uint32_t>(B * w);
+    uint32_t *d_lv1 = f.ks_input<uint32_t>(B * 1025);
+    if (!rc) rc = f.rc();
     if (!rc) rc = ensure_tie_flags(d, B);
     if (rc) return rc;
     if (!d.pipe_ev) HIPCHK(d, hipEventCreateWithFlags(d.pipe_ev.make(d.device), hipEventDisableTiming));
@@ -631,23 +642,16 @@ static int pipelined_bootstrap(Device &d, const uint8_t *ops, const uint32_t *a,
     // partial-sum buffer, so every chunk runs the same key-switch form as the
     // unpipelined path (last_kernels names it)
     KsGemm G;
-    rc = ks_gemm_args(d, chunk, G);
+    rc = ks_gemm_args(f, chunk, G);
     if (rc) return rc;
     std::vector<KsGemm> Gs(S, G);
-    if (G.kg) {
-        const size_t pb = ks_gemm_part_bytes(d.K, chunk, 1024, d.K.basebit);
-        rc = ensure(d, d.s_kspart, pb * S);
-        if (rc) return rc;
-        for (int s = 0; s < S; s++) Gs[s].part = (uint32_t *)(d.s_kspart.as<char>() + (size_t)s * pb);
-    }
+    for (int s = 1; s < S && G.kg; s++)
+        if ((rc = ks_gemm_args(f, chunk, Gs[s]))) return rc;
     // everything enqueued on the device's stream (key loads, the flags' memset) first
     HIPCHK(d, hipEventRecord(d.pipe_ev, d.stream));
     LaunchOpts o = d.opts;
     if (!o.br_form) o.br_form = 1;  // whole form for every chunk (a chunk is a quarter round)
-    char *pin_ops = d.pin_in.p, *pin_a = pin_ops + ops_bytes, *pin_b = pin_a + a_bytes;
-    uint8_t *d_ops = d.s_ops.as<uint8_t>();
-    uint32_t *d_a = d.s_a.as<uint32_t>(), *d_b = d.s_b.as<uint32_t>(), *d_out = d.s_out.as<uint32_t>();
-    uint32_t *d_lv1 = d.s_lv1.as<uint32_t>();
+    char *pin_ops = d.pin_in.p, *pin_a = pin_ops + op_bytes, *pin_b = pin_a + a_bytes;
     std::vector<hipError_t> err(S, hipSuccess);
     std::vector<const char *> where(S, "");
     d.workers->run(S, [&](int s) {
@@ -671,7 +675,7 @@ static int pipelined_bootstrap(Device &d, const uint8_t *ops, const uint32_t *a,
             if (b && !chk(hipMemcpyAsync(d_b + k0 * w, pin_b + k0 * wb, n * wb, hipMemcpyHostToDevice, st), "H2D b"))
                 return;
             KParams K = d.K;
-            K.tie_flags = d.s_ties.as<uint8_t>() + k0;
+            K.tie_flags = d.s_ties + k0;
             const BrBatch batch{ops ? d_ops + k0 : nullptr, d_a + k0 * w, b ? d_b + k0 * w : nullptr, nullptr,
                                 tv_dev ? tv_dev : d.d_testvec, d.d_bk, d_lv1 + k0 * 1025, BR_OUT_LV1, n};
             if (!chk(launch_blind_rotate(K, tables(d), batch, st, o, s == 0 && k == 0 ? &d.last_br : nullptr),
@@ -728,23 +732,18 @@ static int host_batch_on(Device &d, const HostBatch &hb, size_t first, size_t B)
             if (ops[i] > TFHE_GATE_ORYN && ops[i] != TFHE_GATE_COPY) return fail(d, TFHE_ERR_INVALID, "bad gate op");
     HIPCHK(d, hipSetDevice(d.device));
     if (hb.needs_key && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
-    const size_t in_bytes = B * w * 4, out_bytes = B * wo * 4;
-    const uint32_t *tv = nullptr;
-    int rc = TFHE_OK;
-    if (hb.testvec) {
-        if ((rc = h2d(d, d.s_tv, hb.testvec, 2 * d.P.N * 4))) return rc;
-        tv = d.s_tv.as<const uint32_t>();
-    }
-    if (hb.may_pipeline && use_pipeline(d, B)) return pipelined_bootstrap(d, ops, a, b, tv, out, B);
-    if (hb.gate) rc = h2d(d, d.s_ops, ops, B);
-    if (!rc) rc = h2d(d, d.s_a, a, in_bytes);
-    if (!rc && hb.gate) rc = h2d(d, d.s_b, b, in_bytes);
-    if (!rc) rc = ensure(d, d.s_out, out_bytes);
-    if (!rc)
-        rc = run_bootstrap_dev(d, hb.gate ? d.s_ops.as<const uint8_t>() : nullptr, d.s_a.as<const uint32_t>(),
-                               hb.gate ? d.s_b.as<const uint32_t>() : nullptr, tv, d.s_out.as<uint32_t>(), B, hb.kind);
-    if (!rc) rc = d2h_sync(d, out, d.s_out.p, out_bytes);
-    return rc;
+    const size_t in_bytes = B * w * 4;
+    Frame f(d);
+    Io io{f, /*dev*/ false};
+    const uint32_t *tv = hb.testvec ? f.h2d(hb.testvec, 2 * d.P.N * 4) : nullptr;
+    if (f.rc()) return f.rc();
+    if (hb.may_pipeline && use_pipeline(d, B)) return pipelined_bootstrap(f, ops, a, b, tv, out, B);
+    if (hb.gate) io.in(ops, B);
+    io.in(a, in_bytes);
+    if (hb.gate) io.in(b, in_bytes);
+    int rc = io.out(out, B * wo * 4);
+    if (!rc) rc = run_bootstrap_dev(d, ops, a, b, tv, out, B, hb.kind);
+    return rc ? rc : io.finish();
 }
 
 }  // namespace tfhe
@@ -794,21 +793,20 @@ static int reencrypt_on(Device &d, const tfhe_gpu_reenc_key &key, size_t slot, c
     if (B == 0) return TFHE_OK;
     HIPCHK(d, hipSetDevice(d.device));
     const size_t w = tlwe0_words(d.P);
-    Io io{d, dev};
-    int rc = ensure(d, d.s_a, B * w * 4 + KS_GEMM_INPUT_SLACK);  // the gemm form reads whole blocks of 8
-    if (!rc) rc = io.out(out, B * w * 4);
-    if (rc) return rc;
-    if (dev) HIPCHK(d, hipMemcpyAsync(d.s_a.p, in, B * w * 4, hipMemcpyDeviceToDevice, d.stream));
-    else if ((rc = h2d(d, d.s_a, in, B * w * 4))) return rc;
+    Frame f(d);
+    Io io{f, dev};
+    uint32_t *x = f.ks_input<uint32_t>(B * w);  // the gemm form reads whole blocks of 8
+    int rc = io.out(out, B * w * 4);
     KsGemm G;
     if (k.key_gemm) {
-        rc = ensure(d, d.s_kspart, ks_gemm_part_bytes(d.K, B, (int)d.P.n, (int)key.basebit));
-        if (rc) return rc;
         G.kg = k.key_gemm;
-        G.part = d.s_kspart.as<uint32_t>();
+        G.part = static_cast<uint32_t *>(f.bytes(ks_gemm_part_bytes(d.K, B, (int)d.P.n, (int)key.basebit)));
+        rc = f.rc();
     }
-    HIPCHK(d, launch_reencrypt(d.K, (int)key.t, (int)key.basebit, d.s_a.as<const uint32_t>(), k.key, out, B, d.stream,
-                               d.opts, &d.last_ks, &G));
+    if (rc) return rc;
+    if (dev) HIPCHK(d, hipMemcpyAsync(x, in, B * w * 4, hipMemcpyDeviceToDevice, d.stream));
+    else if ((rc = h2d_copy(d, x, in, B * w * 4))) return rc;
+    HIPCHK(d, launch_reencrypt(d.K, (int)key.t, (int)key.basebit, x, k.key, out, B, d.stream, d.opts, &d.last_ks, &G));
     return io.finish();
 }
 
@@ -833,24 +831,21 @@ namespace tfhe {
 
 // Device side of a plan on one device: wire table with the inputs, the gather
 // indices and op codes, uploaded on its stream.
-int upload_plan(Device &d, const CircuitPlan &pl, size_t W, size_t n_inputs, const uint32_t *inputs,
-                size_t n_outputs, bool inputs_on_device) {
+int upload_plan(Frame &f, const CircuitPlan &pl, size_t W, size_t n_inputs, const uint32_t *inputs, PlanBufs &pb,
+                bool inputs_on_device) {
+    Device &d = f.d;
     const size_t w1 = tlwe0_words(d.P);
     HIPCHK(d, hipSetDevice(d.device));
-    int rc = ensure(d, d.s_wires, std::max<size_t>(W, 1) * w1 * 4);
-    if (!rc) rc = ensure(d, d.s_cidx, std::max<size_t>(pl.idx.size(), 1) * 4);
-    if (!rc) rc = ensure(d, d.s_cops, std::max<size_t>(pl.cops.size(), 1));
-    if (!rc) rc = ensure(d, d.s_out, std::max<size_t>(n_outputs, 1) * w1 * 4);
-    if (rc) return rc;
+    DescBlob blob;  // the gather indices, then the op bytes padded to words: one copy
+    blob.add(pl.idx.data(), pl.idx.size());
+    const size_t op_at = blob.add_bytes(pl.cops.data(), pl.cops.size());
+    pb.wires = f.take<uint32_t>(W * w1);
+    pb.idx = blob.upload(f);
+    if (f.rc()) return f.rc();
+    pb.ops = reinterpret_cast<const uint8_t *>(pb.idx + op_at);
     if (n_inputs)
-        HIPCHK(d, hipMemcpyAsync(d.s_wires.p, inputs, n_inputs * w1 * 4,
+        HIPCHK(d, hipMemcpyAsync(pb.wires, inputs, n_inputs * w1 * 4,
                                  inputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-    // the plan vectors are pageable: hipMemcpyAsync stages them before it returns, so the caller
-    // may drop `pl` while the copies are still in flight (the _dev circuit call does not sync)
-    if (!pl.idx.empty())
-        HIPCHK(d, hipMemcpyAsync(d.s_cidx.p, pl.idx.data(), pl.idx.size() * 4, hipMemcpyHostToDevice, d.stream));
-    if (!pl.cops.empty())
-        HIPCHK(d, hipMemcpyAsync(d.s_cops.p, pl.cops.data(), pl.cops.size(), hipMemcpyHostToDevice, d.stream));
     return TFHE_OK;
 }
 
@@ -860,7 +855,7 @@ int upload_plan(Device &d, const CircuitPlan &pl, size_t W, size_t n_inputs, con
 // returns without waiting (async on the device's stream, like the other _dev entries)
 int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t n_gates, const uint8_t *ops,
                      const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
-                     uint32_t *outputs, uint32_t *levels_out, bool dev) {
+                     uint32_t *outputs, uint32_t *depth_out, bool dev) {
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t W = n_inputs + n_gates, w1 = tlwe0_words(d.P);
     HIPCHK(d, hipSetDevice(d.device));
@@ -868,16 +863,18 @@ int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t 
     if (const char *why = plan_circuit(n_inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires, d.circuit_pack != 0,
                                        device_cus(), level_cost, pl))
         return fail(d, TFHE_ERR_INVALID, why);
-    Io io{d, dev};
-    int rc = upload_plan(d, pl, W, n_inputs, inputs, n_outputs, dev);
-    if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w1 * 4);  // room made by upload_plan
+    Frame f(d);
+    Io io{f, dev};
+    PlanBufs pb;
+    int rc = upload_plan(f, pl, W, n_inputs, inputs, pb, dev);
+    if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w1 * 4);
     if (rc) return rc;
     const auto &bs = pl.bs;
     const auto &nots = pl.nots;
     const uint32_t max_level = pl.max_level;
-    uint32_t *wires = d.s_wires.as<uint32_t>();
-    const uint32_t *d_idx = d.s_cidx.as<const uint32_t>();
-    const uint8_t *d_ops = d.s_cops.as<const uint8_t>();
+    uint32_t *wires = pb.wires;
+    const uint32_t *d_idx = pb.idx;
+    const uint8_t *d_ops = pb.ops;
     size_t ip = 0, op_pos = 0, sp = n_inputs;
     for (uint32_t lv = 0; lv <= max_level; lv++) {
         const size_t nb = bs[lv].size(), nn = nots[lv].size();
@@ -897,7 +894,7 @@ int circuit_eval_one(Device &d, size_t n_inputs, const uint32_t *inputs, size_t 
     }
     if (n_outputs) HIPCHK(d, launch_tlwe_gather(d.K, wires, d_idx + ip, outputs, n_outputs, false, d.stream));
     if ((rc = io.finish())) return rc;
-    if (levels_out) *levels_out = max_level;
+    if (depth_out) *depth_out = max_level;
     return TFHE_OK;
 }
 
@@ -905,12 +902,15 @@ static int key_switch_on(Device &d, const uint32_t *in_lv1, uint32_t *out_lv0, s
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     if (B == 0) return TFHE_OK;
     HIPCHK(d, hipSetDevice(d.device));
-    Io io{d, /*dev*/ false};
-    int rc = io.in(d.s_lv1, in_lv1, B * 1025 * 4);
-    if (!rc) rc = io.out(out_lv0, B * tlwe0_words(d.P) * 4);
+    Frame f(d);
+    Io io{f, /*dev*/ false};
+    uint32_t *lv1 = f.ks_input<uint32_t>(B * 1025);
+    int rc = io.out(out_lv0, B * tlwe0_words(d.P) * 4);
+    if (!rc) rc = h2d_copy(d, lv1, in_lv1, B * 1025 * 4);
     if (rc) return rc;
+    in_lv1 = lv1;
     KsGemm G;
-    if ((rc = ks_gemm_args(d, B, G))) return rc;
+    if ((rc = ks_gemm_args(f, B, G))) return rc;
     HIPCHK(d, launch_key_switch(d.K, in_lv1, d.d_ksk, out_lv0, B, d.stream, d.opts, &d.last_ks, &G));
     return io.finish();
 }
@@ -980,9 +980,10 @@ int tfhe_gpu_fft_forward_batch(tfhe_gpu_ctx *c, const uint32_t *in, double *out,
     if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        Io io{d, /*dev*/ false};
-        int rc = io.in(d.s_a, in, B * 1024 * 4);
-        if (!rc) rc = io.out(out, B * 1024 * 8, d.s_tmp);
+        Frame f(d);
+        Io io{f, /*dev*/ false};
+        int rc = io.in(in, B * 1024 * 4);
+        if (!rc) rc = io.out(out, B * 1024 * 8);
         if (rc) return rc;
         HIPCHK(d, launch_fft_forward(tables(d), in, out, B, d.stream));
         return io.finish();
@@ -993,8 +994,9 @@ int tfhe_gpu_fft_inverse_batch(tfhe_gpu_ctx *c, const double *in, uint32_t *out,
     if (!c || (B && (!in || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        Io io{d, /*dev*/ false};
-        int rc = io.in(d.s_tmp, in, B * 1024 * 8);
+        Frame f(d);
+        Io io{f, /*dev*/ false};
+        int rc = io.in(in, B * 1024 * 8);
         if (!rc) rc = io.out(out, B * 1024 * 4);
         if (rc) return rc;
         HIPCHK(d, launch_fft_inverse(tables(d), in, out, B, d.stream));
@@ -1006,9 +1008,10 @@ int tfhe_gpu_poly_mul_batch(tfhe_gpu_ctx *c, const uint32_t *a, const uint32_t *
     if (!c || (B && (!a || !b || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
-        Io io{d, /*dev*/ false};
-        int rc = io.in(d.s_a, a, B * 1024 * 4);
-        if (!rc) rc = io.in(d.s_b, b, B * 1024 * 4);
+        Frame f(d);
+        Io io{f, /*dev*/ false};
+        int rc = io.in(a, B * 1024 * 4);
+        if (!rc) rc = io.in(b, B * 1024 * 4);
         if (!rc) rc = io.out(out, B * 1024 * 4);
         if (rc) return rc;
         HIPCHK(d, launch_poly_mul(tables(d), a, b, 1024, out, B, d.stream));
@@ -1023,21 +1026,22 @@ int tfhe_gpu_external_product_batch(tfhe_gpu_ctx *c, const double *trgsw_fft, ui
     return on_device0(c, [&](Device &d) -> int {
         const size_t row_d = (size_t)2 * d.P.L * 2048;  // doubles per TRGSW
         const double *row = nullptr;
-        Io io{d, /*dev*/ false};
+        Frame f(d);
+        Io io{f, /*dev*/ false};
         int rc = TFHE_OK;
         if (trgsw_fft) {
-            rc = io.in(d.s_tmp, trgsw_fft, row_d * 8);
-            if (!rc) rc = ensure(d, d.s_tv, row_d * 8);
-            if (rc) return rc;
-            HIPCHK(d, launch_bk_permute(d.K, trgsw_fft, d.s_tv.as<double>(), 2 * d.P.L, d.stream));
-            row = d.s_tv.as<const double>();
+            rc = io.in(trgsw_fft, row_d * 8);
+            double *permuted = f.take<double>(row_d);
+            if ((rc = f.rc())) return rc;
+            HIPCHK(d, launch_bk_permute(d.K, trgsw_fft, permuted, 2 * d.P.L, d.stream));
+            row = permuted;
             if (d.K.offset == 0) d.K.offset = decomposition_offset(d.P);  // no key loaded yet: the parameter set's
         } else {
             if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
             if (bk_index >= d.P.n) return fail(d, TFHE_ERR_INVALID, "bk_index >= n");
             row = d.d_bk + (size_t)bk_index * row_d;
         }
-        rc = io.in(d.s_a, in, B * 2048 * 4);
+        rc = io.in(in, B * 2048 * 4);
         if (!rc) rc = io.out(out, B * 2048 * 4);
         if (rc) return rc;
         HIPCHK(d, launch_external_product(d.K, tables(d), row, in, out, B, d.stream));

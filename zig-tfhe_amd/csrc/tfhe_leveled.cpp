@@ -46,15 +46,17 @@ static KParams leveled_params(const Device &d) {
 // in0 / in1 / out: B TRLWELv1 each, host (dev = false: staged, synchronous) or device.
 static int cmux_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *in0, const uint32_t *in1,
                    uint32_t *out, size_t B, bool dev) {
-    Io io{d, dev};
-    int rc = h2d(d, d.s_cidx, sel, B * sizeof(uint32_t));
-    if (!rc) rc = io.in(d.s_a, in0, B * TRLWE_BYTES);
-    if (!rc) rc = io.in(d.s_b, in1, B * TRLWE_BYTES);
-    if (!rc) rc = io.out(out, B * TRLWE_BYTES);
-    if (rc) return rc;
+    Frame f(d);
+    Io io{f, dev};
+    DescBlob blob;
+    blob.add(sel, B);
+    const uint32_t *sel_dev = blob.upload(f);
+    io.in(in0, B * TRLWE_BYTES);
+    io.in(in1, B * TRLWE_BYTES);
+    if (const int rc = io.out(out, B * TRLWE_BYTES)) return rc;
     CmuxBatch b;
     b.sel_rows = set.rows;
-    b.sel = d.s_cidx.as<const uint32_t>();
+    b.sel = sel_dev;
     b.src0 = in0;
     b.src1 = in1;
     b.out = out;
@@ -66,8 +68,8 @@ static int cmux_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel
 
 // The CMUX tree (vertical packing): level j pairs entries 2i, 2i + 1 of level j - 1
 // (level 0: of the table) under address bit j, one launch per level; levels ping-pong
-// between s_lk_a (level 0, 2, ...) and s_lk_b, the last one writes the outputs.
-// Queries go in chunks that keep s_lk_a within LOOKUP_SCRATCH_CAP.  The selector and
+// between two slices (level 0, 2, ... in the larger), the last one writes the outputs.
+// Queries go in chunks that keep the larger slice within LOOKUP_SCRATCH_CAP.  The selector and
 // gather indices of all levels go up once, in one array:
 //   sel[j][q][i] = addr[q k + j]  (i < 2^(k-1-j) pairs of query q at level j), all Q queries;
 //   level 0 reads table entries 2i, 2i + 1 (the table is shared by the queries);
@@ -84,10 +86,12 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
     }
     const size_t l0a_at = words, l0b_at = l0a_at + chunk * cnt0, even_at = l0b_at + chunk * cnt0,
                  odd_at = even_at + chunk * cnt1;
-    std::vector<uint32_t> idx(odd_at + chunk * cnt1);
+    DescBlob blob;
+    blob.reserve(odd_at + chunk * cnt1);
+    uint32_t *idx = blob.words.data();
     for (uint32_t j = 0; j < k; j++) {
         const size_t cnt = cnt0 >> j;
-        uint32_t *s = idx.data() + sel_at[j];
+        uint32_t *s = idx + sel_at[j];
         for (size_t q = 0; q < Q; q++) std::fill(s + q * cnt, s + (q + 1) * cnt, addr[q * k + j]);
     }
     for (size_t g = 0; g < chunk * cnt0; g++) {
@@ -98,15 +102,13 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
         idx[even_at + g] = (uint32_t)(2 * g);
         idx[odd_at + g] = (uint32_t)(2 * g + 1);
     }
-    Io io{d, dev};
-    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): idx may go
-    int rc = h2d(d, d.s_lk_idx, idx.data(), idx.size() * sizeof(uint32_t));
-    if (!rc && k > 1) rc = ensure(d, d.s_lk_a, chunk * cnt0 * TRLWE_BYTES);
-    if (!rc && k > 2) rc = ensure(d, d.s_lk_b, chunk * cnt1 * TRLWE_BYTES);
-    if (!rc) rc = io.in(d.s_a, table, entries * TRLWE_BYTES);
-    if (!rc) rc = io.out(out, Q * TRLWE_BYTES);
-    if (rc) return rc;
-    const uint32_t *didx = d.s_lk_idx.as<const uint32_t>();
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *didx = blob.upload(f);
+    uint32_t *even = k > 1 ? f.take<uint32_t>(chunk * cnt0 * 2048) : nullptr;  // levels 0, 2, ...
+    uint32_t *odd = k > 2 ? f.take<uint32_t>(chunk * cnt1 * 2048) : nullptr;
+    io.in(table, entries * TRLWE_BYTES);
+    if (const int rc = io.out(out, Q * TRLWE_BYTES)) return rc;
     const KParams K = leveled_params(d);
     const DevTables T = tables(d);
     d.last_br = d.last_ks = "";
@@ -121,7 +123,7 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
             b.src0 = b.src1 = prev;
             b.i0 = didx + (j ? even_at : l0a_at);
             b.i1 = didx + (j ? odd_at : l0b_at);
-            b.out = j + 1 == k ? out + q0 * 2048 : (j & 1) ? d.s_lk_b.as<uint32_t>() : d.s_lk_a.as<uint32_t>();
+            b.out = j + 1 == k ? out + q0 * 2048 : (j & 1) ? odd : even;
             b.B = nq * cnt;
             // the workgroup form where 4 consecutive items share their selector (>= 4 pairs per
             // query; cnt is a power of two) unless TFHE_OPT_CMUX_FORM = 1 forces the per-wave form:
@@ -143,20 +145,18 @@ static int table_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint3
 // device pointers but sel / rot / i_src.  The three go up once, in one array.
 static int rotate_launch_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
                             const uint32_t *src, const uint32_t *i_src, uint32_t *out, size_t B, const char **used) {
-    std::vector<uint32_t> idx(B * h + h + (i_src ? B : 0));
-    std::copy(sel, sel + B * h, idx.begin());
-    std::copy(rot, rot + h, idx.begin() + B * h);
-    if (i_src) std::copy(i_src, i_src + B, idx.begin() + B * h + h);
-    const int rc = h2d(d, d.s_rot_idx, idx.data(), idx.size() * sizeof(uint32_t));
-    if (rc) return rc;
-    const uint32_t *didx = d.s_rot_idx.as<const uint32_t>();
+    Frame f(d);
+    DescBlob blob;
+    const size_t sel_at = blob.add(sel, B * h), rot_at = blob.add(rot, h), src_at = blob.add(i_src, i_src ? B : 0);
+    const uint32_t *didx = blob.upload(f);
+    if (f.rc()) return f.rc();
     RotateBatch b;
     b.sel_rows = set.rows;
-    b.sel = didx;
-    b.rot = didx + B * h;
+    b.sel = didx + sel_at;
+    b.rot = didx + rot_at;
     b.h = h;
     b.src = src;
-    b.i_src = i_src ? didx + B * h + h : nullptr;
+    b.i_src = i_src ? didx + src_at : nullptr;
     b.out = out;
     b.B = B;
     HIPCHK(d, launch_rotate_chain(leveled_params(d), tables(d), b, d.stream, used));
@@ -165,8 +165,9 @@ static int rotate_launch_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint
 
 static int rotate_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *sel, const uint32_t *rot, uint32_t h,
                      const uint32_t *in, uint32_t *out, size_t B, bool dev) {
-    Io io{d, dev};
-    int rc = io.in(d.s_a, in, B * TRLWE_BYTES);
+    Frame f(d);
+    Io io{f, dev};
+    int rc = io.in(in, B * TRLWE_BYTES);
     if (!rc) rc = io.out(out, B * TRLWE_BYTES);
     if (rc) return rc;
     d.last_ks = "";
@@ -175,29 +176,30 @@ static int rotate_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *s
 }
 
 // The packed lookup (tfhe_packed_lookup_plan): the CMUX tree over the 2^v table TRLWEs under address
-// bits h .. k - 1 (table_lookup_on, into context scratch), then one k_rotate_chain launch under bits
+// bits h .. k - 1 (table_lookup_on, into a slice of this call's frame), then one k_rotate_chain launch under bits
 // 0 .. h - 1.  v = 0: every query's chain starts from table TRLWE 0; h = 0 (an entry fills a TRLWE):
 // the tree alone.
 static int packed_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
                             const tfhe_packed_plan &pl, const uint32_t *table, uint32_t *out, size_t Q, bool dev) {
     const uint32_t h = pl.h, v = pl.v;
-    Io io{d, dev};
-    int rc = io.in(d.s_a, table, (size_t)pl.trlwes * TRLWE_BYTES);
+    Frame f(d);
+    Io io{f, dev};
+    int rc = io.in(table, (size_t)pl.trlwes * TRLWE_BYTES);
     if (!rc) rc = io.out(out, Q * TRLWE_BYTES);
-    if (!rc && v && h) rc = ensure(d, d.s_rot_in, Q * TRLWE_BYTES);
-    if (rc) return rc;
+    uint32_t *tree_out = v && h ? f.take<uint32_t>(Q * 2048) : out;
+    if ((rc = f.rc())) return rc;
     d.last_br = d.last_ks = "";
     if (v) {  // the table is on the device by now, staged or the caller's
         std::vector<uint32_t> hi(Q * v);
         for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.begin() + q * v);
-        rc = table_lookup_on(d, set, hi.data(), v, table, h ? d.s_rot_in.as<uint32_t>() : out, Q, /*dev*/ true);
+        rc = table_lookup_on(d, set, hi.data(), v, table, tree_out, Q, /*dev*/ true);
         if (rc) return rc;
     }
     if (h) {
         std::vector<uint32_t> lo(Q * h), first(v ? 0 : Q, 0u);
         for (size_t q = 0; q < Q; q++) std::copy(addr + q * k, addr + q * k + h, lo.begin() + q * h);
         // last_kernels: the tree's first level, then the chain
-        rc = rotate_launch_on(d, set, lo.data(), pl.rot, h, v ? d.s_rot_in.as<const uint32_t>() : table,
+        rc = rotate_launch_on(d, set, lo.data(), pl.rot, h, v ? tree_out : table,
                               v ? nullptr : first.data(), out, Q, v ? &d.last_ks : &d.last_br);
         if (rc) return rc;
     }
@@ -205,10 +207,10 @@ static int packed_lookup_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint
 }
 
 // The packed scatter-add (include/tfhe_gpu.h): one k_rotate_chain launch over all Q deltas under address bits
-// 0 .. h - 1 (rot[j] = stride << j, into context scratch), then per chunk of queries the demux tree under bits
+// 0 .. h - 1 (rot[j] = stride << j, into a slice of the call's frame), then per chunk of queries the demux tree under bits
 // k - 1 .. h, one launch per level, and one k_scatter_reduce that adds the chunk's leaves into the table.  Level l
-// (2^l parents per query) writes s_sc_a when v - 1 - l is even, so the leaves (2^v TRLWELv1 per query) end up in
-// s_sc_a and s_sc_b holds at most half as much; a chunk is as many queries as keep the leaves within
+// (2^l parents per query) writes the larger of two slices when v - 1 - l is even, so the leaves (2^v TRLWELv1 per query) end up
+// there and the other holds at most half as much; a chunk is as many queries as keep the leaves within
 // TFHE_OPT_SCATTER_SCRATCH_MB.  v = 0: the rotation's outputs (h = 0 as well: the deltas) are the leaves.
 // The address bits h .. k - 1 of all queries go up once; a level's parents find their selector in them.
 static int packed_scatter_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, uint32_t k,
@@ -216,35 +218,28 @@ static int packed_scatter_on(Device &d, const tfhe_gpu_trgsw_set &set, const uin
     const uint32_t h = pl.h, v = pl.v;
     const size_t leaves = (size_t)1 << v;
     const size_t chunk = std::min(Q, std::max<size_t>(1, ((size_t)d.scatter_scratch_mb << 20) / (leaves * TRLWE_BYTES)));
-    Io io{d, dev};
-    const uint32_t *staged = table;
-    int rc = io.in(d.s_a, staged, leaves * TRLWE_BYTES);
-    if (!dev) {  // the table is this call's output as well: finish() copies the scratch copy back
-        io.host_out = table;
-        io.staged_out = staged;
-        io.out_bytes = leaves * TRLWE_BYTES;
-        table = d.s_a.as<uint32_t>();
-    }
-    if (!rc) rc = io.in(d.s_b, delta, Q * TRLWE_BYTES);
-    if (!rc && h) rc = ensure(d, d.s_rot_in, Q * TRLWE_BYTES);
-    if (!rc && v) rc = ensure(d, d.s_sc_a, chunk * leaves * TRLWE_BYTES);
-    if (!rc && v > 1) rc = ensure(d, d.s_sc_b, chunk * (leaves / 2) * TRLWE_BYTES);
-    if (rc) return rc;
+    Frame f(d);
+    Io io{f, dev};
+    int rc = io.inout(table, leaves * TRLWE_BYTES);  // the table is this call's output as well
+    if (!rc) rc = io.in(delta, Q * TRLWE_BYTES);
+    uint32_t *rotated = h ? f.take<uint32_t>(Q * 2048) : nullptr;
+    uint32_t *big = v ? f.take<uint32_t>(chunk * leaves * 2048) : nullptr;
+    uint32_t *small = v > 1 ? f.take<uint32_t>(chunk * (leaves / 2) * 2048) : nullptr;
+    if ((rc = f.rc())) return rc;
     d.last_br = d.last_ks = "";
     if (h) {
         std::vector<uint32_t> lo(Q * h), rot(h);
         for (size_t q = 0; q < Q; q++) std::copy(addr + q * k, addr + q * k + h, lo.begin() + q * h);
         for (uint32_t j = 0; j < h; j++) rot[j] = pl.stride << j;
-        rc = rotate_launch_on(d, set, lo.data(), rot.data(), h, delta, nullptr, d.s_rot_in.as<uint32_t>(), Q, &d.last_br);
+        rc = rotate_launch_on(d, set, lo.data(), rot.data(), h, delta, nullptr, rotated, Q, &d.last_br);
         if (rc) return rc;
-        delta = d.s_rot_in.as<const uint32_t>();
+        delta = rotated;
     }
-    if (v) {
-        std::vector<uint32_t> hi(Q * v);
-        for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.begin() + q * v);
-        if ((rc = h2d(d, d.s_sc_idx, hi.data(), hi.size() * sizeof(uint32_t)))) return rc;
-    }
-    const uint32_t *bits = d.s_sc_idx.as<const uint32_t>();
+    DescBlob hi;  // address bits h .. k - 1 of every query, uploaded behind the rotation's launch
+    hi.reserve(Q * v);
+    for (size_t q = 0; q < Q; q++) std::copy(addr + q * k + h, addr + (q + 1) * k, hi.words.begin() + q * v);
+    const uint32_t *bits = hi.upload(f);
+    if ((rc = f.rc())) return rc;
     const KParams K = leveled_params(d);
     const DevTables T = tables(d);
     for (size_t q0 = 0; q0 < Q; q0 += chunk) {
@@ -257,7 +252,7 @@ static int packed_scatter_on(Device &d, const tfhe_gpu_trgsw_set &set, const uin
             b.level = l;
             b.sel_stride = v;
             b.src = prev;
-            b.out = ((v - 1 - l) & 1) ? d.s_sc_b.as<uint32_t>() : d.s_sc_a.as<uint32_t>();
+            b.out = ((v - 1 - l) & 1) ? small : big;
             b.B = nq << l;
             // the workgroup form where a query has at least 4 parents, as in table_lookup_on
             const bool shared = d.opts.cmux_form != 1 && ((size_t)1 << l) >= CMUX_SHARED_ITEMS;
@@ -277,17 +272,19 @@ static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *c
     if (key_switch && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t items = B * C, wo = key_switch ? tlwe0_words(d.P) : (size_t)d.P.N + 1;
     if (items == 0) return TFHE_OK;
-    Io io{d, dev};
-    int rc = h2d(d, d.s_cidx, coef, C * sizeof(uint32_t));
-    if (!rc) rc = io.in(d.s_a, trlwe, B * TRLWE_BYTES);
-    if (!rc) rc = io.out(out, items * wo * 4);
-    if (!rc && key_switch) rc = ensure(d, d.s_lv1, items * 1025 * 4 + KS_GEMM_INPUT_SLACK);
-    if (rc) return rc;
-    uint32_t *lv1 = key_switch ? d.s_lv1.as<uint32_t>() : out;
-    HIPCHK(d, launch_sample_extract(trlwe, d.s_cidx.as<const uint32_t>(), C, lv1, B, d.stream));
+    Frame f(d);
+    Io io{f, dev};
+    DescBlob blob;
+    blob.add(coef, C);
+    const uint32_t *coef_dev = blob.upload(f);
+    io.in(trlwe, B * TRLWE_BYTES);
+    int rc = io.out(out, items * wo * 4);
+    uint32_t *lv1 = key_switch ? f.ks_input<uint32_t>(items * 1025) : out;
+    if ((rc = f.rc())) return rc;
+    HIPCHK(d, launch_sample_extract(trlwe, coef_dev, C, lv1, B, d.stream));
     if (key_switch) {
         KsGemm G;
-        if ((rc = ks_gemm_args(d, items, G))) return rc;
+        if ((rc = ks_gemm_args(f, items, G))) return rc;
         HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, items, d.stream, d.opts, &d.last_ks, &G));
     }
     return io.finish();
@@ -306,11 +303,12 @@ int tfhe_gpu_trgsw_set_load(tfhe_gpu_ctx *c, const double *trgsw_fft, size_t S, 
     set->S = S;
     const int rc = on_device0(c, [&](Device &d) -> int {
         const size_t rows = S * 2 * d.P.L, bytes = rows * 2048 * sizeof(double);
-        int rc = h2d(d, d.s_tmp, trgsw_fft, bytes);
-        if (rc) return rc;
+        Frame f(d);
+        const double *staged = f.h2d(trgsw_fft, bytes);
+        if (f.rc()) return f.rc();
         if (hipMalloc((void **)set->rows.make(d.device), bytes) != hipSuccess)
             return fail(d, TFHE_ERR_OOM, "hipMalloc(selector set)");
-        HIPCHK(d, launch_bk_permute(d.K, d.s_tmp.as<const double>(), set->rows, rows, d.stream));
+        HIPCHK(d, launch_bk_permute(d.K, staged, set->rows, rows, d.stream));
         HIPCHK(d, hipStreamSynchronize(d.stream));
         return TFHE_OK;
     });

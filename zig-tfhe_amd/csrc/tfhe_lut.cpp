@@ -31,18 +31,6 @@ struct tfhe_gpu_lut_set {
 
 namespace tfhe {
 
-// Descriptor arrays of one call, concatenated into one upload (u32 words; the
-// coefficients keep their bits): where each starts in the device copy.
-struct DescBlob {
-    std::vector<uint32_t> words;
-    size_t add(const void *p, size_t count) {
-        const size_t at = words.size();
-        words.resize(at + count);
-        if (count) std::memcpy(words.data() + at, p, count * sizeof(uint32_t));
-        return at;
-    }
-};
-
 // B nodes over a pool of P ciphertexts (checked descriptors).  dev: pool and out are
 // device pointers, and the call returns without waiting.
 static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, size_t P, const uint32_t *term_off,
@@ -53,15 +41,13 @@ static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *
     DescBlob blob;
     const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
                  coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B);
-    Io io{d, dev};
-    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
-    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
-    if (!rc && terms) rc = io.in(d.s_a, pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
-    if (!rc) rc = io.out(out, B * w * 4);
-    if (!rc) rc = ensure(d, d.s_lut_x, B * w * 4);
-    if (rc) return rc;
-    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
-    uint32_t *x = d.s_lut_x.as<uint32_t>();
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *desc = blob.upload(f);
+    if (terms) io.in(pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
+    int rc = io.out(out, B * w * 4);
+    uint32_t *x = f.take<uint32_t>(B * w);  // the combined ciphertexts, the bootstrap's inputs
+    if ((rc = f.rc())) return rc;
     HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
                                  desc + konst_at, x, B, d.stream));
     rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, out, B, RUN_BOOTSTRAP, nullptr, desc + lut_at);
@@ -70,21 +56,22 @@ static int lut_apply_on(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *
 
 // The multi-output form of a launch of B nodes with M >= B outputs: x (rounded per node by shift[])
 // -> one accumulator per node -> the M extractions fan[] names -> one key switch into out
-// (M TLWELv0).  desc pointers are device copies; the caller has ensured s_lut_x.
+// (M TLWELv0).  desc pointers are device copies.  x, the accumulators and the extractions are the launch's own.
 static int lut_multi_launch(Device &d, const tfhe_gpu_lut_set &set, const uint32_t *pool, const uint32_t *off,
                             const uint32_t *src, const int32_t *coef, const uint32_t *konst, const uint32_t *lut,
                             const uint32_t *shift, const uint32_t *fan, uint32_t *out, size_t B, size_t M) {
-    int rc = ensure(d, d.s_lut_acc, B * 2 * (size_t)d.P.N * sizeof(uint32_t));
-    if (!rc) rc = ensure(d, d.s_lv1, M * 1025 * 4 + KS_GEMM_INPUT_SLACK);
+    Frame f(d);
+    uint32_t *x = f.take<uint32_t>(B * tlwe0_words(d.P)), *acc = f.take<uint32_t>(B * 2 * (size_t)d.P.N);
+    uint32_t *lv1 = f.ks_input<uint32_t>(M * 1025);
+    int rc = f.rc();
     if (rc) return rc;
-    uint32_t *x = d.s_lut_x.as<uint32_t>(), *acc = d.s_lut_acc.as<uint32_t>(), *lv1 = d.s_lv1.as<uint32_t>();
     HIPCHK(d, launch_lut_combine_round(d.K, pool, off, src, coef, konst, shift, x, B, d.stream));
     const size_t ev_at = d.ev_used;
     if ((rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, acc, B, RUN_TRLWE, nullptr, lut))) return rc;
     const char *fan_name = "";
     HIPCHK(d, launch_lut_fanout_extract(acc, fan, lv1, M, d.stream, &fan_name));
     KsGemm G;
-    if ((rc = ks_gemm_args(d, M, G))) return rc;
+    if ((rc = ks_gemm_args(f, M, G))) return rc;
     HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, M, d.stream, d.opts, &d.last_ks, &G));
     // last_kernels: the blind rotation, then the fan-out extraction and the key switch
     d.lut_multi_ks = std::string(fan_name) + " + " + d.last_ks;
@@ -117,26 +104,23 @@ static int lut_apply_multi_on(Device &d, const tfhe_gpu_lut_set &set, const uint
     const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
                  coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B),
                  shift_at = blob.add(shift.data(), B), fan_at = blob.add(fan.data(), fan.size());
-    Io io{d, dev};
-    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
-    if (!rc && terms) rc = io.in(d.s_a, pool, P * w * 4);
-    if (!rc) rc = io.out(out, M * w * 4);
-    if (!rc) rc = ensure(d, d.s_lut_x, B * w * 4);
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *desc = blob.upload(f);
+    if (terms) io.in(pool, P * w * 4);
+    int rc = io.out(out, M * w * 4);
     if (rc) return rc;
-    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
     rc = lut_multi_launch(d, set, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
                           desc + konst_at, desc + lut_at, desc + shift_at, desc + fan_at, out, B, M);
     return rc ? rc : io.finish();
 }
 
 // A whole LUT circuit: one combine and one bootstrap launch per level into the
-// wire table (d.s_wires, in the plan's slot order), the outputs gathered at the end.
+// wire table (in the plan's slot order), the outputs gathered at the end; a level's temporaries go with its frame.
 static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
                           const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev) {
     if (n_nodes && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t w = tlwe0_words(d.P), W = pl.slot.size();  // inputs + every node's outputs
-    size_t widest = 0;
-    for (uint32_t lv = 1; lv <= pl.depth; lv++) widest = std::max<size_t>(widest, pl.first[lv] - pl.first[lv - 1]);
     // multi-output nodes anywhere: round_theta's shift per node (evaluation order) and the plan's fan-out pairs
     const bool multi = std::any_of(pl.theta.begin(), pl.theta.end(), [](uint32_t t) { return t != 0; });
     std::vector<uint32_t> shift;
@@ -148,24 +132,15 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
                  lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs),
                  shift_at = blob.add(shift.data(), shift.size()),
                  fan_at = multi ? blob.add(pl.fan.data(), pl.fan.size()) : 0;
-    Io io{d, dev};
-    int rc = ensure(d, d.s_wires, std::max<size_t>(W, 1) * w * 4);
-    // hipMemcpyAsync stages a pageable source before it returns (upload_plan): blob may go
-    if (!rc && !blob.words.empty()) rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
-    if (!rc) rc = ensure(d, d.s_lut_x, std::max<size_t>(widest, 1) * w * 4);
-    if (!rc && multi) {  // the widest level's accumulators and extractions now: no level grows them mid-circuit
-        size_t widest_out = 0;
-        for (uint32_t lv = 1; lv <= pl.depth; lv++) widest_out = std::max<size_t>(widest_out, pl.ofirst[lv] - pl.ofirst[lv - 1]);
-        rc = ensure(d, d.s_lut_acc, widest * 2 * (size_t)d.P.N * sizeof(uint32_t));
-        if (!rc) rc = ensure(d, d.s_lv1, widest_out * 1025 * 4 + KS_GEMM_INPUT_SLACK);
-    }
-    if (!rc && n_outputs) rc = io.out(outputs, n_outputs * w * 4);
+    Frame f(d);
+    Io io{f, dev};
+    uint32_t *wires = f.take<uint32_t>(W * w);
+    const uint32_t *desc = blob.upload(f);
+    int rc = n_outputs ? io.out(outputs, n_outputs * w * 4) : f.rc();
     if (rc) return rc;
     if (n_inputs)
-        HIPCHK(d, hipMemcpyAsync(d.s_wires.p, inputs, n_inputs * w * 4,
-                                 dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, d.stream));
-    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
-    uint32_t *wires = d.s_wires.as<uint32_t>(), *x = d.s_lut_x.as<uint32_t>();
+        HIPCHK(d, hipMemcpyAsync(wires, inputs, n_inputs * w * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                 d.stream));
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
         const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at, oat = pl.ofirst[lv - 1], no = pl.ofirst[lv] - oat;
         uint32_t *level_out = wires + (n_inputs + oat) * w;  // the level's outputs: one run of slots
@@ -176,7 +151,10 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
             if (rc) return rc;
             continue;
         }
-        // reads slots below this level's first (earlier wires), writes the staging buffer
+        // reads slots below this level's first (earlier wires), writes the level's staging slice
+        Frame level(d);
+        uint32_t *x = level.take<uint32_t>(nb * w);
+        if ((rc = level.rc())) return rc;
         HIPCHK(d, launch_lut_combine(d.K, wires, desc + off_at + at + (lv - 1), desc + src_at,
                                      reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at, x, nb,
                                      d.stream));
@@ -243,8 +221,9 @@ static int spread_entry(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_
     if (B == 0) return TFHE_OK;
     return on_device0(c, [&](Device &d) -> int {
         const size_t bytes = B * 2 * (size_t)d.P.N * sizeof(uint32_t);
-        Io io{d, dev};
-        int rc = io.in(d.s_tv, in, bytes);
+        Frame f(d);
+        Io io{f, dev};
+        int rc = io.in(in, bytes);
         if (!rc) rc = io.out(out, bytes);
         if (rc) return rc;
         d.last_br = d.last_ks = "";
@@ -270,14 +249,14 @@ static int each_entry(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testv
         const size_t w = tlwe0_words(d.P);
         DescBlob blob;
         add_iota(blob, B);
-        Io io{d, dev};
-        int rc = h2d(d, d.s_cidx, blob.words.data(), B * sizeof(uint32_t));
-        if (!rc) rc = io.in(d.s_a, in, B * w * 4);
-        if (!rc) rc = io.in(d.s_tv, testvecs, B * 2 * (size_t)d.P.N * sizeof(uint32_t));
-        if (!rc) rc = io.out(out, B * w * 4);
+        Frame f(d);
+        Io io{f, dev};
+        const uint32_t *iota = blob.upload(f);
+        io.in(in, B * w * 4);
+        io.in(testvecs, B * 2 * (size_t)d.P.N * sizeof(uint32_t));
+        int rc = io.out(out, B * w * 4);
         if (rc) return rc;
-        rc = run_bootstrap_dev(d, nullptr, in, nullptr, testvecs, out, B, RUN_BOOTSTRAP, nullptr,
-                               d.s_cidx.as<const uint32_t>());
+        rc = run_bootstrap_dev(d, nullptr, in, nullptr, testvecs, out, B, RUN_BOOTSTRAP, nullptr, iota);
         return rc ? rc : io.finish();
     });
 }
@@ -301,20 +280,19 @@ static int lut_apply2_on(Device &d, const tfhe_gpu_lut_set &set, const tfhe_gpu_
     for (uint32_t i = 0; i < m; i++) coef[i] = i * slot;
     DescBlob blob;
     const size_t iota_at = add_iota(blob, items + 1), src1_at = blob.add(src1.data(), items),
-                 lut1_at = blob.add(lut1.data(), items), ones_at = blob.add(ones.data(), items),
-                 zeros_at = blob.add(zeros.data(), items), src2_at = blob.add(x_src, B), coef_at = blob.add(coef.data(), m);
-    Io io{d, dev};
-    int rc = h2d(d, d.s_cidx, blob.words.data(), blob.words.size() * sizeof(uint32_t));
-    if (!rc) rc = io.in(d.s_a, pool, P * w * 4);
-    if (!rc) rc = io.out(out, B * w * 4);
-    if (!rc) rc = ensure(d, d.s_lut_x, nodes * m * w * 4);
-    if (!rc) rc = ensure(d, d.s_b, nodes * m * w * 4 + 2 * KS_GEMM_INPUT_SLACK);  // the pack's inputs: its GEMM's slack
-    if (!rc) rc = ensure(d, d.s_lut_acc, nodes * 2 * N * sizeof(uint32_t));
-    if (rc) return rc;
-    const uint32_t *desc = d.s_cidx.as<const uint32_t>();
-    const uint32_t *iota = desc + iota_at, *zeros_d = desc + zeros_at;
-    const int32_t *ones_d = reinterpret_cast<const int32_t *>(desc + ones_at);
-    uint32_t *x = d.s_lut_x.as<uint32_t>(), *g = d.s_b.as<uint32_t>(), *tv = d.s_lut_acc.as<uint32_t>();
+                 lut1_at = blob.add(lut1.data(), items), one_at = blob.add(ones.data(), items),
+                 zero_at = blob.add(zeros.data(), items), src2_at = blob.add(x_src, B), coef_at = blob.add(coef.data(), m);
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *desc = blob.upload(f);
+    io.in(pool, P * w * 4);
+    int rc = io.out(out, B * w * 4);
+    // a chunk's combined ciphertexts, level 1's outputs (the pack's inputs) and test vectors: every chunk's alike
+    uint32_t *x = f.take<uint32_t>(nodes * m * w), *g = f.ks_input<uint32_t>(nodes * m * w, /*pack*/ true);
+    uint32_t *tv = f.take<uint32_t>(nodes * 2 * N);
+    if ((rc = f.rc())) return rc;
+    const uint32_t *iota = desc + iota_at, *zeros_d = desc + zero_at;
+    const int32_t *ones_d = reinterpret_cast<const int32_t *>(desc + one_at);
     for (size_t b0 = 0; b0 < B; b0 += nodes) {
         const size_t nb = std::min(nodes, B - b0), ni = nb * m;
         // term_off = iota from 0 with src advanced to the chunk: item k of the chunk has the one term k

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <deque>
 #include <mutex>
 
 #include "tfhe_ctx.hpp"
@@ -189,18 +190,22 @@ static bool split_by_levels(const tfhe_gpu_ctx *c, size_t n_gates, const uint8_t
 // of the level's gates into its table; each slice is then copied to every other
 // device (peer copies over xGMI, ordered by an event on the producer's stream:
 // an all-gather), and every device applies the level's NOTs itself.  Outputs
-// come from the first device's table.
+// come from the first device's table.  Every device's frame stays open for the
+// whole call: the wire tables are the peer copies' sources and targets.
 static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t *inputs, size_t n_gates,
                                const uint8_t *ops, const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs,
-                               const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels_out) {
+                               const uint32_t *out_wires, uint32_t *outputs, uint32_t *depth_out) {
     const size_t W = n_inputs + n_gates, D = c->dev.size(), w1 = tlwe0_words(c->P);
     CircuitPlan pl;
     if (const char *why = plan_circuit(n_inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires,
                                        c->dev[0].circuit_pack != 0, device_cus() * D, level_cost, pl))
         return fail(c, TFHE_ERR_INVALID, why);
+    std::deque<Frame> frames;  // one per device
+    std::vector<PlanBufs> pb(D);
     for (size_t d = 0; d < D; d++) {
         Device &s = c->dev[d];
-        int rc = upload_plan(s, pl, W, n_inputs, inputs, n_outputs);
+        frames.emplace_back(s);
+        int rc = upload_plan(frames[d], pl, W, n_inputs, inputs, pb[d]);
         if (!rc && !s.level_ev && hipEventCreateWithFlags(s.level_ev.make(s.device), hipEventDisableTiming) != hipSuccess)
             rc = fail(s, TFHE_ERR_HIP, "hipEventCreate");
         if (rc) return lift(c, d, rc);
@@ -218,14 +223,14 @@ static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t 
                 const Slice sl = slice_of(nb, D, d);
                 if (!sl.n) continue;
                 if (hipSetDevice(s.device) != hipSuccess) return fail(c, TFHE_ERR_HIP, "hipSetDevice");
-                uint32_t *wires = s.s_wires.as<uint32_t>();
-                int rc = run_bootstrap_dev(s, s.s_cops.as<const uint8_t>() + op_pos + sl.lo, wires, wires, nullptr,
-                                           wires + (sp + sl.lo) * w1, sl.n, RUN_BOOTSTRAP,
-                                           s.s_cidx.as<const uint32_t>() + ip + 2 * sl.lo);
+                uint32_t *wires = pb[d].wires;
+                int rc = run_bootstrap_dev(s, pb[d].ops + op_pos + sl.lo, wires, wires, nullptr, wires + (sp + sl.lo) * w1,
+                                           sl.n, RUN_BOOTSTRAP, pb[d].idx + ip + 2 * sl.lo);
                 if (!rc && hipEventRecord(s.level_ev, s.stream) != hipSuccess) rc = fail(s, TFHE_ERR_HIP, "hipEventRecord");
                 if (rc) return lift(c, d, rc);
             }
-            for (Device &t : c->dev) {  // all-gather of the level's outputs
+            for (size_t to = 0; to < D; to++) {  // all-gather of the level's outputs
+                Device &t = c->dev[to];
                 if (hipSetDevice(t.device) != hipSuccess) return fail(c, TFHE_ERR_HIP, "hipSetDevice");
                 for (size_t d = 0; d < D; d++) {
                     Device &s = c->dev[d];
@@ -233,8 +238,8 @@ static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t 
                     if (&s == &t || !sl.n) continue;
                     const size_t off = (sp + sl.lo) * w1;
                     if (hipStreamWaitEvent(t.stream, s.level_ev, 0) != hipSuccess ||
-                        hipMemcpyPeerAsync(t.s_wires.as<uint32_t>() + off, t.device, s.s_wires.as<const uint32_t>() + off,
-                                           s.device, sl.n * w1 * 4, t.stream) != hipSuccess)
+                        hipMemcpyPeerAsync(pb[to].wires + off, t.device, pb[d].wires + off, s.device, sl.n * w1 * 4,
+                                           t.stream) != hipSuccess)
                         return fail(c, TFHE_ERR_HIP, "level all-gather to device " + std::to_string(t.device));
                 }
             }
@@ -243,11 +248,11 @@ static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t 
             sp += nb;
         }
         if (nn) {
-            for (Device &s : c->dev) {  // every device negates the level's NOT inputs itself
-                uint32_t *wires = s.s_wires.as<uint32_t>();
+            for (size_t d = 0; d < D; d++) {  // every device negates the level's NOT inputs itself
+                Device &s = c->dev[d];
+                uint32_t *wires = pb[d].wires;
                 if (hipSetDevice(s.device) != hipSuccess ||
-                    launch_tlwe_gather(s.K, wires, s.s_cidx.as<const uint32_t>() + ip, wires + sp * w1, nn, true,
-                                       s.stream) != hipSuccess)
+                    launch_tlwe_gather(s.K, wires, pb[d].idx + ip, wires + sp * w1, nn, true, s.stream) != hipSuccess)
                     return fail(c, TFHE_ERR_HIP, "NOT gather on device " + std::to_string(s.device));
             }
             ip += nn;
@@ -258,15 +263,16 @@ static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t 
     // every device's work done and its error word clean; device 0 last, whose wait brings the outputs
     for (size_t d = D; d-- > 0;) {
         Device &s = c->dev[d];
-        const bool out = d == 0 && n_outputs;
+        Io io{frames[d], /*dev*/ false};
         if (hipSetDevice(s.device) != hipSuccess) return fail(c, TFHE_ERR_HIP, "hipSetDevice");
-        if (out && launch_tlwe_gather(s.K, s.s_wires.as<const uint32_t>(), s.s_cidx.as<const uint32_t>() + ip,
-                                      s.s_out.as<uint32_t>(), n_outputs, false, s.stream) != hipSuccess)
-            return fail(c, TFHE_ERR_HIP, "output gather");
-        const int rc = out ? d2h_sync(s, outputs, s.s_out.p, n_outputs * w1 * 4) : sync_check(s);
-        if (rc) return lift(c, d, rc);
+        if (d == 0 && n_outputs) {
+            if (const int rc = io.out(outputs, n_outputs * w1 * 4)) return lift(c, d, rc);
+            if (launch_tlwe_gather(s.K, pb[d].wires, pb[d].idx + ip, outputs, n_outputs, false, s.stream) != hipSuccess)
+                return fail(c, TFHE_ERR_HIP, "output gather");
+        }
+        if (const int rc = io.finish()) return lift(c, d, rc);
     }
-    if (levels_out) *levels_out = pl.max_level;
+    if (depth_out) *depth_out = pl.max_level;
     return TFHE_OK;
 }
 
@@ -281,7 +287,7 @@ static int circuit_eval_levels(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t 
 // (examples/add_two_numbers.zig:24-73) stays whole.
 int circuit_eval_multi(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t *inputs, size_t n_gates, const uint8_t *ops,
                        const uint32_t *in_a, const uint32_t *in_b, size_t n_outputs, const uint32_t *out_wires,
-                       uint32_t *outputs, uint32_t *levels_out) {
+                       uint32_t *outputs, uint32_t *depth_out) {
     if (!c->dev[0].has_key) return fail(c, TFHE_ERR_NO_KEY, "no cloud key loaded");
     if (n_inputs + n_gates > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "too many wires");
     const size_t D = c->dev.size(), w1 = tlwe0_words(c->P);
@@ -291,7 +297,7 @@ int circuit_eval_multi(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t *inputs,
     std::vector<uint32_t> dev_of_gate;
     partition_gates(n_inputs, n_gates, ops, in_a, in_b, D, dev_of_gate);
     if (split_by_levels(c, n_gates, ops, dev_of_gate))
-        return circuit_eval_levels(c, n_inputs, inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires, outputs, levels_out);
+        return circuit_eval_levels(c, n_inputs, inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires, outputs, depth_out);
     const std::vector<SubCircuit> sub = split_circuit(n_inputs, n_gates, ops, in_a, in_b, n_outputs, out_wires, dev_of_gate, D);
     std::vector<std::vector<uint32_t>> sub_out(D);
     std::vector<uint32_t> sub_levels(D, 0);
@@ -310,7 +316,7 @@ int circuit_eval_multi(tfhe_gpu_ctx *c, size_t n_inputs, const uint32_t *inputs,
     for (size_t d = 0; d < D; d++)
         for (size_t k = 0; k < sub[d].out_index.size(); k++)
             std::memcpy(outputs + (size_t)sub[d].out_index[k] * w1, sub_out[d].data() + k * w1, w1 * 4);
-    if (levels_out) *levels_out = *std::max_element(sub_levels.begin(), sub_levels.end());
+    if (depth_out) *depth_out = *std::max_element(sub_levels.begin(), sub_levels.end());
     return TFHE_OK;
 }
 

@@ -32,10 +32,11 @@ int pack_launch(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *x0, 
     const size_t items = B * C, w = tlwe0_words(d.P);
     const int basebit = (int)key.basebit, t = (int)key.t;
     const size_t chunk = pack_chunk_items(d, items, basebit);
-    if (const int rc = ensure(d, d.s_kspart, pack_gemm_part_bytes(d.K, chunk, basebit))) return rc;
+    Frame f(d);  // the K splits' sums, every chunk's in the same slice
     KsGemm G;
     G.kg = key.key_gemm;
-    G.part = d.s_kspart.as<uint32_t>();
+    G.part = static_cast<uint32_t *>(f.bytes(pack_gemm_part_bytes(d.K, chunk, basebit)));
+    if (f.rc()) return f.rc();
     d.last_br = d.last_ks = "";
     for (size_t item0 = 0; item0 < items; item0 += chunk) {
         const size_t M = std::min(chunk, items - item0);
@@ -54,15 +55,18 @@ int pack_launch(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *x0, 
 static int pack_on(Device &d, const tfhe_gpu_packing_key &key, const uint32_t *in, const uint32_t *coef, size_t C,
                    uint32_t *out, size_t B, bool dev) {
     const size_t in_bytes = B * C * tlwe0_words(d.P) * sizeof(uint32_t);
-    Io io{d, dev};
+    Frame f(d);
+    Io io{f, dev};
     // the last block of 8 coefficients may reach 6 words past the last row's n + 1 (n = 8q + 1)
-    int rc = ensure(d, d.s_a, in_bytes + 2 * KS_GEMM_INPUT_SLACK);
-    if (!rc) rc = io.out(out, B * 2 * d.P.N * sizeof(uint32_t));
-    if (!rc) rc = h2d(d, d.s_cidx, coef, C * sizeof(uint32_t));
+    uint32_t *x = f.ks_input<uint32_t>(in_bytes / sizeof(uint32_t), /*pack*/ true);
+    DescBlob blob;
+    blob.add(coef, C);
+    const uint32_t *coef_dev = blob.upload(f);
+    int rc = io.out(out, B * 2 * d.P.N * sizeof(uint32_t));
     if (rc) return rc;
-    if (dev) HIPCHK(d, hipMemcpyAsync(d.s_a.p, in, in_bytes, hipMemcpyDeviceToDevice, d.stream));
-    else if ((rc = h2d(d, d.s_a, in, in_bytes))) return rc;
-    rc = pack_launch(d, key, d.s_a.as<const uint32_t>(), d.s_cidx.as<const uint32_t>(), C, out, B);
+    if (dev) HIPCHK(d, hipMemcpyAsync(x, in, in_bytes, hipMemcpyDeviceToDevice, d.stream));
+    else if ((rc = h2d_copy(d, x, in, in_bytes))) return rc;
+    rc = pack_launch(d, key, x, coef_dev, C, out, B);
     return rc ? rc : io.finish();
 }
 
