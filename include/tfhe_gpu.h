@@ -42,7 +42,8 @@ extern "C" {
                                    tfhe_gpu_lut_circuit_eval_multi*, tfhe_lut_circuit_schedule_multi) and the
                                    packed scatter-add (tfhe_gpu_packed_scatter_add_*, TFHE_OPT_SCATTER_SCRATCH_MB)
                                    and the bivariate LUT bootstrap (tfhe_lut_spread, tfhe_gpu_lut_spread_*,
-                                   tfhe_gpu_bootstrap_lut_each_*, tfhe_gpu_lut_apply2_*);
+                                   tfhe_gpu_bootstrap_lut_each_*, tfhe_gpu_lut_apply2_*) and the CMUX graphs
+                                   (tfhe_cmux_graph_plan, tfhe_gpu_cmux_graph_*, TFHE_OPT_GRAPH_CHUNK_QUERIES);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -232,10 +233,14 @@ enum {
     TFHE_OPT_PACK_SCRATCH_MB = 19,/* packing key switch: bound in MB on the context scratch that holds a chunk's
                                      GEMM sums, 1..256 (default 256).  Same words at any value; tests lower it to
                                      run a small batch in several chunks */
-    TFHE_OPT_SCATTER_SCRATCH_MB = 20 /* packed scatter-add: bound in MB on the context scratch that holds a chunk's
+    TFHE_OPT_SCATTER_SCRATCH_MB = 20,/* packed scatter-add: bound in MB on the context scratch that holds a chunk's
                                      leaves, 1..256 (default 256): max(1, bound / (2^v * 8 KB)) queries per chunk.
                                      Same words at any value; tests lower it to run a small batch in several
                                      chunks */
+    TFHE_OPT_GRAPH_CHUNK_QUERIES = 21 /* CMUX graphs: 0 (default) as many queries per chunk as keep their slots
+                                     (n_slots * 8 KB each) within 256 MB of context scratch; 1 .. 2^31-1: at most
+                                     that many as well.  Same words at any value; tests lower it to run a small
+                                     batch in several chunks */
 };
 enum { TFHE_STAGING_PAGEABLE = 0, TFHE_STAGING_PINNED = 1 };  /* TFHE_OPT_HOST_STAGING */
 /* TFHE_ARITH_AUTO (default): at the L=3 / Bg=2^6 sets the blind rotation
@@ -515,6 +520,62 @@ int tfhe_gpu_packed_scatter_add_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_se
 int tfhe_gpu_packed_scatter_add_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/,
                                     uint32_t k, uint32_t width, const uint32_t *delta_dev,
                                     uint32_t *table_dev /*in place*/, size_t Q);
+/* CMUX graphs: decision diagrams and (weighted) automata over TRGSW-encrypted bits, the leveled mode of the TFHE
+ * paper.  One graph is shared by the Q queries of a call:
+ *   nL >= 1 leaves, TRLWELv1 leaves[nL*2N] (usually trivial), and V >= 0 inner nodes.  Value ids: 0 .. nL-1 are the
+ *   leaves, nL + v is node v.  Node v has var[v] < k, lo[v], hi[v] < nL + v (topological order) and rotations
+ *   rlo[v], rhi[v] <= 2N.  For query q, with mulxk = polyMulWithXK (trgsw.zig:442-466),
+ *       value[nL + v] = trgsw.cmux(mulxk(value[lo[v]], rlo[v]), mulxk(value[hi[v]], rhi[v]), set[addr[q*k + var[v]]])
+ *   so hi (rotated) is chosen where the bit is 1.  roots[R] are value ids (a leaf id is allowed) and
+ *   out[q*R + r] = value[roots[r]] of query q.
+ * Word for word this is tfhe_gpu_cmux_batch node by node on inputs rotated on the host by polyMulWithXK: the rotations
+ * are exact index and sign arithmetic, the CMUX is k_cmux's arithmetic in k_cmux's order (the reference's expression
+ * trees; TFHE_OPT_ARITH does not apply and the near-tie counter is untouched).  The rotations add up in the exponent
+ * along a path, so a leaf that is a test vector turns "the sum of the weights along the path" into any function of
+ * that sum (weighted automata: popcount thresholds, small additions), and several roots give several functions
+ * from one graph.
+ * Noise: every CMUX on the path from a root to its chosen leaf adds one external product's error, whatever the
+ * graph's width and however many nodes share a child, so a root's error grows with its depth only.  Two terms, both
+ * measured at the 128-bit set on ladders of up to 64 levels (tests/test_cmux_graph.py):
+ *   random: sigma = 2.1e-5 on the phase per CMUX, growing with the square root of the depth (1.6e-4 after 64 levels
+ *     under selectors of 0);
+ *   truncation: the reference's decomposition offset (key.zig:121-131) has no rounding half, so a CMUX whose selector
+ *     encrypts 1 hands on its input less r, 0 <= r < 2^(32 - L*bgbit), on every word.  On the phase of coefficient i
+ *     that is 2^-(L*bgbit + 1) * ((1 * s)[i] - 1) on average, 1 * s being the negacyclic product of the all-ones
+ *     polynomial and the level-1 key: about -2^-(L*bgbit + 1) * N/2 at coefficient 0, the same at every such CMUX, so
+ *     it adds up LINEARLY in the number of one-bits on the path.  128-bit set (L*bgbit = 18): -9.4e-4 per one-bit at
+ *     coefficient 0, 3.1e-2 after 32 one-bits, a quarter of the +-1/8 of a bit; 64 one-bits take half of it.  A CMUX
+ *     whose two inputs are the same words (a pass-through) adds exactly nothing: its digits are all zero.
+ * Keep a path's one-bits below 1/8 over that step (about 130 at the 128-bit set), less what the leaves' own noise
+ * and the key switch need.
+ * tfhe_cmux_graph_plan (host only) checks a graph and gives level[v] = 1 + the largest level among node v's
+ * non-leaf children (leaves are level 0, a node on two leaves is level 1), depth = the largest level, and
+ * slot[v] < n_slots, the TRLWELv1 of per-query scratch node v is written to.  One level is one launch, within which
+ * reads and writes are unordered: a slot is taken again by a node of level l only when its occupant and every reader
+ * of it have levels < l, and a root's slot never is.  TFHE_ERR_INVALID, and nothing written: nL = 0, a child id >= the
+ * node's own, var >= k, a rotation > 2N, a root >= nL + V, a null array with a non-zero count (level / slot with
+ * V > 0 included; depth and n_slots may be NULL).
+ * tfhe_gpu_cmux_graph_*: addr, the node arrays and roots are HOST arrays in both variants.  extract = 0: out = Q*R
+ * TRLWELv1; 1: sampleExtractIndex(., 0) of each (trlwe.zig:146-162), Q*R TLWELv1 of N + 1 words; 2: that plus
+ * identityKeySwitching (trgsw.zig:471-502), Q*R TLWELv0, what tfhe_gpu_sample_extract_* with coef = {0} and
+ * key_switch gives: ordinary gate or LUT inputs (TFHE_ERR_NO_KEY without a cloud key).  One launch per level over all
+ * queries of a chunk; queries run in chunks whose slots (n_slots * 8 KB per query) stay within the lookup's 256 MB,
+ * or of at most TFHE_OPT_GRAPH_CHUNK_QUERIES queries; chunking changes no word.  TFHE_ERR_INVALID before any upload
+ * or launch: the plan's refusals, an addr[] >= the set's size, a set of another context, a null argument, extract
+ * outside 0..2, k = 0 with V > 0.  Q = 0 is TFHE_OK; V = 0 is legal (the roots are leaves).  Runs on the context's
+ * first device.  The _dev variant takes leaves and out in HBM, is asynchronous on the context stream, refuses a
+ * multi-device context and requires out not to overlap leaves. */
+int tfhe_cmux_graph_plan(uint32_t nL, uint32_t V, uint32_t k, const uint32_t *var, const uint32_t *lo,
+                         const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi, uint32_t R, const uint32_t *roots,
+                         uint32_t N, uint32_t *level /*V*/, uint32_t *slot /*V*/, uint32_t *depth, uint32_t *n_slots);
+int tfhe_gpu_cmux_graph_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/, uint32_t k,
+                              const uint32_t *leaves /*nL*2N*/, uint32_t nL, uint32_t V, const uint32_t *var,
+                              const uint32_t *lo, const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi,
+                              uint32_t R, const uint32_t *roots, int extract, uint32_t *out, size_t Q);
+int tfhe_gpu_cmux_graph_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_trgsw_set *set, const uint32_t *addr /*Q*k*/, uint32_t k,
+                            const uint32_t *leaves_dev, uint32_t nL, uint32_t V, const uint32_t *var,
+                            const uint32_t *lo, const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi,
+                            uint32_t R, const uint32_t *roots, int extract, uint32_t *out_dev, size_t Q);
 /* sampleExtractIndex (trlwe.zig:146-162) at the C coefficients coef[] (host, each < N) of each of B TRLWELv1,
  * TRLWE-major; key_switch != 0 adds identityKeySwitching (trgsw.zig:471-502; TFHE_ERR_NO_KEY without a cloud
  * key): out = B*C*(N+1) or B*C*(n+1) words, ordinary TLWELv1 / TLWELv0 (gate inputs). */

@@ -404,6 +404,69 @@ inline TRLWELv1 rotateByBits(const TRLWELv1 &in, const std::vector<uint32_t> &ro
     return out;
 }
 
+// A CMUX graph (tfhe_gpu.h "CMUX graphs"): nLeaves leaves (value ids 0 .. nLeaves-1) and nodes over k encrypted bits,
+// node v (id nLeaves + v) = cmux(X^rlo value[lo], X^rhi value[hi], bit var), hi where the bit is 1; children are
+// earlier values.  lessThan is the comparator of two nbits-bit numbers over the leaves {0: false, 1: true}
+// (boolLeaves): variable 2i is bit nbits-1-i of a, variable 2i+1 that bit of b.
+struct CmuxGraph {
+    uint32_t k = 0, nLeaves = 0;
+    std::vector<uint32_t> var, lo, hi, rlo, rhi, roots;
+    CmuxGraph(uint32_t k_, uint32_t leaves) : k(k_), nLeaves(leaves) {}
+    uint32_t node(uint32_t v, uint32_t l, uint32_t h, uint32_t rl = 0, uint32_t rh = 0) {
+        var.push_back(v), lo.push_back(l), hi.push_back(h), rlo.push_back(rl), rhi.push_back(rh);
+        return nLeaves + (uint32_t)var.size() - 1;
+    }
+    // node(), or lo itself when both sides are the same value
+    uint32_t mux(uint32_t v, uint32_t l, uint32_t h) { return l == h ? l : node(v, l, h); }
+    static CmuxGraph lessThan(uint32_t nbits) {
+        CmuxGraph g(2 * nbits, 2);
+        uint32_t rest = 0;  // equal on the bits below: not less
+        for (uint32_t i = nbits; i-- > 0;) {
+            const uint32_t a0 = g.mux(2 * i + 1, rest, 1), a1 = g.mux(2 * i + 1, 0, rest);
+            rest = g.mux(2 * i, a0, a1);
+        }
+        g.roots.push_back(rest);
+        return g;
+    }
+    // tfhe_cmux_graph_plan: levels, slots, depth and the per-query scratch slots
+    struct Plan {
+        std::vector<uint32_t> level, slot;
+        uint32_t depth = 0, nSlots = 0;
+    };
+    Plan plan(uint32_t N = 1024) const {
+        Plan p;
+        p.level.resize(var.size()), p.slot.resize(var.size());
+        check(tfhe_cmux_graph_plan(nLeaves, (uint32_t)var.size(), k, var.data(), lo.data(), hi.data(), rlo.data(), rhi.data(),
+                                   (uint32_t)roots.size(), roots.data(), N, p.level.data(), p.slot.data(), &p.depth,
+                                   &p.nSlots),
+              "cmux_graph_plan");
+        return p;
+    }
+    // trivial TRLWEs with -1/8 (leaf 0, false) and +1/8 (leaf 1, true) in every coefficient
+    static std::vector<Torus> boolLeaves(const tfhe_params &p) {
+        std::vector<Torus> lv(2 * 2 * (size_t)p.N, 0u);
+        std::fill(lv.begin() + p.N, lv.begin() + 2 * (size_t)p.N, 0xE0000000u);
+        std::fill(lv.begin() + 3 * (size_t)p.N, lv.end(), 0x20000000u);
+        return lv;
+    }
+};
+
+// tfhe_gpu_cmux_graph_batch with extract = 2: the graph's roots for each query (addr[q * g.k + j] the selector of
+// variable j), extracted at coefficient 0 and key-switched, Q * R TLWELv0, query-major: ordinary gate inputs.
+inline std::vector<TLWELv0> cmuxGraph(const CloudKey &ck, const TrgswSet &set, const std::vector<uint32_t> &addr,
+                                      const CmuxGraph &g, const std::vector<Torus> &leaves) {
+    const size_t Q = g.k ? addr.size() / g.k : 0, R = g.roots.size(), w = ck.params().n + 1;
+    if (leaves.size() != (size_t)g.nLeaves * 2 * ck.params().N) throw Error(TFHE_ERR_INVALID, "cmuxGraph: nLeaves * 2N words");
+    std::vector<Torus> out(Q * R * w);
+    check(tfhe_gpu_cmux_graph_batch(ck.ctx(), set.get(), addr.data(), g.k, leaves.data(), g.nLeaves, (uint32_t)g.var.size(),
+                                    g.var.data(), g.lo.data(), g.hi.data(), g.rlo.data(), g.rhi.data(), (uint32_t)R,
+                                    g.roots.data(), 2, out.data(), Q),
+          "cmux_graph", ck.ctx());
+    std::vector<TLWELv0> r(Q * R, TLWELv0(ck.params().n));
+    for (size_t i = 0; i < Q * R; i++) std::copy(out.begin() + i * w, out.begin() + (i + 1) * w, r[i].p.begin());
+    return r;
+}
+
 class PackingKey;  // below
 inline std::vector<TRLWELv1> packTlwe(const CloudKey &ck, const PackingKey &key, const std::vector<TLWELv0> &in,
                                const std::vector<uint32_t> &coef);

@@ -454,6 +454,69 @@ const char *check_pack_args(const tfhe_params &p, uint32_t basebit, uint32_t t, 
     return nullptr;
 }
 
+// ---- CMUX graphs: checks, levels and the per-query scratch slots ------------------------
+// level[v] = 1 + the largest level among node v's children (leaves are level 0).  One level is one
+// launch, inside which reads and writes are unordered: a node of level l takes the lowest slot whose
+// occupant is out of use below l, that is, whose occupant and all of its readers have levels < l;
+// a root's slot stays its own to the end.  Nodes are placed in (level, index) order, so the plan is
+// a function of the graph alone.
+const char *plan_cmux_graph(uint32_t nL, uint32_t V, uint32_t k, const uint32_t *var, const uint32_t *lo,
+                            const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi, uint32_t R,
+                            const uint32_t *roots, uint32_t N, CmuxGraphPlan &pl) {
+    if (nL == 0) return "CMUX graph: no leaves";
+    if (nL >= 0x80000000u || V >= 0x80000000u - nL) return "CMUX graph: more than 2^31 values";
+    if (V && (!var || !lo || !hi || !rlo || !rhi)) return "CMUX graph: a null node array";
+    if (R && !roots) return "CMUX graph: null roots";
+    if (N == 0 || N > 0x40000000u) return "CMUX graph: N outside 1..2^30";
+    for (uint32_t v = 0; v < V; v++) {
+        if (var[v] >= k) return "CMUX graph: a node's variable >= k";
+        if (lo[v] >= nL + v || hi[v] >= nL + v) return "CMUX graph: a node's child is not an earlier value";
+        if (rlo[v] > 2 * N || rhi[v] > 2 * N) return "CMUX graph: a rotation > 2N";
+    }
+    for (uint32_t r = 0; r < R; r++)
+        if (roots[r] >= nL + V) return "CMUX graph: a root >= nL + V";
+    pl.level.assign(V, 0);
+    pl.slot.assign(V, 0);
+    pl.depth = pl.n_slots = 0;
+    std::vector<uint32_t> last(V, 0);  // the largest level among a node's readers (0: none)
+    std::vector<bool> is_root(V, false);
+    for (uint32_t v = 0; v < V; v++) {
+        uint32_t l = 0;
+        for (const uint32_t c : {lo[v], hi[v]})
+            if (c >= nL) l = std::max(l, pl.level[c - nL]);
+        pl.level[v] = l + 1;
+        pl.depth = std::max(pl.depth, l + 1);
+        for (const uint32_t c : {lo[v], hi[v]})
+            if (c >= nL) last[c - nL] = std::max(last[c - nL], l + 1);
+    }
+    for (uint32_t r = 0; r < R; r++)
+        if (roots[r] >= nL) is_root[roots[r] - nL] = true;
+    pl.first.assign(pl.depth + 1, 0);
+    for (uint32_t v = 0; v < V; v++) pl.first[pl.level[v]]++;  // first[l]: nodes of level l, then the running sum
+    for (uint32_t l = 1, sum = 0; l <= pl.depth; l++) {
+        const uint32_t c = pl.first[l];
+        pl.first[l - 1] = sum;
+        sum += c;
+        if (l == pl.depth) pl.first[l] = sum;
+    }
+    pl.order.assign(V, 0);
+    {
+        std::vector<uint32_t> at(pl.first.begin(), pl.first.end());
+        for (uint32_t v = 0; v < V; v++) pl.order[at[pl.level[v] - 1]++] = v;
+    }
+    constexpr uint32_t NEVER = 0xFFFFFFFFu;
+    std::vector<uint32_t> free_from;  // per slot: the first level whose nodes may take it
+    for (const uint32_t v : pl.order) {
+        uint32_t s = 0;
+        while (s < free_from.size() && free_from[s] > pl.level[v]) s++;
+        if (s == free_from.size()) free_from.push_back(0);
+        pl.slot[v] = s;
+        free_from[s] = is_root[v] ? NEVER : std::max(last[v], pl.level[v]) + 1;
+    }
+    pl.n_slots = (uint32_t)free_from.size();
+    return nullptr;
+}
+
 }  // namespace tfhe
 
 using namespace tfhe;
@@ -831,6 +894,22 @@ int tfhe_packed_lookup_plan(const tfhe_params *p, uint32_t k, uint32_t width, tf
     pl.cmuxes = pl.trlwes - 1 + h;
     for (uint32_t j = 0; j < h; j++) pl.rot[j] = 2 * p->N - (stride << j);
     *out = pl;
+    return TFHE_OK;
+}
+
+// A CMUX graph's levels and scratch slots (plan_cmux_graph above); nothing is written on a refusal.
+int tfhe_cmux_graph_plan(uint32_t nL, uint32_t V, uint32_t k, const uint32_t *var, const uint32_t *lo, const uint32_t *hi,
+                         const uint32_t *rlo, const uint32_t *rhi, uint32_t R, const uint32_t *roots, uint32_t N,
+                         uint32_t *level, uint32_t *slot, uint32_t *depth, uint32_t *n_slots) {
+    CmuxGraphPlan pl;
+    if (V && (!level || !slot)) return TFHE_ERR_INVALID;
+    if (plan_cmux_graph(nL, V, k, var, lo, hi, rlo, rhi, R, roots, N, pl)) return TFHE_ERR_INVALID;
+    if (V) {
+        std::memcpy(level, pl.level.data(), V * sizeof(uint32_t));
+        std::memcpy(slot, pl.slot.data(), V * sizeof(uint32_t));
+    }
+    if (depth) *depth = pl.depth;
+    if (n_slots) *n_slots = pl.n_slots;
     return TFHE_OK;
 }
 

@@ -116,6 +116,18 @@ size_t pack_key_words(const tfhe_params &p, uint32_t basebit, uint32_t t);  // n
 // coefficient >= N or listed twice)
 const char *check_pack_args(const tfhe_params &p, uint32_t basebit, uint32_t t, const uint32_t *coef, size_t C);
 
+// ---- CMUX graphs (tfhe_cmux_graph_plan here; tfhe_leveled.cpp evaluates the plan) ----
+// level / slot per node; the nodes in evaluation order, order[first[l-1] .. first[l]) being level l
+// (1-based; first has depth + 1 entries); n_slots TRLWELv1 of scratch per query.
+struct CmuxGraphPlan {
+    std::vector<uint32_t> level, slot, order, first;
+    uint32_t depth = 0, n_slots = 0;
+};
+// nullptr, or what is wrong with the graph (include/tfhe_gpu.h "CMUX graphs").
+const char *plan_cmux_graph(uint32_t nL, uint32_t V, uint32_t k, const uint32_t *var, const uint32_t *lo,
+                            const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi, uint32_t R,
+                            const uint32_t *roots, uint32_t N, CmuxGraphPlan &pl);
+
 // Device d's contiguous slice of B items over D devices: ceil(B/D) each, the
 // last non-empty one ragged, the ones after it empty.
 struct Slice {

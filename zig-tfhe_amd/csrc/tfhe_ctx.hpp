@@ -166,6 +166,7 @@ struct Device {
     int64_t circuit_pack = 1;
     int64_t pack_scratch_mb = 256;  // TFHE_OPT_PACK_SCRATCH_MB: bound on the packing key switch's GEMM sums per chunk
     int64_t scatter_scratch_mb = 256;  // TFHE_OPT_SCATTER_SCRATCH_MB: bound on the packed scatter-add's leaves per chunk
+    int64_t graph_chunk_queries = 0;   // TFHE_OPT_GRAPH_CHUNK_QUERIES: a CMUX graph's queries per chunk at most (0: the 256 MB bound alone)
     int64_t twiddle_source = TFHE_TWIDDLES_GLIBC;
     bool key_from_keygen = false;  // the resident BK was transformed with this device's tables
     double bk_absmax = 0.0;        // largest |BK spectrum component| of the resident key, reference scale

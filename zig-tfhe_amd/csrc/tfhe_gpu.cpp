@@ -1085,6 +1085,7 @@ static bool option_ok(const Device &d, int key, int64_t v, std::string &why) {
     case TFHE_OPT_CMUX_FORM: ok = v >= 0 && v <= 2; break;
     case TFHE_OPT_PACK_SCRATCH_MB:
     case TFHE_OPT_SCATTER_SCRATCH_MB: ok = v >= 1 && v <= 256; break;
+    case TFHE_OPT_GRAPH_CHUNK_QUERIES: ok = v >= 0 && v <= 0x7FFFFFFFll; break;
     case TFHE_OPT_TWIDDLES:
         ok = v == TFHE_TWIDDLES_GLIBC || v == TFHE_TWIDDLES_FDLIBM;
         // tfhe_gpu_keygen transformed the resident BK with the current tables:
@@ -1121,6 +1122,7 @@ static int apply_option(Device &d, int key, int64_t v) {
     case TFHE_OPT_CMUX_FORM: o.cmux_form = (int)v; break;
     case TFHE_OPT_PACK_SCRATCH_MB: d.pack_scratch_mb = v; break;
     case TFHE_OPT_SCATTER_SCRATCH_MB: d.scatter_scratch_mb = v; break;
+    case TFHE_OPT_GRAPH_CHUNK_QUERIES: d.graph_chunk_queries = v; break;
     case TFHE_OPT_HOST_STAGING:
         if (d.stage_used) HIPCHK(d, hipStreamSynchronize(d.stream));  // nothing in flight from the arena
         d.stage_used = 0;
@@ -1174,6 +1176,7 @@ int tfhe_gpu_get_option(const tfhe_gpu_ctx *c, int key, int64_t *v) {
     case TFHE_OPT_CMUX_FORM: *v = o.cmux_form; break;
     case TFHE_OPT_PACK_SCRATCH_MB: *v = d.pack_scratch_mb; break;
     case TFHE_OPT_SCATTER_SCRATCH_MB: *v = d.scatter_scratch_mb; break;
+    case TFHE_OPT_GRAPH_CHUNK_QUERIES: *v = d.graph_chunk_queries; break;
     default: return TFHE_ERR_INVALID;
     }
     return TFHE_OK;

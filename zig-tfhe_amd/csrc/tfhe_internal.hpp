@@ -260,6 +260,29 @@ struct RotateBatch {
 };
 hipError_t launch_rotate_chain(const KParams &P, const DevTables &T, const RotateBatch &b, hipStream_t s,
                                const char **used = nullptr);
+// One level of a CMUX graph (k_cmux_rot), device pointers: item q * cnt + i is the level's node i for
+// query q < nq of the chunk.  nodes: cnt descriptors of 6 words {var, lo, hi, rlo, rhi, slot}; lo / hi are
+// GRAPH_LEAF_REF | leaf index (into leaves) or a slot index < n_slots; slot < n_slots; rlo, rhi <= 2N;
+// addr[q * k + var] is the item's selector.  Query q's slots are slots[q * n_slots ..], 2N words each; the
+// host's plan (tfhe_cmux_graph_plan) keeps a level's outputs apart from every slot the level reads.
+constexpr uint32_t GRAPH_LEAF_REF = 0x80000000u;
+struct GraphLevel {
+    const double *sel_rows = nullptr;
+    const uint32_t *addr = nullptr;
+    uint32_t k = 0;
+    const uint32_t *nodes = nullptr;
+    uint32_t cnt = 0;
+    const uint32_t *leaves = nullptr;
+    uint32_t *slots = nullptr;
+    uint32_t n_slots = 0;
+    size_t nq = 0;
+};
+hipError_t launch_cmux_graph_level(const KParams &P, const DevTables &T, const GraphLevel &b, hipStream_t s,
+                                   const char **used = nullptr);
+// out[q * R + r] = the value roots[r] names (GRAPH_LEAF_REF | leaf, or a slot of query q), 2N words each, for
+// the nq queries of a chunk; roots on the device.  out must not overlap leaves or slots.
+hipError_t launch_cmux_graph_roots(const uint32_t *roots, uint32_t R, const uint32_t *leaves, const uint32_t *slots,
+                                   uint32_t n_slots, uint32_t *out, size_t nq, hipStream_t s);
 // One level of the demultiplexer tree (k_demux / k_demux_shared), device pointers: parent g reads
 // x = src[g] and writes hi = ExtProd(selector, x) to out[2g + 1] and lo = x - hi to out[2g], under
 // selector sel[(g >> level) * sel_stride]: the 2^level parents of a query share the level's

@@ -1,6 +1,7 @@
 // tfhe_kernels_leveled.hip — the leveled half of zig-tfhe on the device: CMUX
 // against caller-supplied TRGSW selectors (trgsw.zig:260-284), the rotation by
-// encrypted bits built from it (k_rotate_chain) and sampleExtractIndex at any
+// encrypted bits built from it (k_rotate_chain), the CMUX graph's level
+// (k_cmux_rot) and sampleExtractIndex at any
 // coefficient (trlwe.zig:146-162).  Its own unit: the
 // bootstrap kernels' objects (tfhe_kernels.o, tfhe_kernels_whole.o), which
 // tfhe_gpu_build_id() hashes, do not change with it.  Same flags as theirs
@@ -70,6 +71,77 @@ __global__ __launch_bounds__(64 * CMUX_WAVES) void k_cmux(KParams P, DevTables T
         o[t + 64 * m] = accA[m];
         o[1024 + t + 64 * m] = accB[m];
     }
+}
+
+// One level of a CMUX graph (include/tfhe_gpu.h "CMUX graphs"): k_cmux with its two inputs
+// gathered per item and multiplied by a power of X as they are read.  Item g is node
+// i = g % cnt of the level for query q = g / cnt of the chunk; the node's six words
+// nd[i] = {var, lo, hi, rlo, rhi, slot} are shared by the queries.  lo / hi name a leaf of the
+// shared leaves array (GRAPH_LEAF | index) or a slot of the query's own scratch
+// slots[q * n_slots ..], the selector is addr[q * k + var], and the output goes to the query's
+// slot nd.slot.  tA / tB = X^rhi in1 - X^rlo in0 + offset and the accumulators X^rlo in0 come
+// straight from global memory through rot_read (polyMulWithXK, trgsw.zig:442-466: index and sign
+// only, so a wave still reads 64 consecutive words mod N); everything after that is k_cmux, and
+// with rlo = rhi = 0 so are the words.  All of the item's descriptors are wave-uniform.  A slot
+// written in this launch is read by no item of it (tfhe_cmux_graph_plan), so reads and writes
+// need no order.  Waves past B return before they read or write anything; no workgroup barrier.
+constexpr uint32_t GRAPH_LEAF = GRAPH_LEAF_REF;  // tfhe_internal.hpp
+constexpr int GRAPH_NODE_WORDS = 6;
+template <int L>
+__global__ __launch_bounds__(64 * CMUX_WAVES) void k_cmux_rot(KParams P, DevTables TT,
+                                                              const double2 *__restrict__ sel_rows,
+                                                              const uint32_t *__restrict__ addr, uint32_t k,
+                                                              const uint32_t *__restrict__ nd, uint32_t cnt,
+                                                              const uint32_t *leaves, uint32_t *slots,
+                                                              uint32_t n_slots, uint32_t B) {
+    __shared__ C2 s_x[CMUX_WAVES][2 * 512];
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), t = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x * CMUX_WAVES + w;
+    if (g >= B) return;
+    const uint32_t q = g / cnt;
+    const uint32_t *me = nd + (size_t)(g - q * cnt) * GRAPH_NODE_WORDS;
+    const uint32_t lo = me[1], hi = me[2];
+    const int r0 = (int)me[3], r1 = (int)me[4];
+    uint32_t *mine = slots + (size_t)q * n_slots * 2048;
+    const uint32_t *x0 = (lo & GRAPH_LEAF) ? leaves + (size_t)(lo & ~GRAPH_LEAF) * 2048 : mine + (size_t)lo * 2048;
+    const uint32_t *x1 = (hi & GRAPH_LEAF) ? leaves + (size_t)(hi & ~GRAPH_LEAF) * 2048 : mine + (size_t)hi * 2048;
+    const double2 *row = sel_rows + (size_t)addr[(size_t)q * k + me[0]] * (2 * L * 1024);
+    uint32_t *o = mine + (size_t)me[5] * 2048;
+    RegTw T;
+    T.init(TT.tw, t);
+    C2 twl[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) twl[m] = TT.twist[t + 64 * m];
+    uint32_t tA[16], tB[16], accA[16], accB[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        accA[m] = rot_read(x0, t + 64 * m, r0);
+        accB[m] = rot_read(x0 + 1024, t + 64 * m, r0);
+        tA[m] = rot_read(x1, t + 64 * m, r1) - accA[m] + P.offset;
+        tB[m] = rot_read(x1 + 1024, t + 64 * m, r1) - accB[m] + P.offset;
+    }
+    C2 fa[8], fb[8];
+    ext_pairs_global<L>(tA, tB, row, P.bgbit, T, twl, s_x[w], t, fa, fb);
+    uint32_t near = NEAR_NONE;
+    inverse_and_add<false, 1>(fa, fb, s_x[w], T, twl, t, accA, accB, near);
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        o[t + 64 * m] = accA[m];
+        o[1024 + t + 64 * m] = accB[m];
+    }
+}
+
+// out[g] = the value `roots[g % R]` names (a leaf, or a slot of query g / R of the chunk) for the
+// nq * R outputs of a chunk: a copy of 2N words, one block each.
+__global__ __launch_bounds__(256) void k_graph_roots(const uint32_t *__restrict__ roots, uint32_t R,
+                                                     const uint32_t *__restrict__ leaves,
+                                                     const uint32_t *__restrict__ slots, uint32_t n_slots,
+                                                     uint32_t *__restrict__ out) {
+    const uint32_t q = blockIdx.x / R, r = roots[blockIdx.x % R];
+    const uint32_t *x = (r & GRAPH_LEAF) ? leaves + (size_t)(r & ~GRAPH_LEAF) * 2048
+                                         : slots + ((size_t)q * n_slots + r) * 2048;
+    uint32_t *o = out + (size_t)blockIdx.x * 2048;
+    for (uint32_t i = threadIdx.x; i < 2048; i += 256) o[i] = x[i];
 }
 
 // Workgroup form for items that share their selector: the 4 waves' items
@@ -502,6 +574,39 @@ hipError_t launch_cmux(const KParams &P, const DevTables &T, const CmuxBatch &b,
     default: return hipErrorInvalidValue;
     }
     if (used) *used = name;
+    return hipGetLastError();
+}
+
+template <int L>
+static const char *graph_launch(dim3 grid, dim3 block, hipStream_t s, const KParams &P, const DevTables &T,
+                                const GraphLevel &b) {
+    hipLaunchKernelGGL(k_cmux_rot<L>, grid, block, 0, s, P, T, reinterpret_cast<const double2 *>(b.sel_rows), b.addr, b.k,
+                       b.nodes, b.cnt, b.leaves, b.slots, b.n_slots, (uint32_t)(b.nq * b.cnt));
+    return L == 1 ? "k_cmux_rot<1>" : L == 2 ? "k_cmux_rot<2>" : "k_cmux_rot<3>";
+}
+
+hipError_t launch_cmux_graph_level(const KParams &P, const DevTables &T, const GraphLevel &b, hipStream_t s,
+                                   const char **used) {
+    if (b.nq == 0 || b.cnt == 0) return hipSuccess;
+    if (b.nq > 0xFFFFFFFFull / b.cnt) return hipErrorInvalidValue;  // the item index is 32 bits wide
+    const size_t B = b.nq * b.cnt;
+    const dim3 grid((unsigned)((B + CMUX_WAVES - 1) / CMUX_WAVES)), block(64 * CMUX_WAVES);
+    const char *name = "";
+    switch (P.L) {
+    case 1: name = graph_launch<1>(grid, block, s, P, T, b); break;
+    case 2: name = graph_launch<2>(grid, block, s, P, T, b); break;
+    case 3: name = graph_launch<3>(grid, block, s, P, T, b); break;
+    default: return hipErrorInvalidValue;
+    }
+    if (used) *used = name;
+    return hipGetLastError();
+}
+
+hipError_t launch_cmux_graph_roots(const uint32_t *roots, uint32_t R, const uint32_t *leaves, const uint32_t *slots,
+                                   uint32_t n_slots, uint32_t *out, size_t nq, hipStream_t s) {
+    if (nq == 0 || R == 0) return hipSuccess;
+    if (nq > 0xFFFFFFFFull / R) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_graph_roots, dim3((unsigned)(nq * R)), dim3(256), 0, s, roots, R, leaves, slots, n_slots, out);
     return hipGetLastError();
 }
 

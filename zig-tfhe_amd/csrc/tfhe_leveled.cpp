@@ -1,7 +1,7 @@
 // tfhe_leveled.cpp — the leveled half of the C ABI (include/tfhe_gpu.h):
 // resident selector sets, CMUX, table lookup by a CMUX tree, rotation by
 // encrypted bits and the packed lookup built on both, the packed scatter-add
-// (rotation, demultiplexer tree, sum), and sample extraction at
+// (rotation, demultiplexer tree, sum), CMUX graphs, and sample extraction at
 // any coefficient (TRLWE / TRGSW encryption is in tfhe_encrypt.cpp).  Host code;
 // the arithmetic runs in tfhe_kernels_leveled.hip and the stage kernels of
 // tfhe_kernels.hip.  Everything here runs on the context's first device and,
@@ -267,6 +267,74 @@ static int packed_scatter_on(Device &d, const tfhe_gpu_trgsw_set &set, const uin
     return io.finish();
 }
 
+// A CMUX graph (include/tfhe_gpu.h "CMUX graphs") by its plan: per chunk of queries one k_cmux_rot launch per
+// level over all the chunk's queries, each node writing its slot of the query's n_slots TRLWELv1 of scratch, then
+// one copy of the roots (k_graph_roots) into the outputs, or into a slice that sampleExtractIndex(., 0) reads; the
+// key switch of extract = 2 runs once, over all Q * R extractions.  A chunk is as many queries as keep the slots
+// within LOOKUP_SCRATCH_CAP, and at most TFHE_OPT_GRAPH_CHUNK_QUERIES.  The address bits of all queries, the
+// node descriptors in evaluation order (children and outputs as slots), the roots and the extraction's one
+// coefficient go up once, in one array.
+struct CmuxGraphArgs {
+    uint32_t k, nL, V, R;
+    const uint32_t *var, *lo, *hi, *rlo, *rhi, *roots;
+};
+static int cmux_graph_on(Device &d, const tfhe_gpu_trgsw_set &set, const uint32_t *addr, const CmuxGraphArgs &g,
+                         const CmuxGraphPlan &pl, const uint32_t *leaves, int extract, uint32_t *out, size_t Q, bool dev) {
+    if (extract == 2 && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t outs = Q * g.R, wo = extract == 0 ? 2048 : extract == 1 ? (size_t)d.P.N + 1 : tlwe0_words(d.P);
+    size_t chunk = pl.n_slots ? std::min(Q, std::max<size_t>(1, LOOKUP_SCRATCH_CAP / (pl.n_slots * TRLWE_BYTES))) : Q;
+    if (d.graph_chunk_queries) chunk = std::min(chunk, (size_t)d.graph_chunk_queries);
+    const auto ref = [&](uint32_t id) { return id < g.nL ? GRAPH_LEAF_REF | id : pl.slot[id - g.nL]; };
+    DescBlob blob;
+    const size_t addr_at = blob.add(addr, Q * g.k), nodes_at = blob.reserve((size_t)g.V * 6),
+                 roots_at = blob.reserve(g.R), coef_at = blob.reserve(1);  // coefficient 0
+    for (uint32_t i = 0; i < g.V; i++) {
+        const uint32_t v = pl.order[i];
+        const uint32_t nd[6] = {g.var[v], ref(g.lo[v]), ref(g.hi[v]), g.rlo[v], g.rhi[v], pl.slot[v]};
+        std::copy(nd, nd + 6, blob.words.begin() + nodes_at + (size_t)i * 6);
+    }
+    for (uint32_t r = 0; r < g.R; r++) blob.words[roots_at + r] = ref(g.roots[r]);
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *didx = blob.upload(f);
+    io.in(leaves, (size_t)g.nL * TRLWE_BYTES);
+    int rc = io.out(out, outs * wo * 4);
+    uint32_t *slots = pl.n_slots ? f.take<uint32_t>(chunk * pl.n_slots * 2048) : nullptr;
+    uint32_t *picked = extract ? f.take<uint32_t>(chunk * g.R * 2048) : nullptr;  // a chunk's roots before extraction
+    uint32_t *lv1 = extract == 2 ? f.ks_input<uint32_t>(outs * 1025) : out;
+    if ((rc = f.rc())) return rc;
+    const KParams K = leveled_params(d);
+    const DevTables T = tables(d);
+    d.last_br = g.V ? "" : "k_graph_roots";
+    d.last_ks = "";
+    for (size_t q0 = 0; q0 < Q; q0 += chunk) {
+        const size_t nq = std::min(chunk, Q - q0);
+        for (uint32_t l = 1; l <= pl.depth; l++) {
+            GraphLevel b;
+            b.sel_rows = set.rows;
+            b.addr = didx + addr_at + q0 * g.k;
+            b.k = g.k;
+            b.nodes = didx + nodes_at + (size_t)pl.first[l - 1] * 6;
+            b.cnt = pl.first[l] - pl.first[l - 1];
+            b.leaves = leaves;
+            b.slots = slots;
+            b.n_slots = pl.n_slots;
+            b.nq = nq;
+            HIPCHK(d, launch_cmux_graph_level(K, T, b, d.stream, &d.last_br));
+        }
+        uint32_t *to = extract ? picked : out + q0 * g.R * 2048;
+        HIPCHK(d, launch_cmux_graph_roots(didx + roots_at, g.R, leaves, slots, pl.n_slots, to, nq, d.stream));
+        if (extract)
+            HIPCHK(d, launch_sample_extract(picked, didx + coef_at, 1, lv1 + q0 * g.R * 1025, nq * g.R, d.stream));
+    }
+    if (extract == 2) {
+        KsGemm G;
+        if ((rc = ks_gemm_args(f, outs, G))) return rc;
+        HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, outs, d.stream, d.opts, &d.last_ks, &G));
+    }
+    return io.finish();
+}
+
 static int sample_extract_on(Device &d, const uint32_t *trlwe, const uint32_t *coef, size_t C, bool key_switch,
                              uint32_t *out, size_t B, bool dev) {
     if (key_switch && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
@@ -434,6 +502,43 @@ int tfhe_gpu_packed_scatter_add_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set 
 int tfhe_gpu_packed_scatter_add_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
                                     uint32_t width, const uint32_t *delta_dev, uint32_t *table_dev, size_t Q) {
     return scatter_entry(c, set, addr, k, width, delta_dev, table_dev, Q, true);
+}
+
+static int graph_entry(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, const CmuxGraphArgs &g,
+                       const uint32_t *leaves, int extract, uint32_t *out, size_t Q, bool dev) {
+    if (!c || !set || !leaves || (Q && ((g.k && !addr) || (g.R && !out)))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (extract < 0 || extract > 2) return fail(c, TFHE_ERR_INVALID, "CMUX graph: extract outside 0..2");
+    CmuxGraphPlan pl;
+    if (const char *why = plan_cmux_graph(g.nL, g.V, g.k, g.var, g.lo, g.hi, g.rlo, g.rhi, g.R, g.roots, c->P.N, pl))
+        return fail(c, TFHE_ERR_INVALID, why);
+    if (const int rc = set_mismatch(c, set, "selector set")) return rc;
+    const size_t widest = std::max<size_t>({(size_t)g.k, (size_t)g.V, (size_t)g.R, 1});
+    if (Q > 0xFFFFFFFFull / widest) return fail(c, TFHE_ERR_INVALID, "CMUX graph: too many queries");
+    for (size_t i = 0; i < Q * g.k; i++)
+        if (addr[i] >= set->S) return fail(c, TFHE_ERR_INVALID, "address selector index >= the set's size");
+    if (dev && Q && g.R) {
+        const size_t wo = extract == 0 ? 2048 : extract == 1 ? (size_t)c->P.N + 1 : tlwe0_words(c->P);
+        const uint32_t *le = leaves + (size_t)g.nL * 2048, *oe = out + Q * g.R * wo;
+        if (out < le && leaves < oe) return fail(c, TFHE_ERR_INVALID, "CMUX graph: out overlaps leaves");
+    }
+    if (Q == 0 || g.R == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) { return cmux_graph_on(d, *set, addr, g, pl, leaves, extract, out, Q, dev); });
+}
+
+int tfhe_gpu_cmux_graph_batch(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                              const uint32_t *leaves, uint32_t nL, uint32_t V, const uint32_t *var, const uint32_t *lo,
+                              const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi, uint32_t R,
+                              const uint32_t *roots, int extract, uint32_t *out, size_t Q) {
+    return graph_entry(c, set, addr, CmuxGraphArgs{k, nL, V, R, var, lo, hi, rlo, rhi, roots}, leaves, extract, out, Q, false);
+}
+
+int tfhe_gpu_cmux_graph_dev(tfhe_gpu_ctx *c, const tfhe_gpu_trgsw_set *set, const uint32_t *addr, uint32_t k,
+                            const uint32_t *leaves_dev, uint32_t nL, uint32_t V, const uint32_t *var, const uint32_t *lo,
+                            const uint32_t *hi, const uint32_t *rlo, const uint32_t *rhi, uint32_t R,
+                            const uint32_t *roots, int extract, uint32_t *out_dev, size_t Q) {
+    return graph_entry(c, set, addr, CmuxGraphArgs{k, nL, V, R, var, lo, hi, rlo, rhi, roots}, leaves_dev, extract, out_dev, Q,
+                       true);
 }
 
 static int extract_entry(tfhe_gpu_ctx *c, const uint32_t *trlwe, const uint32_t *coef, size_t C, int key_switch,

@@ -25,12 +25,12 @@ LIB_PATH = os.environ.get("TFHE_GPU_LIB") or os.path.join(HERE, "lib", "libtfhe_
 OPTIONS = {"br_form": 1, "br_loader": 2, "ks_form": 3, "ks_narrow": 4, "ks_item_groups": 5, "ks_sel_items": 6,
            "circuit_pack": 7, "twiddles": 8, "arith": 9, "br_sync": 10, "br_spin_cap": 11, "host_pipeline": 12,
            "circuit_split": 13, "host_staging": 17, "cmux_form": 18, "pack_scratch_mb": 19,
-           "scatter_scratch_mb": 20}
+           "scatter_scratch_mb": 20, "graph_chunk_queries": 21}
 READONLY_OPTIONS = {"fused_admitted": 14, "level_issue_us": 15, "key_row_rms_ppm": 16}  # tfhe_gpu_get_option only
 OPTION_DEFAULTS = {"br_form": 0, "br_loader": 1, "ks_form": 3, "ks_narrow": 0, "ks_item_groups": 0,
                    "ks_sel_items": 8, "circuit_pack": 1, "twiddles": 0, "arith": 0, "br_sync": 1, "br_spin_cap": 0,
                    "host_pipeline": 0, "circuit_split": 0, "host_staging": 0, "cmux_form": 0,
-                   "pack_scratch_mb": 256, "scatter_scratch_mb": 256}
+                   "pack_scratch_mb": 256, "scatter_scratch_mb": 256, "graph_chunk_queries": 0}
 # status codes (include/tfhe_gpu.h TFHE_ERR_*)
 ERR_INVALID, ERR_HIP, ERR_NO_KEY, ERR_OOM, ERR_IO, ERR_DEVICE = -1, -2, -3, -4, -5, -6
 # 2 split, 4 pair: removed (round 4); 6 duo, 7 wide2: A/B libraries only (tools/ab/, round 5); 5 octo: L = 1
@@ -211,6 +211,12 @@ _SIGS = {
     "tfhe_gpu_packed_lookup_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
     "tfhe_gpu_packed_scatter_add_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, u32p, u32p, C.c_size_t]),
     "tfhe_gpu_packed_scatter_add_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]),
+    "tfhe_cmux_graph_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, C.c_uint32, u32p,
+                                       C.c_uint32, u32p, u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_cmux_graph_batch": (C.c_int, [vp, vp, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u32p,
+                                            u32p, u32p, C.c_uint32, u32p, C.c_int, u32p, C.c_size_t]),
+    "tfhe_gpu_cmux_graph_dev": (C.c_int, [vp, vp, u32p, C.c_uint32, vp, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p,
+                                          u32p, C.c_uint32, u32p, C.c_int, vp, C.c_size_t]),
     "tfhe_gpu_packing_key_gen": (C.c_int, [vp, u32p, u32p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, u32p]),
     "tfhe_gpu_packing_key_load": (C.c_int, [vp, u32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "tfhe_gpu_packing_key_destroy": (None, [vp]),
@@ -691,6 +697,35 @@ class Context:
         addr, ap = _u32(np.atleast_2d(addr))
         self.check(self.lib.tfhe_gpu_table_lookup_dev(self.h, selectors.h, ap, addr.shape[1], vp(table_ptr),
                                                       vp(out_ptr), addr.shape[0]), "table_lookup_dev")
+
+    def _graph_out_words(self, extract: int) -> int:
+        if extract not in (0, 1, 2):
+            raise ValueError(f"cmux_graph: extract is 0 (TRLWELv1), 1 (TLWELv1) or 2 (TLWELv0), got {extract}")
+        return (2 * self.params.N, self.params.N + 1, self.n1)[extract]
+
+    def cmux_graph(self, selectors: "TrgswSet", addr, graph: "CmuxGraph", leaves, extract: int = 0):
+        """tfhe_gpu_cmux_graph_batch: `graph` evaluated for each of the Q rows of addr (Q, k) selector indices, variable
+        j of the graph being address bit j; leaves (nL, 2N) TRLWELv1 shared by the queries.  -> (Q, R, words): the
+        roots as TRLWELv1 (extract = 0), sampleExtractIndex(., 0) of them (1), or that key-switched to TLWELv0 (2)."""
+        leaves, lp = _u32(np.atleast_2d(leaves))
+        addr, ap = _u32(np.asarray(addr, np.uint32).reshape(-1, graph.k) if graph.k else np.zeros((len(addr), 0), np.uint32))
+        if leaves.shape != (graph.n_leaves, 2 * self.params.N):
+            raise ValueError(f"cmux_graph: the graph has {graph.n_leaves} leaves of {2 * self.params.N} words, got "
+                             f"{leaves.shape}")
+        out = np.zeros((addr.shape[0], len(graph.roots), self._graph_out_words(extract)), np.uint32)
+        self.check(self.lib.tfhe_gpu_cmux_graph_batch(self.h, selectors.h, ap, graph.k, lp, graph.n_leaves,
+                                                      *graph.pointers(), extract, out.ctypes.data_as(u32p),
+                                                      addr.shape[0]), "cmux_graph")
+        return out
+
+    def cmux_graph_dev(self, selectors: "TrgswSet", addr, graph: "CmuxGraph", leaves_ptr, out_ptr, extract: int = 0):
+        """tfhe_gpu_cmux_graph_dev: the leaves (nL TRLWELv1) and the Q * R outputs in HBM (addr and the graph stay
+        host arrays), async on the context stream; the outputs must not overlap the leaves."""
+        addr, ap = _u32(np.asarray(addr, np.uint32).reshape(-1, graph.k) if graph.k else np.zeros((len(addr), 0), np.uint32))
+        self._graph_out_words(extract)
+        self.check(self.lib.tfhe_gpu_cmux_graph_dev(self.h, selectors.h, ap, graph.k, vp(leaves_ptr), graph.n_leaves,
+                                                    *graph.pointers(), extract, vp(out_ptr), addr.shape[0]),
+                   "cmux_graph_dev")
 
     def sample_extract(self, trlwes, coef, key_switch: bool = False):
         """sampleExtractIndex (trlwe.zig:146-162) at coefficients coef of each TRLWE, then optionally
@@ -1439,6 +1474,141 @@ class LutCircuit:
                                                   np.array(self.outputs, np.uint32), outputs_ptr)
         return ctx.lut_circuit_eval_dev(lut_set, inputs_ptr, self.n_inputs, self.packed(),
                                         np.array(self.outputs, np.uint32), outputs_ptr)
+
+
+class CmuxGraph:
+    """A CMUX graph (include/tfhe_gpu.h "CMUX graphs"): n_leaves leaves (value ids 0 .. n_leaves-1) and inner nodes
+    over k encrypted bits, node v (value id n_leaves + v) being cmux(X^rlo value[lo], X^rhi value[hi], bit var): hi
+    where the bit is 1.  Children are earlier values.  Context.cmux_graph evaluates the roots for a batch of queries;
+    plan() and evaluate_plain() need no device.  The builders (less_than, equals_const, dfa, popcount) share equal
+    nodes and drop a node whose two sides are the same value unrotated."""
+
+    def __init__(self, k: int, n_leaves: int):
+        self.k, self.n_leaves = int(k), int(n_leaves)
+        self.var, self.lo, self.hi, self.rlo, self.rhi, self.roots = [], [], [], [], [], []
+        self._shared = {}
+
+    @property
+    def n_nodes(self) -> int:
+        return len(self.var)
+
+    def node(self, var: int, lo: int, hi: int, rlo: int = 0, rhi: int = 0) -> int:
+        """A new node; -> its value id.  Checked by plan() and the device calls, not here."""
+        for a, x in zip((self.var, self.lo, self.hi, self.rlo, self.rhi), (var, lo, hi, rlo, rhi)):
+            a.append(int(x))
+        return self.n_leaves + len(self.var) - 1
+
+    def _mux(self, var: int, lo: int, hi: int) -> int:
+        """node() for the builders: lo itself when hi is the same value, and one node per (var, lo, hi)."""
+        if lo == hi:
+            return lo
+        key = (var, lo, hi)
+        if key not in self._shared:
+            self._shared[key] = self.node(var, lo, hi)
+        return self._shared[key]
+
+    def root(self, *ids):
+        self.roots.extend(int(i) for i in ids)
+        return self
+
+    def pointers(self):
+        """(V, var, lo, hi, rlo, rhi, R, roots) as the C entries take them; the arrays live as long as self."""
+        self._arrays = [np.array(a, np.uint32) for a in (self.var, self.lo, self.hi, self.rlo, self.rhi, self.roots)]
+        p = [a.ctypes.data_as(u32p) if a.size else None for a in self._arrays]
+        return (self.n_nodes, *p[:5], len(self.roots), p[5])
+
+    def plan(self, N: int = 1024):
+        """tfhe_cmux_graph_plan: (level per node, slot per node, depth, n_slots); TfheError where it refuses."""
+        level, slot = np.zeros(self.n_nodes, np.uint32), np.zeros(self.n_nodes, np.uint32)
+        depth, n_slots = C.c_uint32(), C.c_uint32()
+        V, var, lo, hi, rlo, rhi, R, roots = self.pointers()
+        rc = load_library().tfhe_cmux_graph_plan(self.n_leaves, V, self.k, var, lo, hi, rlo, rhi, R, roots, N,
+                                                 level.ctypes.data_as(u32p) if V else None,
+                                                 slot.ctypes.data_as(u32p) if V else None, C.byref(depth), C.byref(n_slots))
+        if rc != 0:
+            raise TfheError(f"cmux_graph_plan: status {rc}", rc)
+        return level, slot, depth.value, n_slots.value
+
+    def evaluate_plain(self, bits, N: int = 1024):
+        """What the graph selects for plain bits (k of them): per root (leaf id, total rotation mod 2N), the root
+        being X^rotation * leaf."""
+        out = []
+        for v in self.roots:
+            rot = 0
+            while v >= self.n_leaves:
+                i = v - self.n_leaves
+                b = int(bits[self.var[i]]) & 1
+                rot += self.rhi[i] if b else self.rlo[i]
+                v = self.hi[i] if b else self.lo[i]
+            out.append((v, rot % (2 * N)))
+        return out
+
+    @staticmethod
+    def bool_leaves(N: int = 1024) -> np.ndarray:
+        """The two trivial leaves of the builders' decision diagrams: leaf 0 = false (-1/8 at every coefficient),
+        leaf 1 = true (+1/8).  (2, 2N)."""
+        out = np.zeros((2, 2 * N), np.uint32)
+        out[0, N:], out[1, N:] = 0xE0000000, 0x20000000
+        return out
+
+    @staticmethod
+    def testvec_leaf(values, N: int = 1024) -> np.ndarray:
+        """A trivial test-vector leaf: coefficient c is +1/8 where values[c] is true, -1/8 elsewhere.  (1, 2N)."""
+        out = np.zeros((1, 2 * N), np.uint32)
+        out[0, N:] = 0xE0000000
+        out[0, N:N + len(values)] = np.where(np.asarray(values, bool), 0x20000000, 0xE0000000)
+        return out
+
+    @classmethod
+    def less_than(cls, nbits: int) -> "CmuxGraph":
+        """a < b for two nbits-bit numbers: variables interleaved, most significant first (variable 2i is bit
+        nbits-1-i of a, variable 2i+1 that bit of b); leaves as in bool_leaves; 3 nodes per bit pair."""
+        g = cls(2 * nbits, 2)
+        rest = 0  # a == b on the bits below: not less
+        for i in reversed(range(nbits)):
+            a0 = g._mux(2 * i + 1, rest, 1)  # a_i = 0: less if b_i = 1
+            a1 = g._mux(2 * i + 1, 0, rest)  # a_i = 1: not less if b_i = 0
+            rest = g._mux(2 * i, a0, a1)
+        return g.root(rest)
+
+    @classmethod
+    def equals_const(cls, nbits: int, c: int) -> "CmuxGraph":
+        """x == c for an nbits-bit x, variable j being bit j of x (least significant first)."""
+        g = cls(nbits, 2)
+        cur = 1
+        for j in range(nbits):
+            cur = g._mux(j, cur, 0) if (c >> j) & 1 == 0 else g._mux(j, 0, cur)
+        return g.root(cur)
+
+    @classmethod
+    def dfa(cls, n_states: int, delta, accepting, length: int, bits_per_symbol: int) -> "CmuxGraph":
+        """Does the automaton (start state 0, delta[state][symbol], accepting: a set of states) accept the string of
+        `length` symbols?  Variable p * bits_per_symbol + b is bit b (least significant first) of symbol p.  Only
+        the states reachable at a position get nodes."""
+        g = cls(length * bits_per_symbol, 2)
+        reach = [{0}]
+        for _ in range(length):
+            reach.append({int(delta[s][a]) for s in reach[-1] for a in range(1 << bits_per_symbol)})
+        val = {s: int(s in accepting) for s in range(n_states)}
+        for p in reversed(range(length)):
+            nxt = {}
+            for s in sorted(reach[p]):
+                items = [val[int(delta[s][a])] for a in range(1 << bits_per_symbol)]
+                for b in range(bits_per_symbol):
+                    items = [g._mux(p * bits_per_symbol + b, items[2 * i], items[2 * i + 1]) for i in range(len(items) // 2)]
+                nxt[s] = items[0]
+            val = nxt
+        return g.root(val[0])
+
+    @classmethod
+    def popcount(cls, nbits: int, N: int = 1024) -> "CmuxGraph":
+        """A chain over one test-vector leaf tv (leaf 0): every set bit multiplies by X^(2N-1) = X^-1, so coefficient
+        0 of the root is tv[popcount of the bits]."""
+        g = cls(nbits, 1)
+        cur = 0
+        for j in range(nbits):
+            cur = g.node(j, cur, cur, 0, 2 * N - 1)
+        return g.root(cur)
 
 
 def lookup_table_pack_bits(params: TfheParams, values, width: int) -> np.ndarray:
