@@ -43,7 +43,9 @@ extern "C" {
                                    packed scatter-add (tfhe_gpu_packed_scatter_add_*, TFHE_OPT_SCATTER_SCRATCH_MB)
                                    and the bivariate LUT bootstrap (tfhe_lut_spread, tfhe_gpu_lut_spread_*,
                                    tfhe_gpu_bootstrap_lut_each_*, tfhe_gpu_lut_apply2_*) and the CMUX graphs
-                                   (tfhe_cmux_graph_plan, tfhe_gpu_cmux_graph_*, TFHE_OPT_GRAPH_CHUNK_QUERIES);
+                                   (tfhe_cmux_graph_plan, tfhe_gpu_cmux_graph_*, TFHE_OPT_GRAPH_CHUNK_QUERIES)
+                                   and the select nodes (tfhe_gpu_lut_circuit_eval_select*, tfhe_gpu_lut_select_*,
+                                   tfhe_lut_circuit_schedule_select, TFHE_LUT_ENTRY_CONST);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -783,6 +785,75 @@ int tfhe_gpu_lut_apply2_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, co
 int tfhe_gpu_lut_apply2_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
                             uint32_t m, const uint32_t *pool_dev, size_t P, const uint32_t *fn /*B*/,
                             const uint32_t *x_src /*B*/, const uint32_t *y_src /*B*/, uint32_t *out_dev, size_t B);
+
+/* ---- Select nodes: LUT-circuit nodes whose table is made of wires ----
+ * The bivariate bootstrap as a node kind of the circuit evaluator, and with it trees over three or more digits and
+ * reads of a client-encrypted table by an address the server computed.  With m a power of two, 2 <= m, 2m <= N,
+ * w = N/m and off = N/(2m) as in tfhe_gpu_lut_apply2_*, a select node g has a combination x_g, exactly as
+ * tfhe_gpu_lut_apply_* defines it (terms, coefficients, konst), and m entries e_g[0 .. m), each either the words of
+ * an earlier wire or the trivial TLWELv0 (0, ..., 0, c) of a torus word c.  Its output is, word for word,
+ *       1. P_g  = tfhe_pack_tlwe(e_g[0 .. m), coef[i] = i*w, C = m);
+ *       2. TV_g = tfhe_lut_spread(P_g, w, 2N - off);
+ *       3. out_g = the tfhe_gpu_bootstrap_lut_each_* output for x_g with TV_g,
+ * so out_g decrypts to what entry number x_g decrypts to.  Consequences: entries that are all constants
+ * Encoder.encode(f(i)) give exactly the words of an ordinary node with the table tfhe_lut_generate(m, f) (the pack of
+ * trivial inputs leaves a = 0 and b[i*w] = c_i, and spread of that is the generator's table, above); m ordinary
+ * one-term nodes with the tables set[fn*m + i] over y feeding a select node over x give exactly the words of
+ * tfhe_gpu_lut_apply2_* for (fn, x, y); a k-digit tree is nested select nodes.
+ * In a circuit, node g is a select node iff sel_off[g+1] - sel_off[g] == m (any other non-zero count is invalid);
+ * entry j is the constant sel_konst[j] where sel_wire[j] == TFHE_LUT_ENTRY_CONST, and the wire sel_wire[j] otherwise.
+ * A select node is single-output (theta = 0) and ignores lut, which must be 0.  Its level is 1 + the largest level
+ * among its x-term wires and its entry wires, and it counts as one bootstrap level.  Wires are numbered as in
+ * tfhe_gpu_lut_circuit_eval_multi.  A level stages its select nodes' entries, packs and spreads them (in chunks
+ * within TFHE_OPT_PACK_SCRATCH_MB), and runs ONE blind-rotation launch over its ordinary and its select nodes: item by
+ * item the test vector comes from the set or from the level's own.  A level that also holds theta > 0 nodes runs
+ * those and its other ordinary nodes as tfhe_gpu_lut_circuit_eval_multi does, and its select nodes in one launch of
+ * their own.  Chunking and launch grouping change no word.  sel_off == NULL runs exactly what the _multi entry runs
+ * (pk and m are not looked at).
+ * The flat form runs B select nodes over a pool of P ciphertexts, as tfhe_gpu_lut_apply_* stands beside the circuit:
+ * node b has the terms term_off[b] .. term_off[b+1] and the m entries sel_src[b*m + i], a pool index or
+ * TFHE_LUT_ENTRY_CONST with the constant sel_konst[b*m + i].  It needs no LUT set.
+ * Noise rule (the library does not police it): the error of TV_g at the coefficient that is read is the selected
+ * entry's own error plus the pack's terms (the bivariate section's: sigma ~ 2e-4 at UINT4 with the default key shape
+ * and alpha_lv1); that sum is added to the OUTPUT's error, not to the input rounding, so a chain of k select nodes
+ * accumulates k such terms linearly, against a message spacing of 1/(2m), that is, a decision margin of 1/(4m).
+ * The warning about packing keys made with alpha_lv0 applies unchanged.  Measured figures: DESIGN.md §4.9d.
+ * Checked before any launch or upload (TFHE_ERR_INVALID): everything tfhe_gpu_lut_circuit_eval_multi checks; m not a
+ * power of two, m < 2 or 2m > N; a set or a packing key of another context; a null argument; an entry count other
+ * than 0 or m; an entry wire that is not an earlier wire (flat form: not in the pool); theta != 0 or lut != 0 on a
+ * select node; sel_off not monotone from 0.  TFHE_ERR_NO_KEY without a cloud key; zero nodes is TFHE_OK.  All
+ * descriptors are HOST arrays in both variants; the _dev ones take the ciphertexts in HBM, are asynchronous on the
+ * context stream and refuse a multi-device context. */
+#define TFHE_LUT_ENTRY_CONST 0xFFFFFFFFu
+int tfhe_gpu_lut_circuit_eval_select(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                     uint32_t m, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
+                                     const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                     const uint32_t *konst, const uint32_t *lut, const uint32_t *theta /*n_nodes or NULL*/,
+                                     const uint32_t *sel_off /*n_nodes+1*/, const uint32_t *sel_wire,
+                                     const uint32_t *sel_konst, size_t n_outputs, const uint32_t *out_wires,
+                                     uint32_t *outputs, uint32_t *levels);
+int tfhe_gpu_lut_circuit_eval_select_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                         uint32_t m, size_t n_inputs, const uint32_t *inputs_dev, size_t n_nodes,
+                                         const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                         const uint32_t *konst, const uint32_t *lut, const uint32_t *theta,
+                                         const uint32_t *sel_off, const uint32_t *sel_wire, const uint32_t *sel_konst,
+                                         size_t n_outputs, const uint32_t *out_wires, uint32_t *outputs_dev,
+                                         uint32_t *levels);
+int tfhe_gpu_lut_select_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool,
+                              size_t P, const uint32_t *term_off /*B+1*/, const uint32_t *term_src,
+                              const int32_t *term_coef, const uint32_t *konst /*B*/, const uint32_t *sel_src /*B*m*/,
+                              const uint32_t *sel_konst /*B*m*/, uint32_t *out /*B*(n+1)*/, size_t B);
+int tfhe_gpu_lut_select_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool_dev,
+                            size_t P, const uint32_t *term_off /*B+1*/, const uint32_t *term_src,
+                            const int32_t *term_coef, const uint32_t *konst /*B*/, const uint32_t *sel_src /*B*m*/,
+                            const uint32_t *sel_konst /*B*m*/, uint32_t *out_dev, size_t B);
+/* host only: the levels and depth of tfhe_gpu_lut_circuit_eval_select under the rule above (levels has n_nodes
+ * entries); it checks the wires, the offsets, the entry counts against m (a power of two >= 2) and theta on select
+ * nodes.  sel_off == NULL is tfhe_lut_circuit_schedule_multi. */
+int tfhe_lut_circuit_schedule_select(size_t n_inputs, size_t n_nodes, const uint32_t *term_off,
+                                     const uint32_t *term_wire, const uint32_t *theta /*n_nodes or NULL*/, uint32_t m,
+                                     const uint32_t *sel_off /*n_nodes+1*/, const uint32_t *sel_wire, uint32_t *levels,
+                                     uint32_t *depth);
 
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
 /* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,

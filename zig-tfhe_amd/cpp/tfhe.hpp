@@ -15,7 +15,8 @@
 //                        tfhe::PackingKey / tfhe::packTlwe (identityKeySwitching's arithmetic with TRLWE rows),
 //                        tfhe::packedScatterAdd / tfhe::packedWrite (writes into a tfhe::PackedTableLookup)
 //   lut/generator.zig -> tfhe::lutGenerate, tfhe::LutSet / tfhe::LutCircuit (per-item tables), tfhe::lutInterleave
-//                        (several tables from one blind rotation), tfhe::lutGenerate2 / tfhe::lutApply2 /
+//                        (several tables from one blind rotation; LutCircuit::select / node2 and tfhe::lutSelect:
+//                        nodes whose table is made of wires), tfhe::lutGenerate2 / tfhe::lutApply2 /
 //                        tfhe::lutSpread / tfhe::bootstrapLutEach (functions of two digits: a test vector
 //                        packed and spread on the device per item)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
@@ -920,6 +921,42 @@ class LutCircuit {
         n_wires_ += 1u << theta;
         return w;
     }
+    // A select node (include/tfhe_gpu.h "Select nodes"): the digit x = sum of terms + konst picks one of the
+    // m = entries.size() entries, each an earlier wire or a constant Torus word; its table is packed from the
+    // entries on the device.  One m per circuit; run / runDevice then take the packing key.
+    struct Entry {
+        Wire wire = TFHE_LUT_ENTRY_CONST;
+        Torus konst = 0;
+        Entry(Wire w) : wire(w) {}  // a wire
+        static Entry constant(Torus c) {
+            Entry e(TFHE_LUT_ENTRY_CONST);
+            e.konst = c;
+            return e;
+        }
+    };
+    Wire select(const std::vector<Term> &terms, const std::vector<Entry> &entries, Torus konst = 0) {
+        const uint32_t m = (uint32_t)entries.size();
+        if (m < 2 || (m & (m - 1)) || (m_ && m != m_))
+            throw Error(TFHE_ERR_INVALID, "LutCircuit: a select node has m entries, m a power of two >= 2, one m per circuit");
+        for (const Entry &e : entries)
+            if (e.wire != TFHE_LUT_ENTRY_CONST && e.wire >= n_wires_)
+                throw Error(TFHE_ERR_INVALID, "LutCircuit: select entries must read existing wires");
+        const Wire w = node(0, terms, konst);
+        m_ = m;
+        for (const Entry &e : entries) sel_wire_.push_back(e.wire), sel_konst_.push_back(e.konst);
+        const uint32_t last = sel_off_.back();
+        sel_off_.resize(lut_.size(), last);  // the ordinary nodes since the last select node: no entries
+        sel_off_.push_back((uint32_t)sel_wire_.size());
+        return w;
+    }
+    // f(x, y) of two m-ary digits: m ordinary nodes with the tables lut_base + i (lutGenerate2's rows) over y_terms
+    // and one select node over x_terms; returns the select node's wire.
+    Wire node2(uint32_t lut_base, const std::vector<Term> &x_terms, const std::vector<Term> &y_terms, uint32_t m) {
+        if (m_ && m != m_) throw Error(TFHE_ERR_INVALID, "LutCircuit: one m per circuit");
+        std::vector<Entry> entries;
+        for (uint32_t i = 0; i < m; i++) entries.push_back(Entry(node(lut_base + i, y_terms)));
+        return select(x_terms, entries);
+    }
     void output(Wire w) { outs_.push_back(w); }
     // Least significant digit first: per digit s = a_i + b_i + carry, message = LUT_msg(s), carry = LUT_carry(s);
     // returns the message wires, then the final carry as an extra digit.
@@ -958,30 +995,37 @@ class LutCircuit {
     // tfhe_lut_circuit_schedule(_multi): the level of every node; *depth (may be NULL) the largest
     std::vector<uint32_t> schedule(uint32_t *depth = nullptr) const {
         std::vector<uint32_t> levels(lut_.size());
-        check(tfhe_lut_circuit_schedule_multi(n_inputs_, lut_.size(), off_.data(), wire_.data(), theta(), levels.data(), depth),
+        check(tfhe_lut_circuit_schedule_select(n_inputs_, lut_.size(), off_.data(), wire_.data(), theta(), m_, selOff(),
+                                               sel_wire_.data(), levels.data(), depth),
               "LutCircuit.schedule");
         return levels;
     }
+    // key: the packing key of a circuit with select nodes (NULL without one)
     std::vector<TLWELv0> run(const CloudKey &ck, const LutSet &set, const std::vector<TLWELv0> &inputs,
-                             uint32_t *levels = nullptr) const {
+                             uint32_t *levels = nullptr, const PackingKey *key = nullptr) const {
         if (inputs.size() != n_inputs_) throw Error(TFHE_ERR_INVALID, "LutCircuit: wrong number of inputs");
+        if (m_ && !key) throw Error(TFHE_ERR_INVALID, "LutCircuit: select nodes need a packing key");
         const size_t w = ck.params().n + 1;
         std::vector<Torus> in(inputs.size() * w), out(outs_.size() * w);
         for (size_t k = 0; k < inputs.size(); k++) std::copy(inputs[k].p.begin(), inputs[k].p.end(), in.begin() + k * w);
-        check(tfhe_gpu_lut_circuit_eval_multi(ck.ctx(), set.get(), n_inputs_, in.data(), lut_.size(), off_.data(),
-                                              wire_.data(), coef_.data(), konst_.data(), lut_.data(), theta(), outs_.size(),
-                                              outs_.data(), out.data(), levels),
+        check(tfhe_gpu_lut_circuit_eval_select(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_, in.data(),
+                                               lut_.size(), off_.data(), wire_.data(), coef_.data(), konst_.data(),
+                                               lut_.data(), theta(), selOff(), sel_wire_.data(), sel_konst_.data(),
+                                               outs_.size(), outs_.data(), out.data(), levels),
               "LutCircuit.run", ck.ctx());
         std::vector<TLWELv0> r(outs_.size(), TLWELv0(ck.params().n));
         for (size_t k = 0; k < outs_.size(); k++) std::copy(out.begin() + k * w, out.begin() + (k + 1) * w, r[k].p.begin());
         return r;
     }
     // Inputs and outputs in HBM; async on the context stream (tfhe_gpu_lut_circuit_eval_dev).  Returns the depth.
-    uint32_t runDevice(const CloudKey &ck, const LutSet &set, const Torus *inputs_dev, Torus *outputs_dev) const {
+    uint32_t runDevice(const CloudKey &ck, const LutSet &set, const Torus *inputs_dev, Torus *outputs_dev,
+                       const PackingKey *key = nullptr) const {
         uint32_t levels = 0;
-        check(tfhe_gpu_lut_circuit_eval_multi_dev(ck.ctx(), set.get(), n_inputs_, inputs_dev, lut_.size(), off_.data(),
-                                                  wire_.data(), coef_.data(), konst_.data(), lut_.data(), theta(),
-                                                  outs_.size(), outs_.data(), outputs_dev, &levels),
+        if (m_ && !key) throw Error(TFHE_ERR_INVALID, "LutCircuit: select nodes need a packing key");
+        check(tfhe_gpu_lut_circuit_eval_select_dev(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_,
+                                                   inputs_dev, lut_.size(), off_.data(), wire_.data(), coef_.data(),
+                                                   konst_.data(), lut_.data(), theta(), selOff(), sel_wire_.data(),
+                                                   sel_konst_.data(), outs_.size(), outs_.data(), outputs_dev, &levels),
               "LutCircuit.runDevice", ck.ctx());
         return levels;
     }
@@ -992,10 +1036,48 @@ class LutCircuit {
   private:
     // NULL without a multi-output node: the _multi entries are then the single-output ones
     const uint32_t *theta() const { return multi_ ? theta_.data() : nullptr; }
-    uint32_t n_inputs_ = 0, n_wires_ = 0;
+    // NULL without a select node (the _select entries are then the _multi ones); else one offset per node and one
+    // more, the nodes behind the last select node without entries
+    const uint32_t *selOff() const {
+        if (!m_) return nullptr;
+        const uint32_t last = sel_off_.back();
+        sel_off_.resize(lut_.size() + 1, last);
+        return sel_off_.data();
+    }
+    uint32_t n_inputs_ = 0, n_wires_ = 0, m_ = 0;
     bool multi_ = false;
-    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, theta_, outs_;
+    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, theta_, outs_, sel_wire_, sel_konst_;
+    mutable std::vector<uint32_t> sel_off_{0};
     std::vector<int32_t> coef_;
 };
+
+// tfhe_gpu_lut_select_batch: the flat form of the select node over a pool.  Node b bootstraps the combination of its
+// terms (pool indices) and konst with the test vector packed from its m entries, pool indices or constants.
+struct LutSelectNode {
+    std::vector<LutCircuit::Term> terms;
+    std::vector<LutCircuit::Entry> entries;
+    Torus konst = 0;
+};
+inline std::vector<TLWELv0> lutSelect(const CloudKey &ck, const PackingKey &key, uint32_t m, const std::vector<TLWELv0> &pool,
+                                      const std::vector<LutSelectNode> &nodes) {
+    const size_t B = nodes.size(), w = ck.params().n + 1;
+    std::vector<Torus> x(pool.size() * w), out(B * w);
+    std::vector<uint32_t> off{0}, src, konst, sel_src, sel_konst;
+    std::vector<int32_t> coef;
+    for (size_t k = 0; k < pool.size(); k++) std::copy(pool[k].p.begin(), pool[k].p.end(), x.begin() + k * w);
+    for (const LutSelectNode &nd : nodes) {
+        if (nd.entries.size() != m) throw Error(TFHE_ERR_INVALID, "lutSelect: a node has m entries");
+        for (const LutCircuit::Term &t : nd.terms) src.push_back(t.first), coef.push_back(t.second);
+        off.push_back((uint32_t)src.size());
+        konst.push_back(nd.konst);
+        for (const LutCircuit::Entry &e : nd.entries) sel_src.push_back(e.wire), sel_konst.push_back(e.konst);
+    }
+    check(tfhe_gpu_lut_select_batch(ck.ctx(), key.get(), m, x.data(), pool.size(), off.data(), src.data(), coef.data(),
+                                    konst.data(), sel_src.data(), sel_konst.data(), out.data(), B),
+          "lut_select", ck.ctx());
+    std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
+    return r;
+}
 
 }  // namespace tfhe

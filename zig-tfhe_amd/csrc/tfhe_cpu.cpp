@@ -338,8 +338,24 @@ static const char *lut_output_offsets(size_t n_nodes, const uint32_t *theta, std
 
 uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta) { return theta ? 32 - (p.nbit + 1) + theta : 0; }
 
+// nullptr, or what is wrong with the select descriptors themselves (m, the offsets, a theta on a select node)
+static const char *check_lut_select(size_t n_nodes, const uint32_t *theta, const LutSelect &sel) {
+    if (sel.m < 2 || (sel.m & (sel.m - 1))) return "m must be a power of two >= 2";
+    if (!sel.off) return "null select offsets";
+    if (sel.off[0] != 0) return "sel_off[0] is not 0";
+    for (size_t g = 0; g < n_nodes; g++) {
+        if (sel.off[g + 1] < sel.off[g]) return "sel_off is not monotone";
+        const uint32_t cnt = sel.off[g + 1] - sel.off[g];
+        if (cnt != 0 && cnt != sel.m) return "a node's entry count is neither 0 nor m";
+        if (cnt && theta && theta[g] != 0) return "a select node has theta != 0";
+    }
+    if (sel.off[n_nodes] && !sel.wire) return "null select entries";
+    return nullptr;
+}
+
 const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
-                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta) {
+                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta,
+                                const LutSelect *sel) {
     level.assign(n_nodes, 0);
     depth = 0;
     if (n_nodes == 0) return nullptr;
@@ -347,57 +363,81 @@ const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t 
     if (const char *why = lut_output_offsets(n_nodes, theta, o)) return why;
     if (n_inputs + o[n_nodes] > 0xFFFFFFFFull) return "too many wires";
     if (term_off[0] != 0) return "term_off[0] is not 0";
-    std::vector<uint32_t> node_of;  // multi-output form: the node that drives a wire
-    if (theta) node_of.resize(o[n_nodes]);
+    if (sel)
+        if (const char *why = check_lut_select(n_nodes, theta, *sel)) return why;
+    const bool by_node = theta || sel;  // both entries number the wires through theta (NULL: one wire per node)
+    std::vector<uint32_t> node_of;      // multi-output form: the node that drives a wire
+    if (by_node) node_of.resize(o[n_nodes]);
     for (size_t g = 0; g < n_nodes; g++) {
         if (term_off[g + 1] < term_off[g]) return "term_off is not monotone";
         uint32_t r = 0;
         for (size_t k = term_off[g]; k < term_off[g + 1]; k++) {
             const size_t w = term_wire[k];
             if (w >= n_inputs + o[g]) return "term wire is not an earlier wire";
-            if (w >= n_inputs) r = std::max(r, level[theta ? node_of[w - n_inputs] : w - n_inputs]);
+            if (w >= n_inputs) r = std::max(r, level[by_node ? node_of[w - n_inputs] : w - n_inputs]);
+        }
+        for (size_t j = sel ? sel->off[g] : 0; sel && j < sel->off[g + 1]; j++) {
+            const size_t w = sel->wire[j];
+            if (w == TFHE_LUT_ENTRY_CONST) continue;
+            if (w >= n_inputs + o[g]) return "entry wire is not an earlier wire";
+            if (w >= n_inputs) r = std::max(r, level[node_of[w - n_inputs]]);
         }
         level[g] = r + 1;
         depth = std::max(depth, level[g]);
-        if (theta) std::fill(node_of.begin() + o[g], node_of.begin() + o[g + 1], (uint32_t)g);
+        if (by_node) std::fill(node_of.begin() + o[g], node_of.begin() + o[g + 1], (uint32_t)g);
     }
     return nullptr;
 }
 
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
-                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl, const uint32_t *theta) {
+                             size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl, const uint32_t *theta,
+                             const LutSelect *sel) {
     std::vector<size_t> fo;  // node g's first output wire, relative to n_inputs
     if (const char *why = lut_output_offsets(n_nodes, theta, fo)) return why;
     const size_t W = n_inputs + fo[n_nodes];
     if (W > 0xFFFFFFFFull) return "too many wires";
-    if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth, theta))
+    if (T >= LUT_TV_EACH) return "the set has 2^31 tables or more";  // the selector's top bit names the other base
+    if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth, theta, sel))
         return why;
-    for (size_t g = 0; g < n_nodes; g++)
+    if (sel && n_nodes && sel->off[n_nodes] && !sel->konst) return "null select constants";
+    auto is_sel = [&](size_t g) { return sel && sel->off[g + 1] != sel->off[g]; };
+    for (size_t g = 0; g < n_nodes; g++) {
+        if (is_sel(g) && lut[g] != 0) return "a select node has lut != 0";
         if (lut[g] >= T) return "table index >= the set's size";
+    }
     for (size_t o = 0; o < n_outputs; o++)
         if (out_wires[o] >= W) return "output wire out of range";
-    // slots in level order (a counting sort of the nodes by level keeps node order inside a level)
+    // slots in level order (a counting sort of the nodes by level, a level's ordinary nodes ahead of its
+    // select nodes, keeps node order inside either group)
+    const uint32_t m = sel ? sel->m : 0;
     pl.first.assign((size_t)pl.depth + 1, 0);
     pl.ofirst.assign((size_t)pl.depth + 1, 0);
+    pl.sfirst.assign((size_t)pl.depth + 1, 0);
+    pl.nsel.assign(pl.depth, 0);
     for (size_t g = 0; g < n_nodes; g++) {
         pl.first[pl.level[g]]++;  // level lv's count at [lv]
         pl.ofirst[pl.level[g]] += (uint32_t)(fo[g + 1] - fo[g]);
+        if (is_sel(g)) pl.sfirst[pl.level[g]]++, pl.nsel[pl.level[g] - 1]++;
     }
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {  // -> its end, its start at [lv - 1]
         pl.first[lv] += pl.first[lv - 1];
         pl.ofirst[lv] += pl.ofirst[lv - 1];
+        pl.sfirst[lv] += pl.sfirst[lv - 1];
     }
     pl.order.assign(n_nodes, 0);
     pl.slot.assign(W, 0);
     for (size_t w = 0; w < n_inputs; w++) pl.slot[w] = (uint32_t)w;
     {
-        std::vector<uint32_t> next(pl.first.begin(), pl.first.end()), onext(pl.ofirst.begin(), pl.ofirst.end());
+        std::vector<uint32_t> next(pl.first.begin(), pl.first.end()), snext(pl.depth);
+        for (uint32_t lv = 1; lv <= pl.depth; lv++) snext[lv - 1] = pl.first[lv] - pl.nsel[lv - 1];
         for (size_t g = 0; g < n_nodes; g++) {
-            const uint32_t lv = pl.level[g], at = next[lv - 1]++;
-            pl.order[at] = (uint32_t)g;
-            for (size_t j = fo[g]; j < fo[g + 1]; j++) pl.slot[n_inputs + j] = (uint32_t)(n_inputs + onext[lv - 1]++);
+            const uint32_t lv = pl.level[g];
+            pl.order[is_sel(g) ? snext[lv - 1]++ : next[lv - 1]++] = (uint32_t)g;
         }
+        size_t out_slot = n_inputs;  // the levels are consecutive in `order`, and so are their output slots
+        for (size_t at = 0; at < n_nodes; at++)
+            for (size_t j = fo[pl.order[at]]; j < fo[pl.order[at] + 1]; j++) pl.slot[n_inputs + j] = (uint32_t)out_slot++;
     }
     // per-level CSR descriptors over slots, concatenated in evaluation order
     const size_t terms = n_nodes ? term_off[n_nodes] : 0;
@@ -408,12 +448,17 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     pl.lut.clear();
     pl.theta.clear();
     pl.fan.clear();
+    pl.tv_sel.clear();
+    pl.e_off.assign(1, 0);
+    pl.e_src.clear();
+    pl.e_konst.clear();
     pl.off.reserve(n_nodes + pl.depth);
     pl.src.reserve(terms);
     pl.coef.reserve(terms);
     pl.fan.reserve(2 * fo[n_nodes]);
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
         pl.off.push_back((uint32_t)pl.src.size());
+        uint32_t k_sel = 0;
         for (uint32_t at = pl.first[lv - 1]; at < pl.first[lv]; at++) {
             const uint32_t g = pl.order[at];
             for (size_t k = term_off[g]; k < term_off[g + 1]; k++) {
@@ -424,9 +469,16 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
             pl.konst.push_back(konst[g]);
             pl.lut.push_back(lut[g]);
             pl.theta.push_back(theta ? theta[g] : 0u);
+            pl.tv_sel.push_back(is_sel(g) ? LUT_TV_EACH | k_sel++ : lut[g]);
             for (uint32_t j = 0; j < fo[g + 1] - fo[g]; j++) {
                 pl.fan.push_back(at - pl.first[lv - 1]);
                 pl.fan.push_back(j);
+            }
+            for (uint32_t i = 0; is_sel(g) && i < m; i++) {  // the node's entries, in pack order
+                const uint32_t e = sel->wire[sel->off[g] + i];
+                if (e != TFHE_LUT_ENTRY_CONST) pl.e_src.push_back(pl.slot[e]);
+                pl.e_konst.push_back(e == TFHE_LUT_ENTRY_CONST ? sel->konst[sel->off[g] + i] : 0u);
+                pl.e_off.push_back((uint32_t)pl.e_src.size());
             }
         }
     }
@@ -742,6 +794,21 @@ int tfhe_lut_circuit_schedule_multi(size_t n_inputs, size_t n_nodes, const uint3
     std::vector<uint32_t> level;
     uint32_t d = 0;
     if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d, theta)) return TFHE_ERR_INVALID;
+    std::copy(level.begin(), level.end(), levels);
+    if (depth) *depth = d;
+    return TFHE_OK;
+}
+
+int tfhe_lut_circuit_schedule_select(size_t n_inputs, size_t n_nodes, const uint32_t *term_off,
+                                     const uint32_t *term_wire, const uint32_t *theta, uint32_t m,
+                                     const uint32_t *sel_off, const uint32_t *sel_wire, uint32_t *levels,
+                                     uint32_t *depth) {
+    if (!sel_off) return tfhe_lut_circuit_schedule_multi(n_inputs, n_nodes, term_off, term_wire, theta, levels, depth);
+    if (n_nodes && (!term_off || !levels || (term_off[n_nodes] && !term_wire))) return TFHE_ERR_INVALID;
+    const LutSelect sel{m, sel_off, sel_wire, nullptr};
+    std::vector<uint32_t> level;
+    uint32_t d = 0;
+    if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d, theta, &sel)) return TFHE_ERR_INVALID;
     std::copy(level.begin(), level.end(), levels);
     if (depth) *depth = d;
     return TFHE_OK;

@@ -73,8 +73,16 @@ const char *check_lut_nodes(size_t B, size_t P, size_t T, const uint32_t *term_o
 // Multi-output form (theta != nullptr, n_nodes entries, each <= TFHE_LUT_MULTI_MAX_LOG): node g
 // drives the 2^theta[g] wires n_inputs + o_g + j, o_g = sum_{g' < g} 2^theta[g'], and reads wires
 // below n_inputs + o_g only; a wire's level is its node's.
+// Select nodes (sel != nullptr, include/tfhe_gpu.h "Select nodes"): node g has the sel->off[g+1] - sel->off[g]
+// entries sel->wire[..], 0 (an ordinary node) or m of them; an entry is TFHE_LUT_ENTRY_CONST or a wire below
+// n_inputs + o_g, and counts towards the node's level as a term wire does.  A select node has theta 0.
+struct LutSelect {
+    uint32_t m;
+    const uint32_t *off, *wire, *konst;  // konst may be NULL where only levels are asked for
+};
 const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
-                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta = nullptr);
+                                std::vector<uint32_t> &level, uint32_t &depth, const uint32_t *theta = nullptr,
+                                const LutSelect *sel = nullptr);
 // round_theta's shift, s = 32 - (log2 N + 1) + theta; 0 for theta = 0 (the identity, not the formula)
 uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta);
 
@@ -89,6 +97,15 @@ uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta);
 // contiguous run of slots n_inputs + ofirst[lv-1] .. n_inputs + ofirst[lv), node by node in evaluation
 // order, so the level's key switch writes the wire table directly.  fan holds one (node's index in its
 // level, coefficient) pair per output slot, in slot order.  Without theta, ofirst == first.
+// Select nodes: a level's run of `order` holds its ordinary nodes (node order), then its select nodes
+// (node order), nsel[lv-1] of them, and the output slots follow that order, so level_out stays one run.
+// sfirst counts the select nodes below a level as first counts the nodes.  tv_sel is, per node in evaluation
+// order, where the item's test vector comes from in the level's bootstrap launch: the table lut for an
+// ordinary node, LUT_TV_EACH | k for the level's k-th select node (test vector k of the level's own).
+// The entries are one CSR over all select nodes in evaluation order, m per node in pack order: entry j
+// has the e_off[j+1] - e_off[j] <= 1 terms e_src[..] (a slot, coefficient 1) and the constant e_konst[j],
+// which is what the combine kernel takes; level lv's start at sfirst[lv-1] * m.
+constexpr uint32_t LUT_TV_EACH = 0x80000000u;
 struct LutCircuitPlan {
     uint32_t depth = 0;
     std::vector<uint32_t> level;  // per node
@@ -101,11 +118,15 @@ struct LutCircuitPlan {
     std::vector<uint32_t> theta;   // per node, evaluation order (all 0 without theta)
     std::vector<uint32_t> ofirst;  // depth + 1 entries
     std::vector<uint32_t> fan;     // 2 words per output slot
+    std::vector<uint32_t> nsel;    // per level (depth entries)
+    std::vector<uint32_t> sfirst;  // depth + 1 entries
+    std::vector<uint32_t> tv_sel;  // per node, evaluation order
+    std::vector<uint32_t> e_off, e_src, e_konst;  // sfirst[depth] * m + 1 offsets, the wire entries' slots, one constant per entry
 };
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
                              size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl,
-                             const uint32_t *theta = nullptr);
+                             const uint32_t *theta = nullptr, const LutSelect *sel = nullptr);
 
 // ---- Packing key switch (tfhe_pack_tlwe here; tfhe_pack.cpp runs it on the device) ----
 // The shapes with the one-hot GEMM form (ks_gemm_supported, tfhe_kernels.hip): basebit 2 with

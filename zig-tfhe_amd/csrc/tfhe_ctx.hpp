@@ -350,7 +350,8 @@ int upload_ksk(Device &d, const uint32_t *ksk);                       // host KS
 int key_loaded(Device &d, bool from_keygen);                          // the end of every key load on device 0: admission
 int key_fingerprint(Device &d, uint64_t &bk, uint64_t &ksk);
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b, const uint32_t *testvec_dev,
-                      uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr, const uint32_t *tv_sel = nullptr);
+                      uint32_t *out, size_t B, int kind, const uint32_t *idx = nullptr, const uint32_t *tv_sel = nullptr,
+                      const uint32_t *tv_each = nullptr);
 int sync_check(Device &d);
 int d2h_sync(Device &d, void *dst, const void *src, size_t bytes);
 // A circuit plan on one device, in slices of f: the wire table with the inputs, the gather indices and the op codes.

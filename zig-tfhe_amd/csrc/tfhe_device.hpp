@@ -1176,7 +1176,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate(
     const uint32_t *A = in_a + ia * (size_t)(n + 1);
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
-    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table (the clamped g: a tail copy reads a real entry)
+    if constexpr (TV) testvec = item_testvec(P, testvec, g);  // the item's own table (the clamped g: a tail copy reads a real entry)
 
     if (tid < 4) s_sync[tid] = 0u;
     for (int x = tid; x < 511; x += 256) s_tw[x] = TT.tw[x];

@@ -124,7 +124,7 @@ static int ensure_tie_flags(Device &d, size_t B) {
 // Blind rotation (+ key switch for RUN_BOOTSTRAP) over device buffers, async.
 int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const uint32_t *b,
                       const uint32_t *testvec_dev, uint32_t *out, size_t B, int kind, const uint32_t *idx,
-                      const uint32_t *tv_sel) {
+                      const uint32_t *tv_sel, const uint32_t *tv_each) {
     const bool key_switch = kind == RUN_BOOTSTRAP;
     const int out_mode = kind == RUN_BOOTSTRAP ? BR_OUT_LV1 : kind == RUN_TRLWE ? BR_OUT_TRLWE : BR_OUT_LV0_EXTRACT2;
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
@@ -137,6 +137,7 @@ int run_bootstrap_dev(Device &d, const uint8_t *ops, const uint32_t *a, const ui
     KParams K = d.K;
     K.tie_flags = d.s_ties;
     K.tv_sel = tv_sel;  // LUT circuits: B table indices into testvec_dev (device), or NULL
+    set_tv_each(K, tv_each);  // select nodes: the base of the entries of tv_sel with TV_SEL_EACH set, or NULL
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     if (d.profiling) {
         while (d.events.size() < d.ev_used + 3) {
@@ -372,7 +373,7 @@ static int init_device(Device &d, const tfhe_params &p, int device) {
     d.P = p;
     d.device = device;
     d.K = KParams{(int)p.n, (int)p.N, (int)p.L, (int)p.bgbit, (int)p.basebit,
-                  (int)p.iks_t, 0, ks_stride_for((int)p.n), nullptr, 0u, nullptr, 0};
+                  (int)p.iks_t, 0, ks_stride_for((int)p.n), nullptr, 0u, 0u, nullptr, 0};
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return hip_fail(d, e, "hipSetDevice");
     e = hipStreamCreateWithFlags(d.own_stream.make(device), hipStreamNonBlocking);

@@ -29,6 +29,13 @@ struct KParams {
     // items the margin guard's recompute redid (cumulative).
     uint32_t *err;
     uint32_t spin_cap;  // polls before a slot-counter wait gives up (TFHE_OPT_BR_SPIN_CAP; 0 = default)
+    // A second base for the TV = true instantiations (select nodes of LUT circuits),
+    // in two halves that fill the block's two padding words (this one and the one behind `fallback`):
+    // an entry of tv_sel with TV_SEL_EACH set reads tv_each + (entry & ~TV_SEL_EACH) * 2N, a test
+    // vector the call built in its own frame, so one launch mixes the set's tables with those.  The
+    // block keeps its size and every other member its place, so every kernel that does not read the
+    // halves compiles to the code it had (a member appended moved the arguments behind the block).
+    uint32_t tv_each_lo = 0;
     // Near-tie flags of the fused arithmetic's margin guard,
     // one byte per item of a blind-rotation launch, all zero between launches:
     // a fused kernel sets tie_flags[g] when item g rounded a value 1/4 or more off
@@ -39,6 +46,7 @@ struct KParams {
     // the fused arithmetic at load (key admission).
     uint8_t *tie_flags;
     int fallback;
+    uint32_t tv_each_hi = 0;
     // Per-item test vector (LUT circuits): NULL, or one entry per item of the
     // launch; item g then starts from the TRLWELv1 at testvec + tv_sel[g] * 2N.  An item has
     // its own wave or workgroup in every form, so the offset is wave-uniform.  The host checks
@@ -47,6 +55,18 @@ struct KParams {
     // changed the default kernel's registers and schedule and cost the bench 2.5 %.
     const uint32_t *tv_sel = nullptr;
 };
+constexpr uint32_t TV_SEL_EACH = 0x80000000u;
+static_assert(sizeof(KParams) == 72, "KParams: tv_each_lo / tv_each_hi fill padding, the block keeps its size");
+// Item g's test vector in a TV = true instantiation (g is wave-uniform, so these are scalar loads).
+__device__ __forceinline__ const uint32_t *item_testvec(const KParams &P, const uint32_t *testvec, size_t g) {
+    const uint32_t s = P.tv_sel[g];
+    const uint32_t *each = reinterpret_cast<const uint32_t *>((uint64_t)P.tv_each_hi << 32 | P.tv_each_lo);
+    return ((s & TV_SEL_EACH) ? each : testvec) + (size_t)(s & ~TV_SEL_EACH) * 2048;
+}
+inline void set_tv_each(KParams &P, const uint32_t *p) {
+    P.tv_each_lo = (uint32_t)(uintptr_t)p;
+    P.tv_each_hi = (uint32_t)((uint64_t)(uintptr_t)p >> 32);
+}
 
 // Bits of the device error word.
 enum DevErr : uint32_t {

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_octo(
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
     const uint32_t pairs = (uint32_t)n * L;
-    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table (the clamped g)
+    if constexpr (TV) testvec = item_testvec(P, testvec, g);  // the item's own table (the clamped g)
 
     if (lds_layout_bad(smem)) {
         if (tid == 0) __hip_atomic_fetch_or(P.err, (uint32_t)DEV_ERR_LDS_LAYOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_wide(
     const uint32_t *A = in_a + ia * (size_t)(n + 1);
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
-    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;  // the item's own table
+    if constexpr (TV) testvec = item_testvec(P, testvec, g);  // the item's own table
     const size_t trgsw = (size_t)2 * L * 1024;  // double2 per BK[i]
 
     for (int x = tid; x < 511; x += 512) s_tw[x] = TT.tw[x];

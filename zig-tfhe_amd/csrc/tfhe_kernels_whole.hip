@@ -160,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     const uint32_t *Bv = in_b ? in_b + ib * (size_t)(n + 1) : A;
     const int op = ops ? (int)ops[g] : 255;
     // the item's own table (the clamped g), for the gate wave's polynomial a and the loader wave's b alike
-    if constexpr (TV) testvec += (size_t)P.tv_sel[g] * 2048;
+    if constexpr (TV) testvec = item_testvec(P, testvec, g);
     const uint32_t spin_cap = P.spin_cap ? P.spin_cap : BR_SPIN_CAP_DEFAULT;
     const uint32_t msbs = digit_msbs(L, P.bgbit);
     const uint32_t pairs = (uint32_t)n * L;

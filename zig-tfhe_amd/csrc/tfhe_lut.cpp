@@ -8,7 +8,10 @@
 // coefficients in front of one key switch over the outputs.  The bivariate node
 // (lut_apply2_on) chains level 1, the pack (pack_launch, tfhe_pack.cpp), the spread
 // (k_lut_spread) and a bootstrap whose per-item selector is the identity over the
-// chunk's own test vectors.  Everything here runs on the context's first device.
+// chunk's own test vectors.  A select node (select_testvecs) is the same chain inside the
+// circuit evaluator, its m tables' outputs replaced by any earlier wires or constants, and
+// shares its level's bootstrap launch with the ordinary nodes (KParams::tv_each).
+// Everything here runs on the context's first device.
 #include "tfhe_gpu.h"
 
 #include <algorithm>
@@ -115,23 +118,74 @@ static int lut_apply_multi_on(Device &d, const tfhe_gpu_lut_set &set, const uint
     return rc ? rc : io.finish();
 }
 
+static_assert(LUT_TV_EACH == TV_SEL_EACH, "the planner's selector bit is the kernels'");
+
+// The selector of a bootstrap whose item g reads testvecs + g * 2N: 0 .. B-1, appended to a call's descriptors.
+static size_t add_iota(DescBlob &blob, size_t B) {
+    const size_t at = blob.words.size();
+    for (size_t i = 0; i < B; i++) blob.words.push_back((uint32_t)i);
+    return at;
+}
+
+// The test vectors of ns select nodes (include/tfhe_gpu.h "Select nodes") into tv (ns TRLWELv1): per chunk of
+// nodes the m entries of each are staged in pack order (the combine kernel with at most one term: a wire is
+// copied, a constant becomes a trivial ciphertext) and packed into the slots i*w; then one spread in place over
+// all of them.  The chunk is the pack's own (pack_chunk_items) in whole nodes, as in lut_apply2_on, and every
+// step is per item, so chunking changes no word.  e_off / e_konst start at the first node's first entry, e_src and
+// ones (a 1 per wire entry) are whole arrays the offsets index, coef_dev holds the m slot coefficients; all device.
+static int select_testvecs(Device &d, const tfhe_gpu_packing_key &pk, uint32_t m, const uint32_t *pool,
+                           const uint32_t *e_off, const uint32_t *e_src, const int32_t *ones, const uint32_t *e_konst,
+                           const uint32_t *coef_dev, uint32_t *tv, size_t ns) {
+    const size_t w = tlwe0_words(d.P), N = d.P.N;
+    const size_t nodes = std::min(ns, std::max<size_t>(1, pack_chunk_items(d, ns * m, (int)pk.basebit) / m));
+    Frame f(d);
+    uint32_t *g = f.ks_input<uint32_t>(nodes * m * w, /*pack*/ true);
+    int rc = f.rc();
+    if (rc) return rc;
+    for (size_t b0 = 0; b0 < ns; b0 += nodes) {
+        const size_t nb = std::min(nodes, ns - b0);
+        HIPCHK(d, launch_lut_combine(d.K, pool, e_off + b0 * m, e_src, ones, e_konst + b0 * m, g, nb * m, d.stream));
+        if ((rc = pack_launch(d, pk, g, coef_dev, m, tv + b0 * 2 * N, nb))) return rc;
+    }
+    HIPCHK(d, launch_lut_spread(tv, (uint32_t)(N / m), (uint32_t)(2 * N - N / (2 * m)), tv, ns, d.stream));
+    return TFHE_OK;
+}
+
+// The pack's slot coefficients i * N/m of a select node, appended to a call's descriptors.
+static size_t add_slot_coefs(DescBlob &blob, uint32_t N, uint32_t m) {
+    const size_t at = blob.reserve(m);
+    for (uint32_t i = 0; i < m; i++) blob.words[at + i] = i * (N / m);
+    return at;
+}
+
 // A whole LUT circuit: one combine and one bootstrap launch per level into the
 // wire table (in the plan's slot order), the outputs gathered at the end; a level's temporaries go with its frame.
+// A level with select nodes (pk, m: theirs) builds their test vectors first; its one bootstrap launch then reads,
+// item by item, the set or those (the plan's tv_sel, KParams::tv_each).
 static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
-                          const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev) {
+                          const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev,
+                          const tfhe_gpu_packing_key *pk = nullptr, uint32_t m = 0) {
     if (n_nodes && !d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t w = tlwe0_words(d.P), W = pl.slot.size();  // inputs + every node's outputs
     // multi-output nodes anywhere: round_theta's shift per node (evaluation order) and the plan's fan-out pairs
     const bool multi = std::any_of(pl.theta.begin(), pl.theta.end(), [](uint32_t t) { return t != 0; });
+    const bool select = pl.depth && pl.sfirst[pl.depth] != 0;
     std::vector<uint32_t> shift;
     if (multi)
         for (uint32_t t : pl.theta) shift.push_back(lut_round_shift(d.P, t));
+    const std::vector<uint32_t> ones(pl.e_src.size(), 1u);
     DescBlob blob;
+    // tv_sel is lut on every ordinary node, so it serves the multi-output launches as their table indices too
     const size_t off_at = blob.add(pl.off.data(), pl.off.size()), src_at = blob.add(pl.src.data(), pl.src.size()),
                  coef_at = blob.add(pl.coef.data(), pl.coef.size()), konst_at = blob.add(pl.konst.data(), n_nodes),
-                 lut_at = blob.add(pl.lut.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs),
+                 lut_at = blob.add(pl.tv_sel.data(), n_nodes), out_at = blob.add(pl.out_slots.data(), n_outputs),
                  shift_at = blob.add(shift.data(), shift.size()),
-                 fan_at = multi ? blob.add(pl.fan.data(), pl.fan.size()) : 0;
+                 fan_at = multi ? blob.add(pl.fan.data(), pl.fan.size()) : 0,
+                 eoff_at = select ? blob.add(pl.e_off.data(), pl.e_off.size()) : 0,
+                 esrc_at = select ? blob.add(pl.e_src.data(), pl.e_src.size()) : 0,
+                 one_at = select ? blob.add(ones.data(), ones.size()) : 0,
+                 ekonst_at = select ? blob.add(pl.e_konst.data(), pl.e_konst.size()) : 0,
+                 pcoef_at = select ? add_slot_coefs(blob, d.P.N, m) : 0;
     Frame f(d);
     Io io{f, dev};
     uint32_t *wires = f.take<uint32_t>(W * w);
@@ -141,29 +195,81 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     if (n_inputs)
         HIPCHK(d, hipMemcpyAsync(wires, inputs, n_inputs * w * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                  d.stream));
+    const int32_t *coef = reinterpret_cast<const int32_t *>(desc + coef_at);
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
         const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at, oat = pl.ofirst[lv - 1], no = pl.ofirst[lv] - oat;
+        const size_t ns = pl.nsel[lv - 1], nord = nb - ns;  // the level's run: its ordinary nodes, then its select nodes
+        const uint32_t *off = desc + off_at + at + (lv - 1);
         uint32_t *level_out = wires + (n_inputs + oat) * w;  // the level's outputs: one run of slots
-        if (no != nb) {  // a theta > 0 in this level
-            rc = lut_multi_launch(d, set, wires, desc + off_at + at + (lv - 1), desc + src_at,
-                                  reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at,
-                                  desc + lut_at + at, desc + shift_at + at, desc + fan_at + 2 * oat, level_out, nb, no);
-            if (rc) return rc;
-            continue;
-        }
-        // reads slots below this level's first (earlier wires), writes the level's staging slice
+        // reads slots below this level's first (earlier wires), writes the level's staging slices
         Frame level(d);
-        uint32_t *x = level.take<uint32_t>(nb * w);
+        uint32_t *tv = nullptr;
+        if (ns) {
+            tv = level.take<uint32_t>(ns * 2 * (size_t)d.P.N);
+            if ((rc = level.rc())) return rc;
+            const size_t e0 = (size_t)pl.sfirst[lv - 1] * m;
+            rc = select_testvecs(d, *pk, m, wires, desc + eoff_at + e0, desc + esrc_at,
+                                 reinterpret_cast<const int32_t *>(desc + one_at), desc + ekonst_at + e0,
+                                 desc + pcoef_at, tv, ns);
+            if (rc) return rc;
+        }
+        // a theta > 0 in this level: the ordinary nodes as before, the select nodes in one launch of their own
+        const bool split = no != nb;
+        if (split) {
+            rc = lut_multi_launch(d, set, wires, off, desc + src_at, coef, desc + konst_at + at, desc + lut_at + at,
+                                  desc + shift_at + at, desc + fan_at + 2 * oat, level_out, nord, no - ns);
+            if (rc) return rc;
+            if (!ns) continue;
+        }
+        const size_t skip = split ? nord : 0, items = nb - skip;
+        uint32_t *x = level.take<uint32_t>(items * w);
         if ((rc = level.rc())) return rc;
-        HIPCHK(d, launch_lut_combine(d.K, wires, desc + off_at + at + (lv - 1), desc + src_at,
-                                     reinterpret_cast<const int32_t *>(desc + coef_at), desc + konst_at + at, x, nb,
+        HIPCHK(d, launch_lut_combine(d.K, wires, off + skip, desc + src_at, coef, desc + konst_at + at + skip, x, items,
                                      d.stream));
-        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, level_out, nb, RUN_BOOTSTRAP, nullptr,
-                               desc + lut_at + at);
+        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, level_out + (no - items) * w, items, RUN_BOOTSTRAP,
+                               nullptr, desc + lut_at + at + skip, tv);
         if (rc) return rc;
     }
     if (n_outputs) HIPCHK(d, launch_tlwe_gather(d.K, wires, desc + out_at, outputs, n_outputs, false, d.stream));
     return io.finish();
+}
+
+// B select nodes over a pool of P ciphertexts (checked descriptors): x, the B test vectors, and the bootstrap
+// whose item b reads test vector b.
+static int lut_select_on(Device &d, const tfhe_gpu_packing_key &pk, uint32_t m, const uint32_t *pool, size_t P,
+                         const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                         const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out,
+                         size_t B, bool dev) {
+    if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), terms = term_off[B], E = B * m;
+    std::vector<uint32_t> e_off(1, 0u), e_src, e_konst(E);
+    for (size_t j = 0; j < E; j++) {
+        const bool c = sel_src[j] == TFHE_LUT_ENTRY_CONST;
+        if (!c) e_src.push_back(sel_src[j]);
+        e_konst[j] = c ? sel_konst[j] : 0u;
+        e_off.push_back((uint32_t)e_src.size());
+    }
+    const std::vector<uint32_t> ones(e_src.size(), 1u);
+    DescBlob blob;
+    const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
+                 coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B),
+                 eoff_at = blob.add(e_off.data(), e_off.size()), esrc_at = blob.add(e_src.data(), e_src.size()),
+                 one_at = blob.add(ones.data(), ones.size()), ekonst_at = blob.add(e_konst.data(), E),
+                 pcoef_at = add_slot_coefs(blob, d.P.N, m), iota_at = add_iota(blob, B);
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *desc = blob.upload(f);
+    if (terms || !e_src.empty()) io.in(pool, P * w * 4);  // neither: the pool (may be NULL) is never read
+    int rc = io.out(out, B * w * 4);
+    uint32_t *x = f.take<uint32_t>(B * w), *tv = f.take<uint32_t>(B * 2 * (size_t)d.P.N);
+    if ((rc = f.rc())) return rc;
+    HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
+                                 desc + konst_at, x, B, d.stream));
+    rc = select_testvecs(d, pk, m, pool, desc + eoff_at, desc + esrc_at, reinterpret_cast<const int32_t *>(desc + one_at),
+                         desc + ekonst_at, desc + pcoef_at, tv, B);
+    if (rc) return rc;
+    rc = run_bootstrap_dev(d, nullptr, x, nullptr, tv, out, B, RUN_BOOTSTRAP, nullptr, desc + iota_at);
+    return rc ? rc : io.finish();
 }
 
 // theta: NULL for the single-output entries
@@ -191,24 +297,60 @@ static int apply_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const uint3
     });
 }
 
+// nullptr, or what is wrong with a select node's m on this context's parameters (lut_apply2's conditions)
+static const char *select_m_bad(const tfhe_gpu_ctx *c, uint32_t m) {
+    return m < 2 || (m & (m - 1)) || 2 * (uint64_t)m > c->P.N
+               ? "select nodes: m must be a power of two with 2 <= m and 2m <= N"
+               : nullptr;
+}
+
 static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_inputs, const uint32_t *inputs,
                          size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
                          const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, size_t n_outputs,
-                         const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels, bool dev) {
+                         const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels, bool dev,
+                         const tfhe_gpu_packing_key *pk = nullptr, const LutSelect *sel = nullptr) {
     if (!c || !set || (n_inputs && !inputs) || (n_nodes && (!term_off || !konst || !lut)) ||
-        (n_outputs && (!out_wires || !outputs)))
+        (n_outputs && (!out_wires || !outputs)) || (sel && !pk))
         return fail(c, TFHE_ERR_INVALID, "null argument");
     if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
     if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
+    if (sel) {
+        if (const int rc = set_mismatch(c, pk, "packing key")) return rc;
+        if (const char *why = select_m_bad(c, sel->m)) return fail(c, TFHE_ERR_INVALID, why);
+        if (n_nodes && sel->off[n_nodes] && (!sel->wire || !sel->konst)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    }
     if (n_nodes && term_off[n_nodes] && (!term_wire || !term_coef)) return fail(c, TFHE_ERR_INVALID, "null argument");
     LutCircuitPlan pl;
     if (const char *why = plan_lut_circuit(n_inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, set->T,
-                                           n_outputs, out_wires, pl, theta))
+                                           n_outputs, out_wires, pl, theta, sel))
         return fail(c, TFHE_ERR_INVALID, std::string("LUT circuit: ") + why);
-    const int rc = on_device0(
-        c, [&](Device &d) { return lut_circuit_on(d, *set, n_inputs, inputs, n_nodes, pl, n_outputs, outputs, dev); });
+    const int rc = on_device0(c, [&](Device &d) {
+        return lut_circuit_on(d, *set, n_inputs, inputs, n_nodes, pl, n_outputs, outputs, dev, pk, sel ? sel->m : 0);
+    });
     if (!rc && levels) *levels = pl.depth;
     return rc;
+}
+
+static int select_entry(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool, size_t P,
+                        const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                        const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out, size_t B,
+                        bool dev) {
+    if (!c || !pk || (B && (!term_off || !konst || !sel_src || !sel_konst || !out)))
+        return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (const int rc = set_mismatch(c, pk, "packing key")) return rc;
+    if (const char *why = select_m_bad(c, m)) return fail(c, TFHE_ERR_INVALID, why);
+    if (B == 0) return TFHE_OK;
+    if (B > 0x7FFFFFFFull / m || P > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "lut_select: too many nodes or ciphertexts");
+    if (term_off[B] && (!term_src || !term_coef || !pool)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (const char *why = check_lut_nodes(B, P, 0, term_off, term_src, nullptr))
+        return fail(c, TFHE_ERR_INVALID, std::string("lut_select: ") + why);
+    for (size_t j = 0; j < B * m; j++)
+        if (sel_src[j] != TFHE_LUT_ENTRY_CONST && (sel_src[j] >= P || !pool))
+            return fail(c, TFHE_ERR_INVALID, "lut_select: an entry is not a ciphertext of the pool");
+    return on_device0(c, [&](Device &d) {
+        return lut_select_on(d, *pk, m, pool, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out, B, dev);
+    });
 }
 
 // ---- Bivariate LUT bootstrap (include/tfhe_gpu.h): spread, a test vector per item, the fused node ----
@@ -230,13 +372,6 @@ static int spread_entry(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_
         HIPCHK(d, launch_lut_spread(in, w, rot, out, B, d.stream, &d.last_br));
         return io.finish();
     });
-}
-
-// The selector of a bootstrap whose item g reads testvecs + g * 2N: 0 .. B-1, appended to a call's descriptors.
-static size_t add_iota(DescBlob &blob, size_t B) {
-    const size_t at = blob.words.size();
-    for (size_t i = 0; i < B; i++) blob.words.push_back((uint32_t)i);
-    return at;
 }
 
 static int each_entry(tfhe_gpu_ctx *c, const uint32_t *in, const uint32_t *testvecs, uint32_t *out, size_t B, bool dev) {
@@ -442,6 +577,44 @@ int tfhe_gpu_lut_circuit_eval_multi_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set 
                                         const uint32_t *out_wires, uint32_t *outputs_dev, uint32_t *levels) {
     return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, theta,
                          n_outputs, out_wires, outputs_dev, levels, true);
+}
+
+// sel_off == NULL: the _multi entry (pk and m are not looked at)
+int tfhe_gpu_lut_circuit_eval_select(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                     uint32_t m, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
+                                     const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                     const uint32_t *konst, const uint32_t *lut, const uint32_t *theta,
+                                     const uint32_t *sel_off, const uint32_t *sel_wire, const uint32_t *sel_konst,
+                                     size_t n_outputs, const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels) {
+    const LutSelect sel{m, sel_off, sel_wire, sel_konst};
+    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, theta, n_outputs,
+                         out_wires, outputs, levels, false, pk, sel_off ? &sel : nullptr);
+}
+
+int tfhe_gpu_lut_circuit_eval_select_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                         uint32_t m, size_t n_inputs, const uint32_t *inputs_dev, size_t n_nodes,
+                                         const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                         const uint32_t *konst, const uint32_t *lut, const uint32_t *theta,
+                                         const uint32_t *sel_off, const uint32_t *sel_wire, const uint32_t *sel_konst,
+                                         size_t n_outputs, const uint32_t *out_wires, uint32_t *outputs_dev,
+                                         uint32_t *levels) {
+    const LutSelect sel{m, sel_off, sel_wire, sel_konst};
+    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, theta,
+                         n_outputs, out_wires, outputs_dev, levels, true, pk, sel_off ? &sel : nullptr);
+}
+
+int tfhe_gpu_lut_select_batch(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool, size_t P,
+                              const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                              const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out,
+                              size_t B) {
+    return select_entry(c, pk, m, pool, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out, B, false);
+}
+
+int tfhe_gpu_lut_select_dev(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool_dev,
+                            size_t P, const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                            const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out_dev,
+                            size_t B) {
+    return select_entry(c, pk, m, pool_dev, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out_dev, B, true);
 }
 
 }  // extern "C"

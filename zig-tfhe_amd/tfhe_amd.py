@@ -253,6 +253,18 @@ _SIGS = {
     "tfhe_gpu_lut_apply2_batch": (C.c_int, [vp, vp, vp, C.c_uint32, u32p, C.c_size_t, u32p, u32p, u32p, u32p,
                                             C.c_size_t]),
     "tfhe_gpu_lut_apply2_dev": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_size_t, u32p, u32p, u32p, vp, C.c_size_t]),
+    "tfhe_gpu_lut_circuit_eval_select": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, u32p, C.c_size_t, u32p, u32p,
+                                                   i32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_size_t, u32p, u32p,
+                                                   C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_lut_circuit_eval_select_dev": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, vp, C.c_size_t, u32p, u32p,
+                                                       i32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_size_t, u32p, vp,
+                                                       C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_lut_select_batch": (C.c_int, [vp, vp, C.c_uint32, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p,
+                                            u32p, C.c_size_t]),
+    "tfhe_gpu_lut_select_dev": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p, vp,
+                                          C.c_size_t]),
+    "tfhe_lut_circuit_schedule_select": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, C.c_uint32, u32p, u32p,
+                                                   u32p, C.POINTER(C.c_uint32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -1012,6 +1024,57 @@ class Context:
                    "lut_circuit_eval_dev")
         return depth.value
 
+    # ---- select nodes: a node whose table is made of wires (include/tfhe_gpu.h "Select nodes") ----
+    def lut_circuit_eval_select(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs, nodes, theta,
+                                select, out_wires):
+        """tfhe_gpu_lut_circuit_eval_select: select = (sel_off, sel_wire, sel_konst), node g being a select node
+        over its m entries sel_wire[sel_off[g] : sel_off[g+1]] (LUT_ENTRY_CONST: the constant sel_konst[j]), or
+        None for lut_circuit_eval_multi -> (outputs, depth)."""
+        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        sel = _select_arrays(select, d.B)
+        ow, owp = _u32(out_wires)
+        out = np.zeros((ow.size, self.n1), np.uint32)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_select(
+            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m, inputs.shape[0], ip, d.B,
+            *d.pointers(), thp, *sel[1], ow.size, owp, out.ctypes.data_as(u32p), C.byref(depth)),
+            "lut_circuit_eval_select")
+        return out, depth.value
+
+    def lut_circuit_eval_select_dev(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs_ptr, n_inputs,
+                                    nodes, theta, select, out_wires, outputs_ptr):
+        """tfhe_gpu_lut_circuit_eval_select_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        sel = _select_arrays(select, d.B)
+        ow, owp = _u32(out_wires)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_select_dev(
+            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m, n_inputs, vp(inputs_ptr), d.B,
+            *d.pointers(), thp, *sel[1], ow.size, owp, vp(outputs_ptr), C.byref(depth)), "lut_circuit_eval_select_dev")
+        return depth.value
+
+    def lut_select(self, packing_key: "PackingKey", m: int, pool, nodes):
+        """tfhe_gpu_lut_select_batch: node b = (terms, entries[, const]) bootstraps x = sum coef * pool[src] + const
+        with the test vector packed from its m entries, each a pool index or ("const", word): the output decrypts
+        to what entry number x decrypts to.  pool (P, n+1) -> (B, n+1)."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        d, src, konst = _select_nodes(nodes, m)
+        out = np.zeros((d.B, self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_select_batch(self.h, packing_key.h, m, pp, pool.shape[0], *d.pointers()[:4],
+                                                      src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p),
+                                                      out.ctypes.data_as(u32p), d.B), "lut_select")
+        return out
+
+    def lut_select_dev(self, packing_key: "PackingKey", m: int, pool_ptr, P, nodes, out_ptr):
+        """tfhe_gpu_lut_select_dev: the pool and the B outputs in HBM (the nodes stay a host description), async."""
+        d, src, konst = _select_nodes(nodes, m)
+        self.check(self.lib.tfhe_gpu_lut_select_dev(self.h, packing_key.h, m, vp(pool_ptr), P, *d.pointers()[:4],
+                                                    src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p), vp(out_ptr),
+                                                    d.B), "lut_select_dev")
+
 
 @dataclass
 class SecretKey:
@@ -1302,6 +1365,49 @@ def lut_spread_host(params: TfheParams, trlwes, w: int, rot: int) -> np.ndarray:
     return out
 
 
+LUT_ENTRY_CONST = 0xFFFFFFFF  # TFHE_LUT_ENTRY_CONST: a select node's entry that is a constant
+
+
+def _select_entries(entries, m: int, what: str):
+    """m entries of a select node, each a wire / pool index or ("const", word) -> (sources, constants)."""
+    entries = list(entries)
+    if len(entries) != m:
+        raise ValueError(f"{what}: a select node has m = {m} entries, got {len(entries)}")
+    src, konst = [], []
+    for e in entries:
+        if isinstance(e, tuple):
+            if len(e) != 2 or e[0] != "const":
+                raise ValueError(f'{what}: an entry is a wire or ("const", word), got {e!r}')
+            src.append(LUT_ENTRY_CONST)
+            konst.append(int(e[1]) & 0xFFFFFFFF)
+        else:
+            src.append(int(e))
+            konst.append(0)
+    return src, konst
+
+
+def _select_arrays(select, B):
+    """(sel_off, sel_wire, sel_konst) or None -> (the arrays kept alive, their three pointers or NULLs)."""
+    if select is None:
+        return None, (None, None, None)
+    arrs = [np.ascontiguousarray(a, np.uint32).reshape(-1) for a in select]
+    if arrs[0].size != B + 1 or arrs[1].size != arrs[2].size:
+        raise ValueError("select: sel_off needs one entry per node and one more, sel_wire and sel_konst one per entry")
+    return arrs, tuple(a.ctypes.data_as(u32p) for a in arrs)
+
+
+def _select_nodes(nodes, m: int):
+    """nodes of Context.lut_select, (terms, entries[, const]) each -> (LutNodes with lut = 0, sel_src, sel_konst)."""
+    flat, src, konst = [], [], []
+    for node in nodes:
+        terms, entries, k = (*node, 0) if len(node) == 2 else node
+        s, c = _select_entries(entries, m, "lut_select")
+        src += s
+        konst += c
+        flat.append((0, terms, k))
+    return pack_lut_nodes(flat), np.array(src, np.uint32), np.array(konst, np.uint32)
+
+
 def _apply2_nodes(nodes):
     """nodes of Context.lut_apply2: (fn, x_src, y_src) arrays, or a sequence of such triples -> three u32 arrays."""
     if isinstance(nodes, tuple) and len(nodes) == 3 and all(np.ndim(a) == 1 for a in nodes):
@@ -1376,8 +1482,9 @@ def pack_lut_nodes(nodes) -> LutNodes:
 
 class LutCircuit:
     """DAG builder for Context.lut_circuit_eval: every node is a small integer combination of earlier wires
-    followed by a programmable bootstrap with one table of a LutSet.  Evaluated level by level, one
-    combination launch and one bootstrap launch per level, every wire in HBM.
+    followed by a programmable bootstrap with one table of a LutSet, or (select, node2, lookup) with a table
+    packed on the device from m earlier wires or constants.  Evaluated level by level, one combination launch
+    and one bootstrap launch per level, every wire in HBM.
 
         c = LutCircuit(); a, b = c.input(), c.input(); s = c.node(0, [(a, 1), (b, 1)]); c.output(s)
         outs, depth = c.run(ctx, lut_set, [ct_a, ct_b])
@@ -1387,6 +1494,8 @@ class LutCircuit:
         self.n_inputs = 0
         self.nodes = []  # (lut, terms, const)
         self.theta = []  # per node: log2 of its output count
+        self.sel = []    # per node: None, or a select node's m entries (a wire or ("const", word) each)
+        self.m = None    # the select nodes' m (one per circuit)
         self.n_wires = 0
         self.outputs = []
 
@@ -1408,12 +1517,71 @@ class LutCircuit:
             raise ValueError("node terms must read existing wires")
         self.nodes.append((int(lut), terms, int(const)))
         self.theta.append(outputs.bit_length() - 1)
+        self.sel.append(None)
         self.n_wires += outputs
         return w if outputs == 1 else list(range(w, w + outputs))
+
+    def select(self, terms, entries, const: int = 0) -> int:
+        """A select node: the digit x = sum coef * wire over terms (+ const) picks one of the m = len(entries)
+        entries, each an earlier wire or ("const", word); the table is packed from the entries on the device
+        (tfhe_gpu_lut_circuit_eval_select).  -> the node's wire, which decrypts to what entry number x decrypts to."""
+        entries = list(entries)
+        m = len(entries)
+        if m < 2 or m & (m - 1) or (self.m is not None and m != self.m):
+            raise ValueError(f"a select node has m entries, m a power of two >= 2 and one m per circuit "
+                             f"({self.m}); got {m}")
+        src, _ = _select_entries(entries, m, "select")
+        w = self.n_wires
+        terms = [(int(s), int(c)) for s, c in terms]
+        if any(not 0 <= s < w for s, _ in terms) or any(e != LUT_ENTRY_CONST and not 0 <= e < w for e in src):
+            raise ValueError("a select node's terms and entries must read existing wires")
+        self.m = m
+        self.nodes.append((0, terms, int(const)))
+        self.theta.append(0)
+        self.sel.append(entries)
+        self.n_wires += 1
+        return w
+
+    def node2(self, lut_base: int, x_terms, y_terms, m: int) -> int:
+        """A bivariate node f(x, y) over two m-ary digits: m ordinary nodes with the tables lut_base + i
+        (y -> f(i, y), lut_generate2's rows) over y_terms and one select node over x_terms -> its wire."""
+        if self.m is not None and m != self.m:
+            raise ValueError(f"node2: the circuit's select nodes have m = {self.m}, got {m}")
+        return self.select(x_terms, [self.node(lut_base + i, y_terms) for i in range(m)])
+
+    def lookup(self, digit_terms_list, lut_base: int, m: int) -> int:
+        """A k-digit lookup over plaintext tables: digit_terms_list holds the terms of the k digits, most
+        significant first, and the set the m^(k-1) tables f(i_1, .., i_{k-1}, .) from lut_base in row-major order.
+        m^(k-1) ordinary nodes on the last digit, then nested select nodes for the earlier digits -> the wire."""
+        digits = list(digit_terms_list)
+        if not digits:
+            raise ValueError("lookup: no digits")
+        k = len(digits)
+        row = [self.node(lut_base + i, digits[-1]) for i in range(m ** (k - 1))]
+        for terms in reversed(digits[:-1]):
+            row = [self.select(terms, row[j * m:(j + 1) * m]) for j in range(len(row) // m)]
+        return row[0]
 
     @property
     def multi(self) -> bool:
         return any(self.theta)
+
+    @property
+    def has_select(self) -> bool:
+        return any(e is not None for e in self.sel)
+
+    def select_arrays(self):
+        """(sel_off, sel_wire, sel_konst) of tfhe_gpu_lut_circuit_eval_select, or None without select nodes."""
+        if not self.has_select:
+            return None
+        off, wire, konst = [0], [], []
+        for e in self.sel:
+            if e is not None:
+                s, c = _select_entries(e, self.m, "select")
+                wire += s
+                konst += c
+            off.append(len(wire))
+        return np.array(off, np.uint32), np.array(wire, np.uint32), np.array(konst, np.uint32)
 
     def output(self, *wires):
         self.outputs.extend(wires)
@@ -1447,7 +1615,12 @@ class LutCircuit:
         d = self.packed()
         levels = np.zeros(max(d.B, 1), np.uint32)
         depth = C.c_uint32(0)
-        if self.multi:
+        if self.has_select:
+            sel, selp = _select_arrays(self.select_arrays(), d.B)
+            rc = lib.tfhe_lut_circuit_schedule_select(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
+                                                      d.src.ctypes.data_as(u32p), _theta(self.theta, d.B)[1], self.m,
+                                                      selp[0], selp[1], levels.ctypes.data_as(u32p), C.byref(depth))
+        elif self.multi:
             rc = lib.tfhe_lut_circuit_schedule_multi(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
                                                      d.src.ctypes.data_as(u32p), _theta(self.theta, d.B)[1],
                                                      levels.ctypes.data_as(u32p), C.byref(depth))
@@ -1458,17 +1631,36 @@ class LutCircuit:
             raise TfheError(f"lut_circuit_schedule: status {rc}", rc)
         return levels[:d.B], depth.value
 
-    def run(self, ctx: "Context", lut_set: LutSet, inputs):
+    def _select_m(self, packing_key, m):
+        if packing_key is None:
+            raise ValueError("a circuit with select nodes needs a packing_key")
+        if m is not None and m != self.m:
+            raise ValueError(f"the circuit's select nodes have m = {self.m}, got {m}")
+        return self.m
+
+    def run(self, ctx: "Context", lut_set: LutSet, inputs, packing_key: "PackingKey" = None, m: int = None):
+        """packing_key (and m, which must be the select nodes' own) for a circuit with select nodes."""
         inputs = np.asarray(inputs, np.uint32).reshape(-1, ctx.params.n + 1)
         if inputs.shape[0] != self.n_inputs:
             raise ValueError(f"circuit has {self.n_inputs} inputs, got {inputs.shape[0]}")
+        if self.has_select:
+            m = self._select_m(packing_key, m)
+            return ctx.lut_circuit_eval_select(lut_set, packing_key, m, inputs,
+                                               self.packed(), self.theta, self.select_arrays(),
+                                               np.array(self.outputs, np.uint32))
         if self.multi:
             return ctx.lut_circuit_eval_multi(lut_set, inputs, self.packed(), self.theta,
                                               np.array(self.outputs, np.uint32))
         return ctx.lut_circuit_eval(lut_set, inputs, self.packed(), np.array(self.outputs, np.uint32))
 
-    def run_dev(self, ctx: "Context", lut_set: LutSet, inputs_ptr, outputs_ptr):
+    def run_dev(self, ctx: "Context", lut_set: LutSet, inputs_ptr, outputs_ptr, packing_key: "PackingKey" = None,
+                m: int = None):
         """Inputs (n_inputs TLWELv0) and outputs in HBM; returns the bootstrap depth."""
+        if self.has_select:
+            m = self._select_m(packing_key, m)
+            return ctx.lut_circuit_eval_select_dev(lut_set, packing_key, m, inputs_ptr,
+                                                   self.n_inputs, self.packed(), self.theta, self.select_arrays(),
+                                                   np.array(self.outputs, np.uint32), outputs_ptr)
         if self.multi:
             return ctx.lut_circuit_eval_multi_dev(lut_set, inputs_ptr, self.n_inputs, self.packed(), self.theta,
                                                   np.array(self.outputs, np.uint32), outputs_ptr)
