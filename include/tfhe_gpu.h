@@ -45,7 +45,9 @@ extern "C" {
                                    tfhe_gpu_bootstrap_lut_each_*, tfhe_gpu_lut_apply2_*) and the CMUX graphs
                                    (tfhe_cmux_graph_plan, tfhe_gpu_cmux_graph_*, TFHE_OPT_GRAPH_CHUNK_QUERIES)
                                    and the select nodes (tfhe_gpu_lut_circuit_eval_select*, tfhe_gpu_lut_select_*,
-                                   tfhe_lut_circuit_schedule_select, TFHE_LUT_ENTRY_CONST);
+                                   tfhe_lut_circuit_schedule_select, TFHE_LUT_ENTRY_CONST) and the extended LUT
+                                   bootstrap (tfhe_lut_generate_ext, tfhe_lut_ext_rotate, tfhe_lut_ext_mod_switch,
+                                   tfhe_gpu_blind_rotate_ext_batch, tfhe_gpu_lut_apply_ext_*);
                                    6: tfhe_gpu_build_kind, tfhe_lut_generate_scaled / _full; BR forms 6-40
                                    A/B-only, BR_LOADER / BR_SYNC = 1 only;
                                    5: _dev LUT / re-encryption / circuit entries; BR forms 2 and 4 removed */
@@ -728,6 +730,61 @@ int tfhe_gpu_lut_circuit_eval_multi_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_se
 int tfhe_lut_circuit_schedule_multi(size_t n_inputs, size_t n_nodes, const uint32_t *term_off,
                                     const uint32_t *term_wire, const uint32_t *theta /*n_nodes*/, uint32_t *levels,
                                     uint32_t *depth);
+
+/* ---- Extended LUT bootstrap: 5- and 6-bit digits on the N = 1024 key ----
+ * The mirror image of the multi-output bootstrap: eta extra bits of message room for 2^eta external products per
+ * step, with the key and the transforms as they are (Lee, Yoon, "Discretization error reduction for TFHE").  The
+ * blind rotation runs in Z[X]/(X^(N E) + 1), E = 2^eta, 0 <= eta <= TFHE_LUT_EXT_MAX_LOG, so its mod switch rounds to
+ * 2N E positions.  A polynomial of that ring is kept as E components over the ring of the key,
+ *     P(X) = sum_{j<E} X^j P_j(Y),  Y = X^E,  Y^N = -1,
+ * each an ordinary TRLWELv1 of 2N words; BK_i, a TRGSW over Z[Y]/(Y^N + 1), acts on every component separately.
+ * Word-exact, with nbit = log2 N, sh = 32 - (nbit + 1) - eta, mulxk = polyMulWithXK (trgsw.zig:442-466) with its
+ * exponent taken mod 2N, cmux = trgsw.cmux (trgsw.zig:260-284) in the reference's expression trees:
+ *   extended test vector: TV = Generator.generateLookupTableAssign at polynomial degree N E (the function of
+ *     (degree, m) tfhe_lut_generate is), stored as E TRLWELv1 tv_j with tv_j.a = 0, tv_j.b[k] = TV.b[k E + j].  In a
+ *     tfhe_gpu_lut_set the extended table t is the E consecutive entries set[t E + j].
+ *   ext_rotate(c_0 .. c_{E-1}, a) for 0 <= a <= 2N E, a = q E + r: output component k is
+ *     mulxk(c_{(k - r) mod E}, q + [k < r]) on both halves; a = 2N E is the identity.
+ *   blind rotation of the TLWELv0 (a_0 .. a_{n-1}, b): b~ = 2N E - ((b + 2^(sh-1)) >> sh),
+ *     a~_i = (a_i + 2^(sh-1)) >> sh, the adds in 64 bits (trgsw.zig:297, :312); acc = ext_rotate(tv, b~); for i < n:
+ *     rot = ext_rotate(acc, a~_i), acc_k = cmux(BK_i; in0 = acc_k, in1 = rot_k) for every k.
+ *   output: identityKeySwitching(sampleExtractIndex(acc_0, 0)).
+ * eta = 0 is the ordinary bootstrap: a call with eta = 0 runs exactly what the entry without eta runs.
+ * Noise rule: the mod switch's phase error, in positions of 2N E, has sigma ~ sqrt((n/2 + 1) / 12) for a binary key
+ * whatever eta is, and a message block of Encoder.new(m) is read N E / (2m) positions from its edge: each eta buys
+ * exactly one bit of m at equal margin.  UINT4 (n = 820, sigma = 5.86): m = 16, eta = 0: 32 / 5.86 = 5.5 sigma
+ * (today's); m = 32, eta = 1 and m = 64, eta = 2 the same; m = 64 at eta = 0 has 1.4 sigma (one input in six is
+ * read wrong) and at eta = 1 2.7 sigma -- do not use them.  The accumulator's own error and the key switch's do not
+ * shrink with eta: at UINT4 they leave the output a phase error of sigma 7.5e-4 (measured) against
+ * the half-spacing 1/(4m) = 3.9e-3 at m = 64, 5.2 sigma.  The library never sees m and does not police it. */
+#define TFHE_LUT_EXT_MAX_LOG 2
+/* host only, no device; TFHE_ERR_INVALID for eta > TFHE_LUT_EXT_MAX_LOG.  The E = 2^eta components of the extended
+ * test vector of f (f_table[x], x < m, as tfhe_lut_generate takes it); eta = 0 gives tfhe_lut_generate's words. */
+int tfhe_lut_generate_ext(const tfhe_params *params, uint32_t eta, uint32_t m, const uint32_t *f_table,
+                          uint32_t *out /*E*2N*/);
+/* ext_rotate on E components (in != out); a > 2N E is TFHE_ERR_INVALID. */
+int tfhe_lut_ext_rotate(const tfhe_params *params, uint32_t eta, const uint32_t *in /*E*2N*/, uint32_t a,
+                        uint32_t *out /*E*2N*/);
+/* (word + 2^(sh-1)) >> sh, a position in [0, 2N E]; a negative status on a refusal. */
+int tfhe_lut_ext_mod_switch(const tfhe_params *params, uint32_t eta, uint32_t word);
+/* Stage entry (parity tests): the blind rotation alone, all E accumulators of each of B TLWELv0 inputs under one
+ * shared extended test vector, item-major (out[(i E + k) 2N ..] is acc_k of item i).  First device only; eta = 0 is
+ * tfhe_gpu_blind_rotate_batch. */
+int tfhe_gpu_blind_rotate_ext_batch(tfhe_gpu_ctx *ctx, uint32_t eta, const uint32_t *in, const uint32_t *testvecs /*E*2N*/,
+                                    uint32_t *out /*B*E*2N*/, size_t B);
+/* tfhe_gpu_lut_apply_* with the extended bootstrap: x_i exactly as tfhe_gpu_lut_apply_* defines it (the same
+ * combination launch), out_i the extended bootstrap of x_i with the extended table lut[i] of the set.  Checked before
+ * any launch (TFHE_ERR_INVALID): eta > TFHE_LUT_EXT_MAX_LOG, a lut[i] E + E beyond the set, and everything
+ * tfhe_gpu_lut_apply_* checks; TFHE_ERR_NO_KEY and B == 0 as there.  First device only; the _dev form is asynchronous
+ * on the context stream and refuses a multi-device context. */
+int tfhe_gpu_lut_apply_ext_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, uint32_t eta, const uint32_t *pool,
+                                 size_t P, const uint32_t *term_off /*B+1*/, const uint32_t *term_src,
+                                 const int32_t *term_coef, const uint32_t *konst /*B*/, const uint32_t *lut /*B*/,
+                                 uint32_t *out, size_t B);
+int tfhe_gpu_lut_apply_ext_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, uint32_t eta, const uint32_t *pool_dev,
+                               size_t P, const uint32_t *term_off /*B+1*/, const uint32_t *term_src,
+                               const int32_t *term_coef, const uint32_t *konst /*B*/, const uint32_t *lut /*B*/,
+                               uint32_t *out_dev, size_t B);
 
 /* ---- Bivariate LUT bootstrap: a test vector built on the device per item ----
  * Any function f(x, y) of two digits at the full message modulus m of the parameter set (UINT4: 4 + 4 bits in), where

@@ -18,7 +18,8 @@
 //                        (several tables from one blind rotation; LutCircuit::select / node2 and tfhe::lutSelect:
 //                        nodes whose table is made of wires), tfhe::lutGenerate2 / tfhe::lutApply2 /
 //                        tfhe::lutSpread / tfhe::bootstrapLutEach (functions of two digits: a test vector
-//                        packed and spread on the device per item)
+//                        packed and spread on the device per item), tfhe::lutGenerateExt / tfhe::blindRotateExt /
+//                        tfhe::lutApplyExt (5- and 6-bit digits: the blind rotation on 2^eta components)
 // Zig error unions become tfhe::Error exceptions carrying the C status.
 // There is no CPU path: every bootstrap runs on the GPU through the C ABI.
 #pragma once
@@ -887,6 +888,66 @@ inline std::vector<TLWELv0> lutApply2(const CloudKey &ck, const LutSet &set, con
     check(tfhe_gpu_lut_apply2_batch(ck.ctx(), set.get(), key.get(), m, x.data(), pool.size(), fn.data(), xs.data(), ys.data(),
                                     out.data(), B),
           "lut_apply2", ck.ctx());
+    std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
+    return r;
+}
+
+// ---- Extended LUT bootstrap (include/tfhe_gpu.h): 5- and 6-bit digits, E = 2^eta accumulator components ----
+// tfhe_lut_generate_ext: the E components (2N words each) of the extended test vector of f_table (m = its size).
+// The components of several functions, one function after the other, make the LutSet of lutApplyExt.
+inline std::vector<std::vector<Torus>> lutGenerateExt(const tfhe_params &p, uint32_t eta,
+                                                      const std::vector<uint32_t> &f_table) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) throw Error(TFHE_ERR_INVALID, "lutGenerateExt: eta > TFHE_LUT_EXT_MAX_LOG");
+    const size_t E = (size_t)1 << eta, W = 2 * (size_t)p.N;
+    std::vector<Torus> all(E * W);
+    check(tfhe_lut_generate_ext(&p, eta, (uint32_t)f_table.size(), f_table.data(), all.data()), "lutGenerateExt");
+    std::vector<std::vector<Torus>> comps;
+    for (size_t j = 0; j < E; j++) comps.emplace_back(all.begin() + j * W, all.begin() + (j + 1) * W);
+    return comps;
+}
+
+// tfhe_gpu_blind_rotate_ext_batch (stage entry): all E accumulators of every input, item-major.
+inline std::vector<TRLWELv1> blindRotateExt(const CloudKey &ck, uint32_t eta, const std::vector<TLWELv0> &in,
+                                            const std::vector<std::vector<Torus>> &testvec) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) throw Error(TFHE_ERR_INVALID, "blindRotateExt: eta > TFHE_LUT_EXT_MAX_LOG");
+    const size_t B = in.size(), w = ck.params().n + 1, W = 2 * (size_t)ck.params().N, E = (size_t)1 << eta;
+    if (testvec.size() != E) throw Error(TFHE_ERR_INVALID, "blindRotateExt: 2^eta components");
+    std::vector<Torus> x(B * w), tv, out(B * E * W);
+    for (size_t b = 0; b < B; b++) std::copy(in[b].p.begin(), in[b].p.end(), x.begin() + b * w);
+    for (const std::vector<Torus> &c : testvec) {
+        if (c.size() != W) throw Error(TFHE_ERR_INVALID, "blindRotateExt: a component has 2N words");
+        tv.insert(tv.end(), c.begin(), c.end());
+    }
+    check(tfhe_gpu_blind_rotate_ext_batch(ck.ctx(), eta, x.data(), tv.data(), out.data(), B), "blind_rotate_ext", ck.ctx());
+    std::vector<TRLWELv1> r(B * E);
+    for (size_t k = 0; k < B * E; k++) std::copy(out.begin() + k * W, out.begin() + (k + 1) * W, r[k].p.begin());
+    return r;
+}
+
+// tfhe_gpu_lut_apply_ext_batch: node i = sum coef * pool[src] + konst on the b word, then the extended bootstrap
+// with the extended table lut (the set's entries lut * E .. lut * E + E - 1).
+struct LutExtNode {
+    uint32_t lut;
+    std::vector<std::pair<uint32_t, int32_t>> terms;  // (pool index, coefficient)
+    Torus konst = 0;
+};
+inline std::vector<TLWELv0> lutApplyExt(const CloudKey &ck, const LutSet &set, uint32_t eta,
+                                        const std::vector<TLWELv0> &pool, const std::vector<LutExtNode> &nodes) {
+    const size_t B = nodes.size(), w = ck.params().n + 1;
+    std::vector<Torus> x(pool.size() * w), out(B * w);
+    for (size_t k = 0; k < pool.size(); k++) std::copy(pool[k].p.begin(), pool[k].p.end(), x.begin() + k * w);
+    std::vector<uint32_t> off(1, 0u), src, konst, lut;
+    std::vector<int32_t> coef;
+    for (const LutExtNode &nd : nodes) {
+        for (const auto &t : nd.terms) src.push_back(t.first), coef.push_back(t.second);
+        off.push_back((uint32_t)src.size());
+        konst.push_back(nd.konst);
+        lut.push_back(nd.lut);
+    }
+    check(tfhe_gpu_lut_apply_ext_batch(ck.ctx(), set.get(), eta, x.data(), pool.size(), off.data(), src.data(), coef.data(),
+                                       konst.data(), lut.data(), out.data(), B),
+          "lut_apply_ext", ck.ctx());
     std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
     for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
     return r;

@@ -924,6 +924,65 @@ int tfhe_lut_generate_full(const tfhe_params *p, uint32_t m, const uint32_t *val
     return TFHE_OK;
 }
 
+// ---- Extended LUT bootstrap (include/tfhe_gpu.h): the host half ----
+// The test vector of degree N * E, split into its E components over Z[Y]/(Y^N + 1), Y = X^E.
+int tfhe_lut_generate_ext(const tfhe_params *p, uint32_t eta, uint32_t m, const uint32_t *f_table, uint32_t *out) {
+    std::string why;
+    if (!params_ok(p, why) || eta > TFHE_LUT_EXT_MAX_LOG || !f_table || !out || m == 0 || m > TFHE_LUT_MAX_M)
+        return TFHE_ERR_INVALID;
+    if (eta == 0) return tfhe_lut_generate(p, m, f_table, out);
+    const size_t N = p->N, E = (size_t)1 << eta;
+    const double scale = 1.0 / (2.0 * (double)m);  // Encoder.new (encoder.zig:29-42)
+    try {
+        std::vector<uint32_t> enc(m), tv(2 * N * E);
+        for (uint32_t x = 0; x < m; x++) enc[x] = host::f64_to_torus((double)(f_table[x] % m) * scale);
+        lut_from_values(N * E, m, enc.data(), tv.data());
+        const uint32_t *b = tv.data() + N * E;
+        for (size_t j = 0; j < E; j++) {
+            uint32_t *c = out + j * 2 * N;
+            for (size_t k = 0; k < N; k++) c[k] = 0, c[N + k] = b[k * E + j];
+        }
+    } catch (const std::bad_alloc &) {
+        return TFHE_ERR_OOM;
+    }
+    return TFHE_OK;
+}
+
+// polyMulWithXK (trgsw.zig:442-466) on one half of N words, the exponent taken mod 2N
+static void mul_xk_half(const uint32_t *x, size_t N, size_t k, uint32_t *y) {
+    k %= 2 * N;
+    for (size_t i = 0; i < N; i++) {
+        const size_t at = (i + k) % (2 * N);
+        y[at % N] = at < N ? x[i] : 0u - x[i];
+    }
+}
+
+// X^a on E components: a = q E + r sends component c to component (c + r) mod E, times Y^q, and once
+// more times Y where c + r wraps (X^E = Y).  Output k reads component (k - r) mod E with q + [k < r].
+int tfhe_lut_ext_rotate(const tfhe_params *p, uint32_t eta, const uint32_t *in, uint32_t a, uint32_t *out) {
+    std::string why;
+    if (!params_ok(p, why) || eta > TFHE_LUT_EXT_MAX_LOG || !in || !out || in == out) return TFHE_ERR_INVALID;
+    const size_t N = p->N, E = (size_t)1 << eta;
+    if (a > 2 * N * E) return TFHE_ERR_INVALID;
+    const size_t q = a >> eta, r = a & (E - 1);
+    for (size_t k = 0; k < E; k++) {
+        const uint32_t *c = in + ((k + E - r) & (E - 1)) * 2 * N;
+        const size_t ex = q + (k < r ? 1 : 0);
+        mul_xk_half(c, N, ex, out + k * 2 * N);
+        mul_xk_half(c + N, N, ex, out + k * 2 * N + N);
+    }
+    return TFHE_OK;
+}
+
+// (word + 2^(sh-1)) >> sh with sh = 32 - (nbit + 1) - eta, the add in 64 bits (trgsw.zig:297, :312):
+// a position in [0, 2N E]
+int tfhe_lut_ext_mod_switch(const tfhe_params *p, uint32_t eta, uint32_t word) {
+    std::string why;
+    if (!params_ok(p, why) || eta > TFHE_LUT_EXT_MAX_LOG) return TFHE_ERR_INVALID;
+    const uint32_t sh = 32 - (p->nbit + 1) - eta;
+    return (int)(((uint64_t)word + ((uint64_t)1 << (sh - 1))) >> sh);
+}
+
 // Table entries for tfhe_gpu_table_lookup_*: entry e as a trivial TRLWELv1 (a = 0) whose
 // coefficient c < width carries bit c of values[e] as +-1/8 (f64ToTorus(+-0.125), the gates'
 // plaintexts, gates.zig:48-121); bits past 63 read as clear.

@@ -805,6 +805,29 @@ DEV void ext_pairs_global(const uint32_t *tA, const uint32_t *tB, const double2 
     }
 }
 
+// ext_pairs_global for the chain's loop, the same arithmetic in the same order.
+// Inside the loop hipcc defers half of every pair's multiply-accumulate (the
+// imaginary sums) to the inverse transform and keeps the selector words and
+// digits they need until then: 1.2-1.6 KB of scratch per lane at L = 3, 150-500 B
+// at L = 2 (k_cmux, the same code without a loop, has none).  An empty asm on the
+// accumulated spectra after each pair makes them complete there, which removes
+// all of it; each pair's row offset behind an opaque asm as well keeps its
+// selector reads at the pair (256 + 187 registers at L = 3 against 256 + 250).
+template <int L, int RP = 0>
+DEV void ext_pairs_chain(const uint32_t *tA, const uint32_t *tB, const double2 *__restrict__ row, int bgbit,
+                         const RegTw &T, const C2 *twl, C2 *xb, int t, C2 *fa, C2 *fb) {
+    if constexpr (RP < L) {
+        C2 d[2][8];
+        forward_pair<L, RP, 1>(tA, tB, bgbit, T, twl, xb, t, d);
+        size_t at = (size_t)RP * 2048;
+        asm volatile("" : "+s"(at)::"memory");
+        mac_pair<RP>(fa, fb, d, row + at, t);
+#pragma unroll
+        for (int q = 0; q < 8; q++) asm volatile("" : "+v"(fa[q].x), "+v"(fa[q].y), "+v"(fb[q].x), "+v"(fb[q].y));
+        ext_pairs_chain<L, RP + 1>(tA, tB, row, bgbit, T, twl, xb, t, fa, fb);
+    }
+}
+
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void global_void_t;
 

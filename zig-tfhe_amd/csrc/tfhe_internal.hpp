@@ -356,4 +356,23 @@ hipError_t launch_lut_fanout_extract(const uint32_t *acc, const uint32_t *fan, u
 hipError_t launch_lut_spread(const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B, hipStream_t s,
                              const char **used = nullptr);
 
+// ---- launcher (tfhe_kernels_lut_ext.hip); asynchronous on `s` -----------
+// One batch of extended blind rotations (k_blind_rotate_ext, include/tfhe_gpu.h "Extended LUT bootstrap"),
+// device pointers: item g rotates in[g] (n + 1 words) over the extended table at
+// testvec + tv_sel[g] * E * 2N (tv_sel NULL: the one table at testvec), E = 2^eta components of 2N words, with
+// the BK in device layout.  all: out takes the E accumulators of every item (item-major, B * E * 2N words);
+// else acc_0 only (B * 2N words).  eta is 1 or 2: hipErrorInvalidValue otherwise.  P.offset is the key's
+// decomposition offset.
+struct BrExtBatch {
+    uint32_t eta = 0;
+    const uint32_t *in = nullptr;
+    const uint32_t *testvec = nullptr, *tv_sel = nullptr;
+    const double *bk = nullptr;
+    uint32_t *out = nullptr;
+    bool all = false;
+    size_t B = 0;
+};
+hipError_t launch_blind_rotate_ext(const KParams &P, const DevTables &T, const BrExtBatch &b, hipStream_t s,
+                                   const char **used = nullptr);
+
 }  // namespace tfhe

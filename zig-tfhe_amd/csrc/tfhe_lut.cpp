@@ -10,7 +10,9 @@
 // (k_lut_spread) and a bootstrap whose per-item selector is the identity over the
 // chunk's own test vectors.  A select node (select_testvecs) is the same chain inside the
 // circuit evaluator, its m tables' outputs replaced by any earlier wires or constants, and
-// shares its level's bootstrap launch with the ordinary nodes (KParams::tv_each).
+// shares its level's bootstrap launch with the ordinary nodes (KParams::tv_each).  The extended
+// bootstrap (lut_apply_ext_on) is lut_apply_on with k_blind_rotate_ext (tfhe_kernels_lut_ext.hip) on
+// 2^eta accumulator components in place of the blind rotation, then the extraction and the key switch.
 // Everything here runs on the context's first device.
 #include "tfhe_gpu.h"
 
@@ -462,9 +464,116 @@ static int apply2_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe
     return on_device0(c, [&](Device &d) { return lut_apply2_on(d, *set, *pk, m, pool, P, fn, x_src, y_src, out, B, dev); });
 }
 
+// ---- Extended LUT bootstrap (include/tfhe_gpu.h): E = 2^eta accumulator components per item, eta = 1 or 2 ----
+
+// The extended blind rotation over device buffers, async: all E accumulators of each item (all) or acc_0.
+static int blind_rotate_ext_launch(Device &d, uint32_t eta, const uint32_t *x, const uint32_t *testvec,
+                                   const uint32_t *tv_sel, uint32_t *acc, bool all, size_t B) {
+    BrExtBatch b;
+    b.eta = eta;
+    b.in = x;
+    b.testvec = testvec;
+    b.tv_sel = tv_sel;
+    b.bk = d.d_bk;
+    b.out = acc;
+    b.all = all;
+    b.B = B;
+    d.last_ks = "";
+    HIPCHK(d, launch_blind_rotate_ext(d.K, tables(d), b, d.stream, &d.last_br));
+    d.bootstraps += B;
+    return TFHE_OK;
+}
+
+static int blind_rotate_ext_entry(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in, const uint32_t *testvecs,
+                                  uint32_t *out, size_t B) {
+    if (!c || (B && (!in || !testvecs || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (eta > TFHE_LUT_EXT_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "blind_rotate_ext: eta > TFHE_LUT_EXT_MAX_LOG");
+    if (eta == 0) return tfhe_gpu_blind_rotate_batch(c, in, testvecs, out, B);
+    if (B > 0x7FFFFFFFull >> eta) return fail(c, TFHE_ERR_INVALID, "blind_rotate_ext: too many items");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+        const size_t w = tlwe0_words(d.P), E = (size_t)1 << eta, TRLWE_BYTES = 2 * (size_t)d.P.N * sizeof(uint32_t);
+        Frame f(d);
+        Io io{f, false};
+        io.in(in, B * w * 4);
+        io.in(testvecs, E * TRLWE_BYTES);
+        int rc = io.out(out, B * E * TRLWE_BYTES);
+        if (rc) return rc;
+        if ((rc = blind_rotate_ext_launch(d, eta, in, testvecs, nullptr, out, /*all*/ true, B))) return rc;
+        return io.finish();
+    });
+}
+
+// lut_apply_on with the extended bootstrap (checked descriptors): the same combination launch, the extended
+// blind rotation with the item's extended table lut[i], then sampleExtractIndex(acc_0, 0) and the key switch.
+static int lut_apply_ext_on(Device &d, const tfhe_gpu_lut_set &set, uint32_t eta, const uint32_t *pool, size_t P,
+                            const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                            const uint32_t *konst, const uint32_t *lut, uint32_t *out, size_t B, bool dev) {
+    if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+    const size_t w = tlwe0_words(d.P), terms = term_off[B];
+    DescBlob blob;
+    const size_t off_at = blob.add(term_off, B + 1), src_at = blob.add(term_src, terms),
+                 coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B), lut_at = blob.add(lut, B),
+                 zero_at = blob.reserve(1);  // the extraction's coefficient 0
+    Frame f(d);
+    Io io{f, dev};
+    const uint32_t *desc = blob.upload(f);
+    if (terms) io.in(pool, P * w * 4);  // no terms: the pool (may be NULL) is never read
+    int rc = io.out(out, B * w * 4);
+    uint32_t *x = f.take<uint32_t>(B * w), *acc = f.take<uint32_t>(B * 2 * (size_t)d.P.N);
+    uint32_t *lv1 = f.ks_input<uint32_t>(B * 1025);
+    if ((rc = f.rc())) return rc;
+    HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
+                                 desc + konst_at, x, B, d.stream));
+    if ((rc = blind_rotate_ext_launch(d, eta, x, set.tables, desc + lut_at, acc, /*all*/ false, B))) return rc;
+    HIPCHK(d, launch_sample_extract(acc, desc + zero_at, 1, lv1, B, d.stream));
+    KsGemm G;
+    if ((rc = ks_gemm_args(f, B, G))) return rc;
+    HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, B, d.stream, d.opts, &d.last_ks, &G));
+    return io.finish();
+}
+
+static int apply_ext_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, uint32_t eta, const uint32_t *pool, size_t P,
+                           const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                           const uint32_t *konst, const uint32_t *lut, uint32_t *out, size_t B, bool dev) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "LUT batch: eta > TFHE_LUT_EXT_MAX_LOG");
+    // eta = 0: exactly the existing entry
+    if (eta == 0) return apply_entry(c, set, pool, P, term_off, term_src, term_coef, konst, lut, nullptr, out, B, dev);
+    if (!c || !set || (B && (!term_off || !konst || !lut || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (const int rc = set_mismatch(c, set, "LUT set")) return rc;
+    if (B == 0) return TFHE_OK;
+    if (B > 0x7FFFFFFFull || P > 0xFFFFFFFFull) return fail(c, TFHE_ERR_INVALID, "LUT batch: too many nodes or ciphertexts");
+    if (term_off[B] && (!term_src || !term_coef || !pool)) return fail(c, TFHE_ERR_INVALID, "null argument");
+    // the extended table t is the entries t E .. t E + E - 1: t < floor(T / E)
+    if (const char *why = check_lut_nodes(B, P, set->T >> eta, term_off, term_src, lut))
+        return fail(c, TFHE_ERR_INVALID, std::string("extended LUT batch: ") + why);
+    return on_device0(c, [&](Device &d) {
+        return lut_apply_ext_on(d, *set, eta, pool, P, term_off, term_src, term_coef, konst, lut, out, B, dev);
+    });
+}
+
 }  // namespace tfhe
 
 extern "C" {
+
+int tfhe_gpu_blind_rotate_ext_batch(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in, const uint32_t *testvecs,
+                                    uint32_t *out, size_t B) {
+    return blind_rotate_ext_entry(c, eta, in, testvecs, out, B);
+}
+
+int tfhe_gpu_lut_apply_ext_batch(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, uint32_t eta, const uint32_t *pool,
+                                 size_t P, const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                                 const uint32_t *konst, const uint32_t *lut, uint32_t *out, size_t B) {
+    return apply_ext_entry(c, set, eta, pool, P, term_off, term_src, term_coef, konst, lut, out, B, false);
+}
+
+int tfhe_gpu_lut_apply_ext_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, uint32_t eta, const uint32_t *pool_dev,
+                               size_t P, const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
+                               const uint32_t *konst, const uint32_t *lut, uint32_t *out_dev, size_t B) {
+    return apply_ext_entry(c, set, eta, pool_dev, P, term_off, term_src, term_coef, konst, lut, out_dev, B, true);
+}
 
 int tfhe_gpu_lut_spread_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B) {
     return spread_entry(c, in, w, rot, out, B, false);

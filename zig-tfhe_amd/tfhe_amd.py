@@ -265,6 +265,14 @@ _SIGS = {
                                           C.c_size_t]),
     "tfhe_lut_circuit_schedule_select": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, C.c_uint32, u32p, u32p,
                                                    u32p, C.POINTER(C.c_uint32)]),
+    "tfhe_lut_generate_ext": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, C.c_uint32, u32p, u32p]),
+    "tfhe_lut_ext_rotate": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, u32p, C.c_uint32, u32p]),
+    "tfhe_lut_ext_mod_switch": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, C.c_uint32]),
+    "tfhe_gpu_blind_rotate_ext_batch": (C.c_int, [vp, C.c_uint32, u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_lut_apply_ext_batch": (C.c_int, [vp, vp, C.c_uint32, u32p, C.c_size_t, u32p, u32p, i32p, u32p, u32p, u32p,
+                                               C.c_size_t]),
+    "tfhe_gpu_lut_apply_ext_dev": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p, vp,
+                                             C.c_size_t]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -907,6 +915,33 @@ class Context:
         d = pack_lut_nodes(nodes)
         self.check(self.lib.tfhe_gpu_lut_apply_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), vp(out_ptr), d.B),
                    "lut_apply_dev")
+
+    def blind_rotate_ext(self, eta: int, cts, testvecs):
+        """tfhe_gpu_blind_rotate_ext_batch (stage entry): the extended blind rotation of (B, n+1) TLWELv0 under one
+        extended test vector (E = 2^eta components, lut_generate_ext) -> (B, E, 2N), all E accumulators."""
+        cts, cp = _u32(np.asarray(cts, np.uint32).reshape(-1, self.n1))
+        E = 1 << eta if 0 <= eta < 8 else 1  # the library refuses eta > 2 itself
+        tv, tvp = _u32(testvecs)
+        out = np.zeros((cts.shape[0], E, 2 * self.params.N), np.uint32)
+        self.check(self.lib.tfhe_gpu_blind_rotate_ext_batch(self.h, eta, cp, tvp, out.ctypes.data_as(u32p),
+                                                            cts.shape[0]), "blind_rotate_ext")
+        return out
+
+    def lut_apply_ext(self, lut_set: "LutSet", eta: int, pool, nodes):
+        """tfhe_gpu_lut_apply_ext_batch: lut_apply with the extended bootstrap; node i's lut names the extended table
+        lut_set[lut * E .. lut * E + E - 1], E = 2^eta (lut_generate_ext).  eta = 0 is lut_apply."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        out = np.zeros((d.B, self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_apply_ext_batch(self.h, lut_set.h, eta, pp, pool.shape[0], *d.pointers(),
+                                                         out.ctypes.data_as(u32p), d.B), "lut_apply_ext")
+        return out
+
+    def lut_apply_ext_dev(self, lut_set: "LutSet", eta: int, pool_ptr, P, nodes, out_ptr):
+        """tfhe_gpu_lut_apply_ext_dev: the pool and the B outputs in HBM, async on the context stream."""
+        d = pack_lut_nodes(nodes)
+        self.check(self.lib.tfhe_gpu_lut_apply_ext_dev(self.h, lut_set.h, eta, vp(pool_ptr), P, *d.pointers(),
+                                                       vp(out_ptr), d.B), "lut_apply_ext_dev")
 
     def lut_apply_multi(self, lut_set: "LutSet", pool, nodes, theta=None):
         """tfhe_gpu_lut_apply_multi_batch: lut_apply with theta[i] per node (None: all 0); node i gives the 2^theta[i]
@@ -1874,6 +1909,40 @@ def lut_generate(params: TfheParams, m: int, f) -> np.ndarray:
     if rc:
         raise TfheError(f"lut_generate: {rc}")
     return tv
+
+
+def lut_generate_ext(params: TfheParams, eta: int, m: int, f) -> np.ndarray:
+    """tfhe_lut_generate_ext: the extended test vector of f (a callable or a table of m values) for the extended
+    bootstrap, (E, 2N) with E = 2^eta: component j holds coefficients j, j + E, ... of the degree-N*E test vector."""
+    table = np.array([f(x) for x in range(m)] if callable(f) else f, dtype=np.uint32)
+    if table.shape != (m,):
+        raise ValueError("lut_generate_ext: the table must have m entries")
+    out = np.zeros((1 << eta if 0 <= eta < 8 else 1, 2 * params.N), np.uint32)
+    rc = load_library().tfhe_lut_generate_ext(C.byref(params), eta, m, table.ctypes.data_as(u32p),
+                                              out.ctypes.data_as(u32p))
+    if rc != 0:
+        raise TfheError(f"lut_generate_ext: status {rc}", rc)
+    return out
+
+
+def lut_ext_rotate_host(params: TfheParams, eta: int, comps, a: int) -> np.ndarray:
+    """tfhe_lut_ext_rotate: X^a on the E = 2^eta components (E, 2N) of a polynomial pair of degree N*E,
+    0 <= a <= 2N*E."""
+    E = 1 << eta if 0 <= eta < 8 else 1
+    x, xp = _u32(np.asarray(comps, np.uint32).reshape(E, 2 * params.N))
+    out = np.zeros_like(x)
+    rc = load_library().tfhe_lut_ext_rotate(C.byref(params), eta, xp, a, out.ctypes.data_as(u32p))
+    if rc != 0:
+        raise TfheError(f"lut_ext_rotate: status {rc}", rc)
+    return out
+
+
+def lut_ext_mod_switch(params: TfheParams, eta: int, word: int) -> int:
+    """tfhe_lut_ext_mod_switch: (word + 2^(sh-1)) >> sh, sh = 32 - (nbit + 1) - eta: a position in [0, 2N*E]."""
+    rc = load_library().tfhe_lut_ext_mod_switch(C.byref(params), eta, int(word) & 0xFFFFFFFF)
+    if rc < 0:
+        raise TfheError(f"lut_ext_mod_switch: status {rc}", rc)
+    return rc
 
 
 def lut_generate2(params: TfheParams, m: int, f) -> np.ndarray:
