@@ -83,8 +83,11 @@ DEV void gather_rot_one(uint32_t base, int t, int at, uint32_t *xb, uint32_t *v)
 // the same way and not kept: the pass-B twiddles ahead of exchange 1's stores
 // (slower), the pass-C twiddles ahead of exchange 2 (slower alone, level with
 // this when combined with it); profiles/ab_lds_read_groups.txt.
+// tres: the caller's resident twist factors, tres[m] = twist_t[64 m] for m < nres
+// (the gate wave's, TWIST_RES below); those are not read again.
 template <bool FU, bool EX2LDS = false>
-DEV void inverse_one(const C2 *f, C2 *xb, const LdsTw &T, const C2 *twist_t, int t, uint32_t *acc, uint32_t &near) {
+DEV void inverse_one(const C2 *f, C2 *xb, const LdsTw &T, const C2 *twist_t, int t, uint32_t *acc, uint32_t &near,
+                     const C2 *tres = nullptr, int nres = 0) {
     C2 e[1][8], tu[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) e[0][q] = f[br3(q)];
@@ -100,7 +103,7 @@ DEV void inverse_one(const C2 *f, C2 *xb, const LdsTw &T, const C2 *twist_t, int
         C2 w[7];
         T.pass_c(w, t);
 #pragma unroll
-        for (int q = 0; q < 8; q++) tu[q] = twist_t[64 * q];
+        for (int q = 0; q < 8; q++) tu[q] = q < nres ? tres[q] : twist_t[64 * q];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < 8; q++) asm volatile("" : "+v"(e[0][q].x), "+v"(e[0][q].y));
@@ -124,6 +127,70 @@ DEV void spin_short(const uint32_t *p, uint32_t target, uint32_t cap, uint32_t &
     uint32_t f = 0;
     spin_until_ge<1>(p, target, cap, f);
     fail |= f;
+}
+
+// spin_short on the loader's tB counter with the 16 tB words (tb_t[64 m], m < 16)
+// read in the counter's LDS batch, as wait_pair_first_group reads the MAC's first
+// group: one LDS round trip instead of the counter's and then the words'.  A
+// wave's LDS operations execute in order, so words read behind a counter value
+// that says "written" are the written ones; a counter that is short sleeps and
+// reads all of them again, bounded as spin_short is.  Alone it measured level with
+// the parent, with the resident twist factors (TWIST_RES) 0.2-0.5 % below them
+// alone (profiles/gate_wave_early_reads_ab.txt).
+DEV void wait_tb_words(const uint32_t *p, uint32_t target, const uint32_t *tb_t, uint32_t cap, uint32_t &fail,
+                       uint32_t *tb) {
+    typedef __attribute__((ext_vector_type(2))) unsigned int u2;
+    u2 w0, w1, w2, w3, w4, w5, w6, w7;
+    uint32_t v, sv, cnt, f = 0;
+    const uint32_t caddr = (uint32_t)(size_t)(const lds_void_t *)p;
+    const uint32_t taddr = (uint32_t)(size_t)(const lds_void_t *)tb_t;
+    asm volatile(
+        "s_mov_b32 %[cnt], %[cap]\n"
+        "1:\n\t"
+        "ds_read_b32 %[v], %[ca]\n\t"
+        "ds_read2st64_b32 %[w0], %[ta] offset1:1\n\t"
+        "ds_read2st64_b32 %[w1], %[ta] offset0:2 offset1:3\n\t"
+        "ds_read2st64_b32 %[w2], %[ta] offset0:4 offset1:5\n\t"
+        "ds_read2st64_b32 %[w3], %[ta] offset0:6 offset1:7\n\t"
+        "ds_read2st64_b32 %[w4], %[ta] offset0:8 offset1:9\n\t"
+        "ds_read2st64_b32 %[w5], %[ta] offset0:10 offset1:11\n\t"
+        "ds_read2st64_b32 %[w6], %[ta] offset0:12 offset1:13\n\t"
+        "ds_read2st64_b32 %[w7], %[ta] offset0:14 offset1:15\n\t"
+        "s_waitcnt lgkmcnt(0)\n\t"
+        "v_readfirstlane_b32 %[sv], %[v]\n\t"
+        "s_cmp_ge_u32 %[sv], %[tgt]\n\t"
+        "s_cbranch_scc1 2f\n\t"
+        "s_sleep 1\n\t"
+        "s_sub_u32 %[cnt], %[cnt], 1\n\t"
+        "s_cmp_eq_u32 %[cnt], 0\n\t"
+        "s_cbranch_scc0 1b\n\t"
+        "s_mov_b32 %[fail], 1\n"
+        "2:"
+        : [v] "=&v"(v), [w0] "=&v"(w0), [w1] "=&v"(w1), [w2] "=&v"(w2), [w3] "=&v"(w3), [w4] "=&v"(w4),
+          [w5] "=&v"(w5), [w6] "=&v"(w6), [w7] "=&v"(w7), [sv] "=&s"(sv), [cnt] "=&s"(cnt), [fail] "+s"(f)
+        : [ca] "v"(caddr), [ta] "v"(taddr), [tgt] "s"(target), [cap] "s"(cap)
+        : "memory", "scc");
+    fail |= f;
+    const u2 w[8] = {w0, w1, w2, w3, w4, w5, w6, w7};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        tb[2 * j] = w[j].x;
+        tb[2 * j + 1] = w[j].y;
+    }
+}
+
+// Twist factors the gate wave keeps in VGPRs across its step loop: the factors
+// of coefficients t + 64 m, m < TWIST_RES.  The step uses the same 8 factors four
+// times (pair 0's, pairs 1 and 2's, the untwist's): 32 ds_read_b128 per step, 8
+// with 6 resident.  6 is what fits: 254 VGPRs, no scratch, 2 waves per SIMD; 7
+// spill 16 B per lane.  4 / 6 resident: 0.5 / 0.7 % below the parent
+// (profiles/gate_wave_early_reads_ab.txt).
+constexpr int TWIST_RES = 6;
+// The gate wave's 8 twist factors in transform order, tw[q] = factor of
+// coefficient t + 64 br3(q) (read_twist8), from the resident ones or LDS.
+DEV void twist8_resident(C2 *tw, const C2 *tres, const C2 *twist_t) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) tw[q] = br3(q) < TWIST_RES ? tres[br3(q)] : twist_t[64 * br3(q)];
 }
 
 template <bool FU, bool TV = false>
@@ -286,6 +353,9 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
     const uint32_t base = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lds_void_t *)X32);  // acc_a copy: X[0, 4 KB)
     int at_next = s_at[0];
     uint32_t near = NEAR_NONE, fail = 0;
+    C2 tres[TWIST_RES];
+#pragma unroll
+    for (int m = 0; m < TWIST_RES; m++) tres[m] = twist_t[64 * m];
     PhaseProf pp;  // tools/phase_prof.hip assist: 0 gather + tmp, 1 pair 0 fft, 2 pub waits, 3 macs, 4 tB wait, 5 pairs 1-2 fft, 6 fb hand-off, 7 inverse a
     pp.start();
     for (int i = 0; i < n; i++) {
@@ -294,8 +364,11 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
         uint32_t tA[16], xb[16];
         C2 tw0[8];
         gather_rot_one(base, t, at, xb, tA);
+        // the empty asm pins the resident factors in their registers: one definition per step, so hipcc
+        // neither reads them again at a use nor moves the reads into the loop
 #pragma unroll
-        for (int q = 0; q < 8; q++) tw0[q] = twist_t[64 * br3(q)];
+        for (int m = 0; m < TWIST_RES; m++) asm volatile("" : "+v"(tres[m].x), "+v"(tres[m].y));
+        twist8_resident(tw0, tres, twist_t);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < 16; m++) {
@@ -319,19 +392,20 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
                 pp.mark(1);
                 load_digits_pair0_regs<FU>(d, tA, nullptr, L, P.bgbit, tw0);  // rows 0, 1: a's levels 0, 1
             } else {
-                // the pair's twist factors as one read group: ahead of the tB wait (pair 1) and of the digit
-                // conversions, which cover its latency (load_digits_pair_tbx)
+                // the pair's twist factors that are not resident as one read group: ahead of the tB wait (pair 1)
+                // and of the digit conversions, which cover its latency (load_digits_pair_tbx)
                 C2 twn[8];
-                read_twist8(twn, twist_t);
+                twist8_resident(twn, tres, twist_t);
                 __builtin_amdgcn_sched_barrier(0);
                 if (rp == 1) {  // tB(i) from the loader, packed with a's level 2 (load_digits_pair_tbx)
                     pp.mark(4);
-                    spin_short(tb_ready + gi, (uint32_t)i + 1u, spin_cap, fail);
+                    uint32_t tb[16];
+                    wait_tb_words(tb_ready + gi, (uint32_t)i + 1u, Y32 + 1024 + t, spin_cap, fail, tb);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int m = 0; m < 16; m++)
                         tbx[m] = __builtin_amdgcn_ubfe(tA[m], 32 - L * P.bgbit, P.bgbit) |
-                                 (Y32[1024 + t + 64 * m] & ~((1u << P.bgbit) - 1u));
+                                 (tb[m] & ~((1u << P.bgbit) - 1u));
                 }
                 pp.mark(5);
                 load_digits_pair_tbx<FU>(d, tbx, rp, P.bgbit, twn);
@@ -353,7 +427,7 @@ __global__ __launch_bounds__(512, 1) void k_blind_rotate_assist(
         __builtin_amdgcn_sched_barrier(0);
         counter_add(fb_ready + gi);
         pp.mark(7);
-        inverse_one<FU, false>(fa, X, T, twist_t, t, accA, near);
+        inverse_one<FU, false>(fa, X, T, twist_t, t, accA, near, tres, TWIST_RES);
         wave_sync();
 #pragma unroll
         for (int m = 0; m < 16; m++) X32[t + 64 * m] = accA[m];
