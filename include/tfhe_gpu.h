@@ -912,6 +912,78 @@ int tfhe_lut_circuit_schedule_select(size_t n_inputs, size_t n_nodes, const uint
                                      const uint32_t *sel_off /*n_nodes+1*/, const uint32_t *sel_wire, uint32_t *levels,
                                      uint32_t *depth);
 
+/* ---- Extended nodes: an eta per LUT-circuit node, select nodes of up to N/2 entries ----
+ * The extended bootstrap as a property of a circuit node, ordinary or select, so that radix-32 and radix-64 digits
+ * and reads of a 32- or 64-entry encrypted table share a circuit's per-level launches.
+ * The identity the select form rests on: where 2m <= N, every component of tfhe_lut_generate_ext(eta, m, f) equals
+ * tfhe_lut_generate(m, f) word for word (a block of N E / m positions covers whole groups of E; at m = N and 2N it does
+ * not hold).  The same algebra holds for an encrypted table: m entries packed at the coefficients i*w of component 0
+ * and spread in the extended ring, with the generator's window (w = N/m, off_ext = (w/2) E, a multiple of E), put the
+ * window sum into every component, and the extended rotation by 2N E - off_ext is polyMulWithXK(., 2N - w/2) on each.
+ * So the extended test vector of a select node is E copies of the ordinary tfhe_lut_spread(P, w, 2N - off).
+ *   each_ext: output i of tfhe_gpu_bootstrap_lut_each_ext_* is, word for word, the extended bootstrap of "Extended LUT
+ *     bootstrap" for in[i] with tv_j = testvecs[i] (one TRLWELv1, any a) for every j < E: the blind rotation, then
+ *     sampleExtractIndex(acc_0, 0), then identityKeySwitching.  eta = 0 runs exactly tfhe_gpu_bootstrap_lut_each_*.
+ *   select_ext: node b of tfhe_gpu_lut_select_ext_*, with x_b, the entries and m as tfhe_gpu_lut_select_* has them:
+ *       1. P_b  = tfhe_pack_tlwe(e_b[0 .. m), coef[i] = i*w, C = m);
+ *       2. TV_b = tfhe_lut_spread(P_b, w, 2N - off);
+ *       3. out_b = the tfhe_gpu_bootstrap_lut_each_ext_* output for x_b with TV_b.
+ *     eta = 0 runs exactly tfhe_gpu_lut_select_*.
+ *   circuit: tfhe_gpu_lut_circuit_eval_ext* is tfhe_gpu_lut_circuit_eval_select* with one more HOST array, eta[g] per
+ *     node (NULL: exactly what the _select entry runs).  An ordinary node with eta[g] > 0 gives the words of
+ *     tfhe_gpu_lut_apply_ext_* for its combination and the extended table lut[g], the entries set[lut[g] E_g + j]; a
+ *     select node with eta[g] > 0 gives the words of tfhe_gpu_lut_select_ext_*.  Levels, wire numbering and the
+ *     outputs' order are the _select entry's: eta does not change a node's level.  A level runs one staging, pack and
+ *     spread over all of its select nodes whatever their eta (chunked within TFHE_OPT_PACK_SCRATCH_MB), its eta = 0
+ *     nodes exactly as the _select entry runs them (the theta > 0 handling included), one combination launch over the
+ *     rest of its nodes, ONE extended blind rotation per eta in {1, 2} present, over that eta's ordinary and select
+ *     nodes together (item by item the test vector is the set's extended table or the level's own), one extraction of
+ *     those accumulators (acc_0 only, 2N words per item) and ONE key switch over them into the level's output slots.
+ *     A group with no nodes launches nothing; grouping and chunking change no word.
+ * Noise rule: "Extended LUT bootstrap" for the input side, "Select nodes" for the table's own error; at UINT4, m = 64
+ * leaves an output 5.2 sigma and a chained input about 3.8 sigma: feed m = 64 nodes fresh inputs.
+ * Checked before any launch or upload (TFHE_ERR_INVALID): an eta > TFHE_LUT_EXT_MAX_LOG; eta > 0 with theta > 0 on one
+ * node; a lut[g] E_g + E_g beyond the set on an ordinary node; everything the entry without eta checks.
+ * TFHE_ERR_NO_KEY, zero nodes and the multi-device refusal as there. */
+int tfhe_gpu_bootstrap_lut_each_ext_batch(tfhe_gpu_ctx *ctx, uint32_t eta, const uint32_t *in /*B*(n+1)*/,
+                                          const uint32_t *testvecs /*B*2N*/, uint32_t *out /*B*(n+1)*/, size_t B);
+int tfhe_gpu_bootstrap_lut_each_ext_dev(tfhe_gpu_ctx *ctx, uint32_t eta, const uint32_t *in_dev,
+                                        const uint32_t *testvecs_dev, uint32_t *out_dev, size_t B);
+int tfhe_gpu_lut_select_ext_batch(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *pk, uint32_t m, uint32_t eta,
+                                  const uint32_t *pool, size_t P, const uint32_t *term_off /*B+1*/,
+                                  const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst /*B*/,
+                                  const uint32_t *sel_src /*B*m*/, const uint32_t *sel_konst /*B*m*/,
+                                  uint32_t *out /*B*(n+1)*/, size_t B);
+int tfhe_gpu_lut_select_ext_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_packing_key *pk, uint32_t m, uint32_t eta,
+                                const uint32_t *pool_dev, size_t P, const uint32_t *term_off /*B+1*/,
+                                const uint32_t *term_src, const int32_t *term_coef, const uint32_t *konst /*B*/,
+                                const uint32_t *sel_src /*B*m*/, const uint32_t *sel_konst /*B*m*/, uint32_t *out_dev,
+                                size_t B);
+int tfhe_gpu_lut_circuit_eval_ext(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                  uint32_t m, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
+                                  const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                  const uint32_t *konst, const uint32_t *lut, const uint32_t *theta /*n_nodes or NULL*/,
+                                  const uint32_t *sel_off /*n_nodes+1 or NULL*/, const uint32_t *sel_wire,
+                                  const uint32_t *sel_konst, const uint32_t *eta /*n_nodes or NULL*/, size_t n_outputs,
+                                  const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels);
+int tfhe_gpu_lut_circuit_eval_ext_dev(tfhe_gpu_ctx *ctx, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                      uint32_t m, size_t n_inputs, const uint32_t *inputs_dev, size_t n_nodes,
+                                      const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                      const uint32_t *konst, const uint32_t *lut, const uint32_t *theta,
+                                      const uint32_t *sel_off, const uint32_t *sel_wire, const uint32_t *sel_konst,
+                                      const uint32_t *eta, size_t n_outputs, const uint32_t *out_wires,
+                                      uint32_t *outputs_dev, uint32_t *levels);
+/* host only: tfhe_lut_circuit_schedule_select plus eta (NULL: exactly that call's levels and depth).  group_nodes
+ * (may be NULL; room for 3 * n_nodes words, 3 * depth are written) receives, per level lv = 1 .. depth, the node
+ * counts of its eta = 0, 1 and 2 groups at [3 (lv-1) + eta]: the grouping tfhe_gpu_lut_circuit_eval_ext runs.
+ * TFHE_ERR_INVALID for an eta > TFHE_LUT_EXT_MAX_LOG, eta > 0 with theta > 0 on one node, and what the _select
+ * schedule refuses. */
+int tfhe_lut_circuit_schedule_ext(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                                  const uint32_t *theta /*n_nodes or NULL*/, uint32_t m,
+                                  const uint32_t *sel_off /*n_nodes+1 or NULL*/, const uint32_t *sel_wire,
+                                  const uint32_t *eta /*n_nodes or NULL*/, uint32_t *levels, uint32_t *depth,
+                                  uint32_t *group_nodes);
+
 /* ---- Host-side TLWELv0 helpers (no device needed) ---------------------- */
 /* Host only: entry e of a lookup table as a trivial TRLWELv1 (a = 0, the form of the reference's test vectors,
  * key.zig:134-145): coefficient c < width = +1/8 if bit c of values[e] is set, else -1/8; coefficients >= width

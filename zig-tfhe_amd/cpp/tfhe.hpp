@@ -965,9 +965,12 @@ class LutCircuit {
         return n_inputs_++;
     }
     // theta > 0: a multi-output node (lut names a lutInterleave table); it drives the 2^theta wires from the
-    // returned one on, one per interleaved table.
-    Wire node(uint32_t lut, const std::vector<Term> &terms, Torus konst = 0, uint32_t theta = 0) {
+    // returned one on, one per interleaved table.  eta > 0 (include/tfhe_gpu.h "Extended nodes"): the extended
+    // bootstrap, lut naming the extended table, lutGenerateExt's 2^eta entries from lut * 2^eta on; theta is then 0.
+    Wire node(uint32_t lut, const std::vector<Term> &terms, Torus konst = 0, uint32_t theta = 0, uint32_t eta = 0) {
         if (theta > TFHE_LUT_MULTI_MAX_LOG) throw Error(TFHE_ERR_INVALID, "LutCircuit: a node has 1, 2, 4 or 8 outputs");
+        if (eta > TFHE_LUT_EXT_MAX_LOG || (eta && theta))
+            throw Error(TFHE_ERR_INVALID, "LutCircuit: a node's eta is 0, 1 or 2, and an extended node has one output");
         const Wire w = n_wires_;
         for (const Term &t : terms) {
             if (t.first >= w) throw Error(TFHE_ERR_INVALID, "LutCircuit: node terms must read existing wires");
@@ -978,13 +981,16 @@ class LutCircuit {
         konst_.push_back(konst);
         lut_.push_back(lut);
         theta_.push_back(theta);
+        eta_.push_back(eta);
         multi_ = multi_ || theta != 0;
+        ext_ = ext_ || eta != 0;
         n_wires_ += 1u << theta;
         return w;
     }
     // A select node (include/tfhe_gpu.h "Select nodes"): the digit x = sum of terms + konst picks one of the
     // m = entries.size() entries, each an earlier wire or a constant Torus word; its table is packed from the
-    // entries on the device.  One m per circuit; run / runDevice then take the packing key.
+    // entries on the device.  One m per circuit; run / runDevice then take the packing key.  eta > 0: x is read by
+    // the extended bootstrap, which keeps the margin of m = 16 at m = 32 (eta = 1) or 64 (eta = 2) on the UINT4 key.
     struct Entry {
         Wire wire = TFHE_LUT_ENTRY_CONST;
         Torus konst = 0;
@@ -995,14 +1001,14 @@ class LutCircuit {
             return e;
         }
     };
-    Wire select(const std::vector<Term> &terms, const std::vector<Entry> &entries, Torus konst = 0) {
+    Wire select(const std::vector<Term> &terms, const std::vector<Entry> &entries, Torus konst = 0, uint32_t eta = 0) {
         const uint32_t m = (uint32_t)entries.size();
         if (m < 2 || (m & (m - 1)) || (m_ && m != m_))
             throw Error(TFHE_ERR_INVALID, "LutCircuit: a select node has m entries, m a power of two >= 2, one m per circuit");
         for (const Entry &e : entries)
             if (e.wire != TFHE_LUT_ENTRY_CONST && e.wire >= n_wires_)
                 throw Error(TFHE_ERR_INVALID, "LutCircuit: select entries must read existing wires");
-        const Wire w = node(0, terms, konst);
+        const Wire w = node(0, terms, konst, 0, eta);
         m_ = m;
         for (const Entry &e : entries) sel_wire_.push_back(e.wire), sel_konst_.push_back(e.konst);
         const uint32_t last = sel_off_.back();
@@ -1011,12 +1017,13 @@ class LutCircuit {
         return w;
     }
     // f(x, y) of two m-ary digits: m ordinary nodes with the tables lut_base + i (lutGenerate2's rows) over y_terms
-    // and one select node over x_terms; returns the select node's wire.
-    Wire node2(uint32_t lut_base, const std::vector<Term> &x_terms, const std::vector<Term> &y_terms, uint32_t m) {
+    // and one select node over x_terms; returns the select node's wire.  eta is the select node's.
+    Wire node2(uint32_t lut_base, const std::vector<Term> &x_terms, const std::vector<Term> &y_terms, uint32_t m,
+               uint32_t eta = 0) {
         if (m_ && m != m_) throw Error(TFHE_ERR_INVALID, "LutCircuit: one m per circuit");
         std::vector<Entry> entries;
         for (uint32_t i = 0; i < m; i++) entries.push_back(Entry(node(lut_base + i, y_terms)));
-        return select(x_terms, entries);
+        return select(x_terms, entries, 0, eta);
     }
     void output(Wire w) { outs_.push_back(w); }
     // Least significant digit first: per digit s = a_i + b_i + carry, message = LUT_msg(s), carry = LUT_carry(s);
@@ -1061,6 +1068,19 @@ class LutCircuit {
               "LutCircuit.schedule");
         return levels;
     }
+    // tfhe_lut_circuit_schedule_ext: the levels, and per level the node counts of its eta = 0, 1 and 2 groups
+    // (groups[3 (lv - 1) + eta]), the items of that level's launches
+    std::vector<uint32_t> scheduleExt(std::vector<uint32_t> &groups, uint32_t *depth = nullptr) const {
+        std::vector<uint32_t> levels(lut_.size());
+        uint32_t d = 0;
+        groups.assign(3 * lut_.size(), 0);
+        check(tfhe_lut_circuit_schedule_ext(n_inputs_, lut_.size(), off_.data(), wire_.data(), theta(), m_, selOff(),
+                                            sel_wire_.data(), eta(), levels.data(), &d, groups.data()),
+              "LutCircuit.scheduleExt");
+        groups.resize(3 * (size_t)d);
+        if (depth) *depth = d;
+        return levels;
+    }
     // key: the packing key of a circuit with select nodes (NULL without one)
     std::vector<TLWELv0> run(const CloudKey &ck, const LutSet &set, const std::vector<TLWELv0> &inputs,
                              uint32_t *levels = nullptr, const PackingKey *key = nullptr) const {
@@ -1069,11 +1089,18 @@ class LutCircuit {
         const size_t w = ck.params().n + 1;
         std::vector<Torus> in(inputs.size() * w), out(outs_.size() * w);
         for (size_t k = 0; k < inputs.size(); k++) std::copy(inputs[k].p.begin(), inputs[k].p.end(), in.begin() + k * w);
-        check(tfhe_gpu_lut_circuit_eval_select(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_, in.data(),
-                                               lut_.size(), off_.data(), wire_.data(), coef_.data(), konst_.data(),
-                                               lut_.data(), theta(), selOff(), sel_wire_.data(), sel_konst_.data(),
-                                               outs_.size(), outs_.data(), out.data(), levels),
-              "LutCircuit.run", ck.ctx());
+        if (ext_)  // some eta > 0: the entry with eta; otherwise exactly the call without it
+            check(tfhe_gpu_lut_circuit_eval_ext(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_, in.data(),
+                                                lut_.size(), off_.data(), wire_.data(), coef_.data(), konst_.data(),
+                                                lut_.data(), theta(), selOff(), sel_wire_.data(), sel_konst_.data(),
+                                                eta(), outs_.size(), outs_.data(), out.data(), levels),
+                  "LutCircuit.run", ck.ctx());
+        else
+            check(tfhe_gpu_lut_circuit_eval_select(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_,
+                                                   in.data(), lut_.size(), off_.data(), wire_.data(), coef_.data(),
+                                                   konst_.data(), lut_.data(), theta(), selOff(), sel_wire_.data(),
+                                                   sel_konst_.data(), outs_.size(), outs_.data(), out.data(), levels),
+                  "LutCircuit.run", ck.ctx());
         std::vector<TLWELv0> r(outs_.size(), TLWELv0(ck.params().n));
         for (size_t k = 0; k < outs_.size(); k++) std::copy(out.begin() + k * w, out.begin() + (k + 1) * w, r[k].p.begin());
         return r;
@@ -1083,11 +1110,20 @@ class LutCircuit {
                        const PackingKey *key = nullptr) const {
         uint32_t levels = 0;
         if (m_ && !key) throw Error(TFHE_ERR_INVALID, "LutCircuit: select nodes need a packing key");
-        check(tfhe_gpu_lut_circuit_eval_select_dev(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_,
-                                                   inputs_dev, lut_.size(), off_.data(), wire_.data(), coef_.data(),
-                                                   konst_.data(), lut_.data(), theta(), selOff(), sel_wire_.data(),
-                                                   sel_konst_.data(), outs_.size(), outs_.data(), outputs_dev, &levels),
-              "LutCircuit.runDevice", ck.ctx());
+        if (ext_)
+            check(tfhe_gpu_lut_circuit_eval_ext_dev(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_,
+                                                    inputs_dev, lut_.size(), off_.data(), wire_.data(), coef_.data(),
+                                                    konst_.data(), lut_.data(), theta(), selOff(), sel_wire_.data(),
+                                                    sel_konst_.data(), eta(), outs_.size(), outs_.data(), outputs_dev,
+                                                    &levels),
+                  "LutCircuit.runDevice", ck.ctx());
+        else
+            check(tfhe_gpu_lut_circuit_eval_select_dev(ck.ctx(), set.get(), key ? key->get() : nullptr, m_, n_inputs_,
+                                                       inputs_dev, lut_.size(), off_.data(), wire_.data(), coef_.data(),
+                                                       konst_.data(), lut_.data(), theta(), selOff(), sel_wire_.data(),
+                                                       sel_konst_.data(), outs_.size(), outs_.data(), outputs_dev,
+                                                       &levels),
+                  "LutCircuit.runDevice", ck.ctx());
         return levels;
     }
     size_t numInputs() const { return n_inputs_; }
@@ -1097,6 +1133,8 @@ class LutCircuit {
   private:
     // NULL without a multi-output node: the _multi entries are then the single-output ones
     const uint32_t *theta() const { return multi_ ? theta_.data() : nullptr; }
+    // NULL without an extended node
+    const uint32_t *eta() const { return ext_ ? eta_.data() : nullptr; }
     // NULL without a select node (the _select entries are then the _multi ones); else one offset per node and one
     // more, the nodes behind the last select node without entries
     const uint32_t *selOff() const {
@@ -1106,8 +1144,8 @@ class LutCircuit {
         return sel_off_.data();
     }
     uint32_t n_inputs_ = 0, n_wires_ = 0, m_ = 0;
-    bool multi_ = false;
-    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, theta_, outs_, sel_wire_, sel_konst_;
+    bool multi_ = false, ext_ = false;
+    std::vector<uint32_t> off_{0}, wire_, konst_, lut_, theta_, eta_, outs_, sel_wire_, sel_konst_;
     mutable std::vector<uint32_t> sel_off_{0};
     std::vector<int32_t> coef_;
 };
@@ -1119,8 +1157,9 @@ struct LutSelectNode {
     std::vector<LutCircuit::Entry> entries;
     Torus konst = 0;
 };
+// eta > 0: tfhe_gpu_lut_select_ext_batch (lutSelectExt below).
 inline std::vector<TLWELv0> lutSelect(const CloudKey &ck, const PackingKey &key, uint32_t m, const std::vector<TLWELv0> &pool,
-                                      const std::vector<LutSelectNode> &nodes) {
+                                      const std::vector<LutSelectNode> &nodes, uint32_t eta = 0) {
     const size_t B = nodes.size(), w = ck.params().n + 1;
     std::vector<Torus> x(pool.size() * w), out(B * w);
     std::vector<uint32_t> off{0}, src, konst, sel_src, sel_konst;
@@ -1133,9 +1172,39 @@ inline std::vector<TLWELv0> lutSelect(const CloudKey &ck, const PackingKey &key,
         konst.push_back(nd.konst);
         for (const LutCircuit::Entry &e : nd.entries) sel_src.push_back(e.wire), sel_konst.push_back(e.konst);
     }
-    check(tfhe_gpu_lut_select_batch(ck.ctx(), key.get(), m, x.data(), pool.size(), off.data(), src.data(), coef.data(),
-                                    konst.data(), sel_src.data(), sel_konst.data(), out.data(), B),
-          "lut_select", ck.ctx());
+    if (eta)
+        check(tfhe_gpu_lut_select_ext_batch(ck.ctx(), key.get(), m, eta, x.data(), pool.size(), off.data(), src.data(),
+                                            coef.data(), konst.data(), sel_src.data(), sel_konst.data(), out.data(), B),
+              "lut_select_ext", ck.ctx());
+    else
+        check(tfhe_gpu_lut_select_batch(ck.ctx(), key.get(), m, x.data(), pool.size(), off.data(), src.data(), coef.data(),
+                                        konst.data(), sel_src.data(), sel_konst.data(), out.data(), B),
+              "lut_select", ck.ctx());
+    std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
+    for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
+    return r;
+}
+
+// tfhe_gpu_lut_select_ext_batch: lutSelect with the extended bootstrap, so that m may be 32 (eta = 1) or 64 (eta = 2).
+inline std::vector<TLWELv0> lutSelectExt(const CloudKey &ck, const PackingKey &key, uint32_t m, uint32_t eta,
+                                         const std::vector<TLWELv0> &pool, const std::vector<LutSelectNode> &nodes) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) throw Error(TFHE_ERR_INVALID, "lutSelectExt: eta > TFHE_LUT_EXT_MAX_LOG");
+    return lutSelect(ck, key, m, pool, nodes, eta);
+}
+
+// tfhe_gpu_bootstrap_lut_each_ext_batch: the extended bootstrap of item i with its one test vector testvecs[i] (any
+// a) in all 2^eta components.
+inline std::vector<TLWELv0> bootstrapLutEachExt(const CloudKey &ck, uint32_t eta, const std::vector<TLWELv0> &in,
+                                                const std::vector<TRLWELv1> &testvecs) {
+    const size_t B = in.size(), w = ck.params().n + 1, W = 2 * (size_t)ck.params().N;
+    if (testvecs.size() != B) throw Error(TFHE_ERR_INVALID, "bootstrapLutEachExt: one test vector per input");
+    std::vector<Torus> x(B * w), tv(B * W), out(B * w);
+    for (size_t b = 0; b < B; b++) {
+        std::copy(in[b].p.begin(), in[b].p.end(), x.begin() + b * w);
+        std::copy(testvecs[b].p.begin(), testvecs[b].p.end(), tv.begin() + b * W);
+    }
+    check(tfhe_gpu_bootstrap_lut_each_ext_batch(ck.ctx(), eta, x.data(), tv.data(), out.data(), B), "bootstrap_lut_each_ext",
+          ck.ctx());
     std::vector<TLWELv0> r(B, TLWELv0(ck.params().n));
     for (size_t b = 0; b < B; b++) std::copy(out.begin() + b * w, out.begin() + (b + 1) * w, r[b].p.begin());
     return r;

@@ -389,10 +389,18 @@ const char *schedule_lut_levels(size_t n_inputs, size_t n_nodes, const uint32_t 
     return nullptr;
 }
 
+const char *check_lut_eta(size_t n_nodes, const uint32_t *theta, const uint32_t *eta) {
+    for (size_t g = 0; eta && g < n_nodes; g++) {
+        if (eta[g] > TFHE_LUT_EXT_MAX_LOG) return "eta > TFHE_LUT_EXT_MAX_LOG";
+        if (eta[g] && theta && theta[g]) return "a node has eta > 0 and theta > 0";
+    }
+    return nullptr;
+}
+
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
                              size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl, const uint32_t *theta,
-                             const LutSelect *sel) {
+                             const LutSelect *sel, const uint32_t *eta) {
     std::vector<size_t> fo;  // node g's first output wire, relative to n_inputs
     if (const char *why = lut_output_offsets(n_nodes, theta, fo)) return why;
     const size_t W = n_inputs + fo[n_nodes];
@@ -401,24 +409,31 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     if (const char *why = schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, pl.level, pl.depth, theta, sel))
         return why;
     if (sel && n_nodes && sel->off[n_nodes] && !sel->konst) return "null select constants";
+    if (const char *why = check_lut_eta(n_nodes, theta, eta)) return why;
     auto is_sel = [&](size_t g) { return sel && sel->off[g + 1] != sel->off[g]; };
+    auto eta_of = [&](size_t g) { return eta ? eta[g] : 0u; };
     for (size_t g = 0; g < n_nodes; g++) {
         if (is_sel(g) && lut[g] != 0) return "a select node has lut != 0";
         if (lut[g] >= T) return "table index >= the set's size";
+        // the extended table t is the entries t E .. t E + E - 1
+        if (!is_sel(g) && (((uint64_t)lut[g] + 1) << eta_of(g)) > T) return "extended table index E + E exceeds the set";
     }
     for (size_t o = 0; o < n_outputs; o++)
         if (out_wires[o] >= W) return "output wire out of range";
-    // slots in level order (a counting sort of the nodes by level, a level's ordinary nodes ahead of its
-    // select nodes, keeps node order inside either group)
+    // slots in level order (a counting sort of the nodes by level, then eta, a group's ordinary nodes ahead of
+    // its select nodes, keeps node order inside each)
     const uint32_t m = sel ? sel->m : 0;
     pl.first.assign((size_t)pl.depth + 1, 0);
     pl.ofirst.assign((size_t)pl.depth + 1, 0);
     pl.sfirst.assign((size_t)pl.depth + 1, 0);
     pl.nsel.assign(pl.depth, 0);
+    pl.neta.assign(3 * (size_t)pl.depth, 0);
+    pl.nsel_eta.assign(3 * (size_t)pl.depth, 0);
     for (size_t g = 0; g < n_nodes; g++) {
         pl.first[pl.level[g]]++;  // level lv's count at [lv]
         pl.ofirst[pl.level[g]] += (uint32_t)(fo[g + 1] - fo[g]);
-        if (is_sel(g)) pl.sfirst[pl.level[g]]++, pl.nsel[pl.level[g] - 1]++;
+        pl.neta[3 * (pl.level[g] - 1) + eta_of(g)]++;
+        if (is_sel(g)) pl.sfirst[pl.level[g]]++, pl.nsel[pl.level[g] - 1]++, pl.nsel_eta[3 * (pl.level[g] - 1) + eta_of(g)]++;
     }
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {  // -> its end, its start at [lv - 1]
         pl.first[lv] += pl.first[lv - 1];
@@ -429,12 +444,17 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     pl.slot.assign(W, 0);
     for (size_t w = 0; w < n_inputs; w++) pl.slot[w] = (uint32_t)w;
     {
-        std::vector<uint32_t> next(pl.first.begin(), pl.first.end()), snext(pl.depth);
-        for (uint32_t lv = 1; lv <= pl.depth; lv++) snext[lv - 1] = pl.first[lv] - pl.nsel[lv - 1];
-        for (size_t g = 0; g < n_nodes; g++) {
-            const uint32_t lv = pl.level[g];
-            pl.order[is_sel(g) ? snext[lv - 1]++ : next[lv - 1]++] = (uint32_t)g;
-        }
+        // next[6 (lv-1) + 2 e + s]: where the next node of level lv, group e, kind s (1: select) goes
+        std::vector<uint32_t> next(6 * (size_t)pl.depth);
+        for (uint32_t lv = 1; lv <= pl.depth; lv++)
+            for (uint32_t e = 0, at = pl.first[lv - 1]; e < 3; e++) {
+                const uint32_t ne = pl.neta[3 * (lv - 1) + e], ns = pl.nsel_eta[3 * (lv - 1) + e];
+                next[6 * (lv - 1) + 2 * e] = at;
+                next[6 * (lv - 1) + 2 * e + 1] = at + ne - ns;
+                at += ne;
+            }
+        for (size_t g = 0; g < n_nodes; g++)
+            pl.order[next[6 * (pl.level[g] - 1) + 2 * eta_of(g) + (is_sel(g) ? 1 : 0)]++] = (uint32_t)g;
         size_t out_slot = n_inputs;  // the levels are consecutive in `order`, and so are their output slots
         for (size_t at = 0; at < n_nodes; at++)
             for (size_t j = fo[pl.order[at]]; j < fo[pl.order[at] + 1]; j++) pl.slot[n_inputs + j] = (uint32_t)out_slot++;
@@ -449,6 +469,7 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
     pl.theta.clear();
     pl.fan.clear();
     pl.tv_sel.clear();
+    pl.eta.clear();
     pl.e_off.assign(1, 0);
     pl.e_src.clear();
     pl.e_konst.clear();
@@ -469,6 +490,7 @@ const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *te
             pl.konst.push_back(konst[g]);
             pl.lut.push_back(lut[g]);
             pl.theta.push_back(theta ? theta[g] : 0u);
+            pl.eta.push_back(eta_of(g));
             pl.tv_sel.push_back(is_sel(g) ? LUT_TV_EACH | k_sel++ : lut[g]);
             for (uint32_t j = 0; j < fo[g + 1] - fo[g]; j++) {
                 pl.fan.push_back(at - pl.first[lv - 1]);
@@ -811,6 +833,23 @@ int tfhe_lut_circuit_schedule_select(size_t n_inputs, size_t n_nodes, const uint
     if (schedule_lut_levels(n_inputs, n_nodes, term_off, term_wire, level, d, theta, &sel)) return TFHE_ERR_INVALID;
     std::copy(level.begin(), level.end(), levels);
     if (depth) *depth = d;
+    return TFHE_OK;
+}
+
+int tfhe_lut_circuit_schedule_ext(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
+                                  const uint32_t *theta, uint32_t m, const uint32_t *sel_off, const uint32_t *sel_wire,
+                                  const uint32_t *eta, uint32_t *levels, uint32_t *depth, uint32_t *group_nodes) {
+    if (n_nodes && !levels) return TFHE_ERR_INVALID;
+    if (check_lut_eta(n_nodes, theta, eta)) return TFHE_ERR_INVALID;
+    uint32_t d = 0;
+    if (const int rc = tfhe_lut_circuit_schedule_select(n_inputs, n_nodes, term_off, term_wire, theta, m, sel_off,
+                                                        sel_wire, levels, &d))
+        return rc;
+    if (depth) *depth = d;
+    if (group_nodes) {
+        std::fill(group_nodes, group_nodes + 3 * (size_t)d, 0u);
+        for (size_t g = 0; g < n_nodes; g++) group_nodes[3 * (levels[g] - 1) + (eta ? eta[g] : 0u)]++;
+    }
     return TFHE_OK;
 }
 

@@ -105,6 +105,13 @@ uint32_t lut_round_shift(const tfhe_params &p, uint32_t theta);
 // The entries are one CSR over all select nodes in evaluation order, m per node in pack order: entry j
 // has the e_off[j+1] - e_off[j] <= 1 terms e_src[..] (a slot, coefficient 1) and the constant e_konst[j],
 // which is what the combine kernel takes; level lv's start at sfirst[lv-1] * m.
+// Extended nodes (eta != nullptr, include/tfhe_gpu.h "Extended nodes"): a level's run of `order` is grouped by eta,
+// eta = 0 first, and inside each group holds the ordinary nodes, then the select nodes, as above; so the eta = 0
+// part of a level is laid out as the whole level is without eta, and each extended group is one run of items and
+// of output slots behind it.  neta[3 (lv-1) + e] / nsel_eta[3 (lv-1) + e] count the nodes / the select nodes of
+// group e of level lv.  The level's select nodes are numbered (tv_sel, the entries' CSR) in evaluation order across
+// the groups, so one staging, pack and spread serves them all.  An extended node has theta 0: one output slot.
+// eta holds each node's eta in evaluation order (all 0 without eta).
 constexpr uint32_t LUT_TV_EACH = 0x80000000u;
 struct LutCircuitPlan {
     uint32_t depth = 0;
@@ -122,11 +129,16 @@ struct LutCircuitPlan {
     std::vector<uint32_t> sfirst;  // depth + 1 entries
     std::vector<uint32_t> tv_sel;  // per node, evaluation order
     std::vector<uint32_t> e_off, e_src, e_konst;  // sfirst[depth] * m + 1 offsets, the wire entries' slots, one constant per entry
+    std::vector<uint32_t> eta;             // per node, evaluation order
+    std::vector<uint32_t> neta, nsel_eta;  // 3 per level
 };
 const char *plan_lut_circuit(size_t n_inputs, size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire,
                              const int32_t *term_coef, const uint32_t *konst, const uint32_t *lut, size_t T,
                              size_t n_outputs, const uint32_t *out_wires, LutCircuitPlan &pl,
-                             const uint32_t *theta = nullptr, const LutSelect *sel = nullptr);
+                             const uint32_t *theta = nullptr, const LutSelect *sel = nullptr,
+                             const uint32_t *eta = nullptr);
+// nullptr, or what is wrong with the etas themselves: one > TFHE_LUT_EXT_MAX_LOG, or eta > 0 with theta > 0 on a node
+const char *check_lut_eta(size_t n_nodes, const uint32_t *theta, const uint32_t *eta);
 
 // ---- Packing key switch (tfhe_pack_tlwe here; tfhe_pack.cpp runs it on the device) ----
 // The shapes with the one-hot GEMM form (ks_gemm_supported, tfhe_kernels.hip): basebit 2 with

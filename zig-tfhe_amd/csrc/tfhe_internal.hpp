@@ -360,13 +360,14 @@ hipError_t launch_lut_spread(const uint32_t *in, uint32_t w, uint32_t rot, uint3
 // One batch of extended blind rotations (k_blind_rotate_ext, include/tfhe_gpu.h "Extended LUT bootstrap"),
 // device pointers: item g rotates in[g] (n + 1 words) over the extended table at
 // testvec + tv_sel[g] * E * 2N (tv_sel NULL: the one table at testvec), E = 2^eta components of 2N words, with
-// the BK in device layout.  all: out takes the E accumulators of every item (item-major, B * E * 2N words);
+// the BK in device layout.  An entry of tv_sel with TV_SEL_EACH set names instead the one TRLWELv1 (any a) at
+// tv_each + (entry & ~TV_SEL_EACH) * 2N, which all E components start from (select nodes).  all: out takes the E accumulators of every item (item-major, B * E * 2N words);
 // else acc_0 only (B * 2N words).  eta is 1 or 2: hipErrorInvalidValue otherwise.  P.offset is the key's
 // decomposition offset.
 struct BrExtBatch {
     uint32_t eta = 0;
     const uint32_t *in = nullptr;
-    const uint32_t *testvec = nullptr, *tv_sel = nullptr;
+    const uint32_t *testvec = nullptr, *tv_sel = nullptr, *tv_each = nullptr;
     const double *bk = nullptr;
     uint32_t *out = nullptr;
     bool all = false;

@@ -29,7 +29,10 @@ namespace tfhe {
 // The exponent q + [k < r] reaches 2N (q = 2N - 1 with k < r, and a~ = 2N E): it is reduced mod 2N
 // before rot_read, whose index mask would take it as well.
 // tv: the item's extended table, E consecutive TRLWELv1 at testvec + tv_sel[g] * E * 2N (tv_sel NULL:
-// the one shared table at testvec).
+// the one shared table at testvec); or, where tv_sel[g] has TV_SEL_EACH set, the one TRLWELv1 (any a) at
+// tv_each + (tv_sel[g] & ~TV_SEL_EACH) * 2N for every component: the extended test vector of a select node is E
+// copies of its ordinary one, so all E waves read it, each with its own exponent.  g is
+// workgroup-uniform, so the choice is a scalar branch in the prologue only; the steps do not change.
 //
 // The BK rows, two forms (EXT_BK_LDS<E>), both measured at UINT4 with 1,024 items:
 //   global  every wave reads its rows from global memory (ext_pairs_chain); all workgroups walk the BK in
@@ -81,6 +84,7 @@ template <int L, int E>
 __global__ __launch_bounds__(64 * E) void k_blind_rotate_ext(KParams P, DevTables TT, const uint32_t *__restrict__ in,
                                                              const uint32_t *__restrict__ testvec,
                                                              const uint32_t *__restrict__ tv_sel,
+                                                             const uint32_t *__restrict__ tv_each,
                                                              const double2 *__restrict__ bk, uint32_t *__restrict__ out,
                                                              int all) {
     constexpr int ETA = E == 2 ? 1 : 2;
@@ -101,7 +105,9 @@ __global__ __launch_bounds__(64 * E) void k_blind_rotate_ext(KParams P, DevTable
     {
         const uint32_t bt = (uint32_t)(2048 * E) - (uint32_t)(((uint64_t)x[n] + HALF) >> SH);  // in [0, 2N E]
         const int q = (int)(bt >> ETA), r = (int)(bt & (E - 1));
-        const uint32_t *tv = testvec + ((size_t)(tv_sel ? tv_sel[g] : 0u) * E + ((k - r) & (E - 1))) * 2048;
+        const uint32_t sel = tv_sel ? tv_sel[g] : 0u;
+        const uint32_t *tv = (sel & TV_SEL_EACH) ? tv_each + (size_t)(sel & ~TV_SEL_EACH) * 2048
+                                                 : testvec + ((size_t)sel * E + ((k - r) & (E - 1))) * 2048;
         const int ex = (q + (k < r ? 1 : 0)) & 2047;
 #pragma unroll
         for (int m = 0; m < 16; m++) {
@@ -173,7 +179,7 @@ __global__ __launch_bounds__(64 * E) void k_blind_rotate_ext(KParams P, DevTable
 
 template <int L, int E>
 static const char *ext_launch(dim3 grid, hipStream_t s, const KParams &P, const DevTables &T, const BrExtBatch &b) {
-    hipLaunchKernelGGL((k_blind_rotate_ext<L, E>), grid, dim3(64 * E), 0, s, P, T, b.in, b.testvec, b.tv_sel,
+    hipLaunchKernelGGL((k_blind_rotate_ext<L, E>), grid, dim3(64 * E), 0, s, P, T, b.in, b.testvec, b.tv_sel, b.tv_each,
                        reinterpret_cast<const double2 *>(b.bk), b.out, b.all ? 1 : 0);
     // the dispatch table: (L, E) -> the name last_kernels() reports
     static const char *const names[3][2] = {{"k_blind_rotate_ext<1,2>", "k_blind_rotate_ext<1,4>"},

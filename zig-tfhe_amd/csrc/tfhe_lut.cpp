@@ -13,6 +13,10 @@
 // shares its level's bootstrap launch with the ordinary nodes (KParams::tv_each).  The extended
 // bootstrap (lut_apply_ext_on) is lut_apply_on with k_blind_rotate_ext (tfhe_kernels_lut_ext.hip) on
 // 2^eta accumulator components in place of the blind rotation, then the extraction and the key switch.
+// Extended nodes (lut_circuit_on with the plan's eta groups) run it inside the circuit
+// evaluator: a select node's extended test vector is E copies of its ordinary one, so the level's one pack
+// serves every eta, and each eta > 0 has one k_blind_rotate_ext launch over its ordinary and select nodes
+// (BrExtBatch::tv_each); each_ext_entry and lut_select_on with an eta are the flat forms.
 // Everything here runs on the context's first device.
 #include "tfhe_gpu.h"
 
@@ -123,10 +127,43 @@ static int lut_apply_multi_on(Device &d, const tfhe_gpu_lut_set &set, const uint
 static_assert(LUT_TV_EACH == TV_SEL_EACH, "the planner's selector bit is the kernels'");
 
 // The selector of a bootstrap whose item g reads testvecs + g * 2N: 0 .. B-1, appended to a call's descriptors.
-static size_t add_iota(DescBlob &blob, size_t B) {
+// mask: LUT_TV_EACH for the extended blind rotation, whose selector names the caller's buffer by that bit.
+static size_t add_iota(DescBlob &blob, size_t B, uint32_t mask = 0) {
     const size_t at = blob.words.size();
-    for (size_t i = 0; i < B; i++) blob.words.push_back((uint32_t)i);
+    for (size_t i = 0; i < B; i++) blob.words.push_back((uint32_t)i | mask);
     return at;
+}
+
+// The extended blind rotation over device buffers, async: all E accumulators of each item (all) or acc_0.
+// tv_each: the base of the entries of tv_sel with TV_SEL_EACH set (select nodes), or NULL.
+static int blind_rotate_ext_launch(Device &d, uint32_t eta, const uint32_t *x, const uint32_t *testvec,
+                                   const uint32_t *tv_sel, uint32_t *acc, bool all, size_t B,
+                                   const uint32_t *tv_each = nullptr) {
+    BrExtBatch b;
+    b.eta = eta;
+    b.in = x;
+    b.testvec = testvec;
+    b.tv_sel = tv_sel;
+    b.tv_each = tv_each;
+    b.bk = d.d_bk;
+    b.out = acc;
+    b.all = all;
+    b.B = B;
+    d.last_ks = "";
+    HIPCHK(d, launch_blind_rotate_ext(d.K, tables(d), b, d.stream, &d.last_br));
+    d.bootstraps += B;
+    return TFHE_OK;
+}
+
+// The end of an extended bootstrap over B accumulators acc_0 (2N words each): sampleExtractIndex(., 0) into lv1
+// (f.ks_input of B * 1025 words) and one key switch into out.  zero: a device word 0, the extraction's coefficient.
+static int ext_extract_ks(Device &d, Frame &f, const uint32_t *acc, const uint32_t *zero, uint32_t *lv1, uint32_t *out,
+                          size_t B) {
+    HIPCHK(d, launch_sample_extract(acc, zero, 1, lv1, B, d.stream));
+    KsGemm G;
+    if (const int rc = ks_gemm_args(f, B, G)) return rc;
+    HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, B, d.stream, d.opts, &d.last_ks, &G));
+    return TFHE_OK;
 }
 
 // The test vectors of ns select nodes (include/tfhe_gpu.h "Select nodes") into tv (ns TRLWELv1): per chunk of
@@ -163,7 +200,9 @@ static size_t add_slot_coefs(DescBlob &blob, uint32_t N, uint32_t m) {
 // A whole LUT circuit: one combine and one bootstrap launch per level into the
 // wire table (in the plan's slot order), the outputs gathered at the end; a level's temporaries go with its frame.
 // A level with select nodes (pk, m: theirs) builds their test vectors first; its one bootstrap launch then reads,
-// item by item, the set or those (the plan's tv_sel, KParams::tv_each).
+// item by item, the set or those (the plan's tv_sel, KParams::tv_each).  Extended nodes (the plan's eta groups) share
+// the level's combination launch and its select nodes' pack, and run one k_blind_rotate_ext launch per eta, one
+// extraction and one key switch behind the level's eta = 0 launches; without them a level runs what it ran before.
 static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_inputs, const uint32_t *inputs, size_t n_nodes,
                           const LutCircuitPlan &pl, size_t n_outputs, uint32_t *outputs, bool dev,
                           const tfhe_gpu_packing_key *pk = nullptr, uint32_t m = 0) {
@@ -172,6 +211,7 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     // multi-output nodes anywhere: round_theta's shift per node (evaluation order) and the plan's fan-out pairs
     const bool multi = std::any_of(pl.theta.begin(), pl.theta.end(), [](uint32_t t) { return t != 0; });
     const bool select = pl.depth && pl.sfirst[pl.depth] != 0;
+    const bool ext = std::any_of(pl.eta.begin(), pl.eta.end(), [](uint32_t e) { return e != 0; });
     std::vector<uint32_t> shift;
     if (multi)
         for (uint32_t t : pl.theta) shift.push_back(lut_round_shift(d.P, t));
@@ -187,7 +227,8 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
                  esrc_at = select ? blob.add(pl.e_src.data(), pl.e_src.size()) : 0,
                  one_at = select ? blob.add(ones.data(), ones.size()) : 0,
                  ekonst_at = select ? blob.add(pl.e_konst.data(), pl.e_konst.size()) : 0,
-                 pcoef_at = select ? add_slot_coefs(blob, d.P.N, m) : 0;
+                 pcoef_at = select ? add_slot_coefs(blob, d.P.N, m) : 0,
+                 zero_at = ext ? blob.reserve(1) : 0;  // the extraction's coefficient 0
     Frame f(d);
     Io io{f, dev};
     uint32_t *wires = f.take<uint32_t>(W * w);
@@ -200,13 +241,16 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
     const int32_t *coef = reinterpret_cast<const int32_t *>(desc + coef_at);
     for (uint32_t lv = 1; lv <= pl.depth; lv++) {
         const size_t at = pl.first[lv - 1], nb = pl.first[lv] - at, oat = pl.ofirst[lv - 1], no = pl.ofirst[lv] - oat;
-        const size_t ns = pl.nsel[lv - 1], nord = nb - ns;  // the level's run: its ordinary nodes, then its select nodes
+        // the level's run: its eta = 0 nodes (ordinary, then select), then its eta = 1 and its eta = 2 nodes (the same)
+        const uint32_t *ne = pl.neta.data() + 3 * (size_t)(lv - 1), *nse = pl.nsel_eta.data() + 3 * (size_t)(lv - 1);
+        const size_t next = (size_t)ne[1] + ne[2], nb0 = nb - next, no0 = no - next;  // an extended node has one output
+        const size_t ns = pl.nsel[lv - 1], ns0 = nse[0], nord = nb0 - ns0;
         const uint32_t *off = desc + off_at + at + (lv - 1);
         uint32_t *level_out = wires + (n_inputs + oat) * w;  // the level's outputs: one run of slots
         // reads slots below this level's first (earlier wires), writes the level's staging slices
         Frame level(d);
         uint32_t *tv = nullptr;
-        if (ns) {
+        if (ns) {  // the test vectors of all of the level's select nodes, whatever their eta
             tv = level.take<uint32_t>(ns * 2 * (size_t)d.P.N);
             if ((rc = level.rc())) return rc;
             const size_t e0 = (size_t)pl.sfirst[lv - 1] * m;
@@ -216,21 +260,36 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
             if (rc) return rc;
         }
         // a theta > 0 in this level: the ordinary nodes as before, the select nodes in one launch of their own
-        const bool split = no != nb;
+        const bool split = no0 != nb0;
         if (split) {
             rc = lut_multi_launch(d, set, wires, off, desc + src_at, coef, desc + konst_at + at, desc + lut_at + at,
-                                  desc + shift_at + at, desc + fan_at + 2 * oat, level_out, nord, no - ns);
+                                  desc + shift_at + at, desc + fan_at + 2 * oat, level_out, nord, no0 - ns0);
             if (rc) return rc;
-            if (!ns) continue;
         }
-        const size_t skip = split ? nord : 0, items = nb - skip;
+        // one combination launch over the rest: the eta = 0 items of the bootstrap launch, then the extended groups
+        const size_t skip = split ? nord : 0, items = nb - skip, items0 = nb0 - skip;
+        if (!items) continue;
         uint32_t *x = level.take<uint32_t>(items * w);
         if ((rc = level.rc())) return rc;
         HIPCHK(d, launch_lut_combine(d.K, wires, off + skip, desc + src_at, coef, desc + konst_at + at + skip, x, items,
                                      d.stream));
-        rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, level_out + (no - items) * w, items, RUN_BOOTSTRAP,
-                               nullptr, desc + lut_at + at + skip, tv);
-        if (rc) return rc;
+        if (items0) {
+            rc = run_bootstrap_dev(d, nullptr, x, nullptr, set.tables, level_out + (no0 - items0) * w, items0,
+                                   RUN_BOOTSTRAP, nullptr, desc + lut_at + at + skip, tv);
+            if (rc) return rc;
+        }
+        if (!next) continue;
+        // one extended blind rotation per eta present (acc_0 of each item), then one extraction and one key switch
+        // over both groups into the slots behind the eta = 0 outputs
+        uint32_t *acc = level.take<uint32_t>(next * 2 * (size_t)d.P.N), *lv1 = level.ks_input<uint32_t>(next * 1025);
+        if ((rc = level.rc())) return rc;
+        for (size_t e = 1, done = 0; e <= 2; done += ne[e], e++) {
+            if (!ne[e]) continue;
+            rc = blind_rotate_ext_launch(d, (uint32_t)e, x + (items0 + done) * w, set.tables, desc + lut_at + at + nb0 + done,
+                                         acc + done * 2 * (size_t)d.P.N, /*all*/ false, ne[e], tv);
+            if (rc) return rc;
+        }
+        if ((rc = ext_extract_ks(d, level, acc, desc + zero_at, lv1, level_out + no0 * w, next))) return rc;
     }
     if (n_outputs) HIPCHK(d, launch_tlwe_gather(d.K, wires, desc + out_at, outputs, n_outputs, false, d.stream));
     return io.finish();
@@ -241,7 +300,7 @@ static int lut_circuit_on(Device &d, const tfhe_gpu_lut_set &set, size_t n_input
 static int lut_select_on(Device &d, const tfhe_gpu_packing_key &pk, uint32_t m, const uint32_t *pool, size_t P,
                          const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
                          const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out,
-                         size_t B, bool dev) {
+                         size_t B, bool dev, uint32_t eta = 0) {
     if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
     const size_t w = tlwe0_words(d.P), terms = term_off[B], E = B * m;
     std::vector<uint32_t> e_off(1, 0u), e_src, e_konst(E);
@@ -257,20 +316,29 @@ static int lut_select_on(Device &d, const tfhe_gpu_packing_key &pk, uint32_t m, 
                  coef_at = blob.add(term_coef, terms), konst_at = blob.add(konst, B),
                  eoff_at = blob.add(e_off.data(), e_off.size()), esrc_at = blob.add(e_src.data(), e_src.size()),
                  one_at = blob.add(ones.data(), ones.size()), ekonst_at = blob.add(e_konst.data(), E),
-                 pcoef_at = add_slot_coefs(blob, d.P.N, m), iota_at = add_iota(blob, B);
+                 pcoef_at = add_slot_coefs(blob, d.P.N, m), iota_at = add_iota(blob, B, eta ? LUT_TV_EACH : 0),
+                 zero_at = blob.reserve(1);  // the extraction's coefficient 0 (eta > 0)
     Frame f(d);
     Io io{f, dev};
     const uint32_t *desc = blob.upload(f);
     if (terms || !e_src.empty()) io.in(pool, P * w * 4);  // neither: the pool (may be NULL) is never read
     int rc = io.out(out, B * w * 4);
     uint32_t *x = f.take<uint32_t>(B * w), *tv = f.take<uint32_t>(B * 2 * (size_t)d.P.N);
+    // eta > 0: acc_0 of each item and the key switch's input
+    uint32_t *acc = eta ? f.take<uint32_t>(B * 2 * (size_t)d.P.N) : nullptr;
+    uint32_t *lv1 = eta ? f.ks_input<uint32_t>(B * 1025) : nullptr;
     if ((rc = f.rc())) return rc;
     HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
                                  desc + konst_at, x, B, d.stream));
     rc = select_testvecs(d, pk, m, pool, desc + eoff_at, desc + esrc_at, reinterpret_cast<const int32_t *>(desc + one_at),
                          desc + ekonst_at, desc + pcoef_at, tv, B);
     if (rc) return rc;
-    rc = run_bootstrap_dev(d, nullptr, x, nullptr, tv, out, B, RUN_BOOTSTRAP, nullptr, desc + iota_at);
+    if (eta) {  // every item reads its own test vector in all E components
+        rc = blind_rotate_ext_launch(d, eta, x, nullptr, desc + iota_at, acc, /*all*/ false, B, tv);
+        if (!rc) rc = ext_extract_ks(d, f, acc, desc + zero_at, lv1, out, B);
+    } else {
+        rc = run_bootstrap_dev(d, nullptr, x, nullptr, tv, out, B, RUN_BOOTSTRAP, nullptr, desc + iota_at);
+    }
     return rc ? rc : io.finish();
 }
 
@@ -310,7 +378,8 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
                          size_t n_nodes, const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
                          const uint32_t *konst, const uint32_t *lut, const uint32_t *theta, size_t n_outputs,
                          const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels, bool dev,
-                         const tfhe_gpu_packing_key *pk = nullptr, const LutSelect *sel = nullptr) {
+                         const tfhe_gpu_packing_key *pk = nullptr, const LutSelect *sel = nullptr,
+                         const uint32_t *eta = nullptr) {
     if (!c || !set || (n_inputs && !inputs) || (n_nodes && (!term_off || !konst || !lut)) ||
         (n_outputs && (!out_wires || !outputs)) || (sel && !pk))
         return fail(c, TFHE_ERR_INVALID, "null argument");
@@ -324,7 +393,7 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
     if (n_nodes && term_off[n_nodes] && (!term_wire || !term_coef)) return fail(c, TFHE_ERR_INVALID, "null argument");
     LutCircuitPlan pl;
     if (const char *why = plan_lut_circuit(n_inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, set->T,
-                                           n_outputs, out_wires, pl, theta, sel))
+                                           n_outputs, out_wires, pl, theta, sel, eta))
         return fail(c, TFHE_ERR_INVALID, std::string("LUT circuit: ") + why);
     const int rc = on_device0(c, [&](Device &d) {
         return lut_circuit_on(d, *set, n_inputs, inputs, n_nodes, pl, n_outputs, outputs, dev, pk, sel ? sel->m : 0);
@@ -336,7 +405,8 @@ static int circuit_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, size_t n_
 static int select_entry(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, const uint32_t *pool, size_t P,
                         const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
                         const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out, size_t B,
-                        bool dev) {
+                        bool dev, uint32_t eta = 0) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "lut_select: eta > TFHE_LUT_EXT_MAX_LOG");
     if (!c || !pk || (B && (!term_off || !konst || !sel_src || !sel_konst || !out)))
         return fail(c, TFHE_ERR_INVALID, "null argument");
     if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
@@ -351,7 +421,8 @@ static int select_entry(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_
         if (sel_src[j] != TFHE_LUT_ENTRY_CONST && (sel_src[j] >= P || !pool))
             return fail(c, TFHE_ERR_INVALID, "lut_select: an entry is not a ciphertext of the pool");
     return on_device0(c, [&](Device &d) {
-        return lut_select_on(d, *pk, m, pool, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out, B, dev);
+        return lut_select_on(d, *pk, m, pool, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out, B, dev,
+                             eta);
     });
 }
 
@@ -466,24 +537,6 @@ static int apply2_entry(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe
 
 // ---- Extended LUT bootstrap (include/tfhe_gpu.h): E = 2^eta accumulator components per item, eta = 1 or 2 ----
 
-// The extended blind rotation over device buffers, async: all E accumulators of each item (all) or acc_0.
-static int blind_rotate_ext_launch(Device &d, uint32_t eta, const uint32_t *x, const uint32_t *testvec,
-                                   const uint32_t *tv_sel, uint32_t *acc, bool all, size_t B) {
-    BrExtBatch b;
-    b.eta = eta;
-    b.in = x;
-    b.testvec = testvec;
-    b.tv_sel = tv_sel;
-    b.bk = d.d_bk;
-    b.out = acc;
-    b.all = all;
-    b.B = B;
-    d.last_ks = "";
-    HIPCHK(d, launch_blind_rotate_ext(d.K, tables(d), b, d.stream, &d.last_br));
-    d.bootstraps += B;
-    return TFHE_OK;
-}
-
 static int blind_rotate_ext_entry(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in, const uint32_t *testvecs,
                                   uint32_t *out, size_t B) {
     if (!c || (B && (!in || !testvecs || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
@@ -501,6 +554,34 @@ static int blind_rotate_ext_entry(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t 
         int rc = io.out(out, B * E * TRLWE_BYTES);
         if (rc) return rc;
         if ((rc = blind_rotate_ext_launch(d, eta, in, testvecs, nullptr, out, /*all*/ true, B))) return rc;
+        return io.finish();
+    });
+}
+
+// bootstrap_lut_each with the extended bootstrap: item i's one test vector serves all E components.
+static int each_ext_entry(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in, const uint32_t *testvecs, uint32_t *out,
+                          size_t B, bool dev) {
+    if (eta > TFHE_LUT_EXT_MAX_LOG) return fail(c, TFHE_ERR_INVALID, "bootstrap_lut_each: eta > TFHE_LUT_EXT_MAX_LOG");
+    if (eta == 0) return each_entry(c, in, testvecs, out, B, dev);  // exactly the existing entry
+    if (!c || (B && (!in || !testvecs || !out))) return fail(c, TFHE_ERR_INVALID, "null argument");
+    if (dev && is_multi(c)) return fail(c, TFHE_ERR_INVALID, "device-resident calls take a single-device context");
+    if (B > 0x7FFFFFFFull / 2048) return fail(c, TFHE_ERR_INVALID, "bootstrap_lut_each: too many items");
+    if (B == 0) return TFHE_OK;
+    return on_device0(c, [&](Device &d) -> int {
+        if (!d.has_key) return fail(d, TFHE_ERR_NO_KEY, "no cloud key loaded");
+        const size_t w = tlwe0_words(d.P), TRLWE = 2 * (size_t)d.P.N;
+        DescBlob blob;
+        const size_t iota_at = add_iota(blob, B, LUT_TV_EACH), zero_at = blob.reserve(1);
+        Frame f(d);
+        Io io{f, dev};
+        const uint32_t *desc = blob.upload(f);
+        io.in(in, B * w * 4);
+        io.in(testvecs, B * TRLWE * sizeof(uint32_t));
+        int rc = io.out(out, B * w * 4);
+        uint32_t *acc = f.take<uint32_t>(B * TRLWE), *lv1 = f.ks_input<uint32_t>(B * 1025);
+        if ((rc = f.rc())) return rc;
+        if ((rc = blind_rotate_ext_launch(d, eta, in, nullptr, desc + iota_at, acc, /*all*/ false, B, testvecs))) return rc;
+        if ((rc = ext_extract_ks(d, f, acc, desc + zero_at, lv1, out, B))) return rc;
         return io.finish();
     });
 }
@@ -527,10 +608,7 @@ static int lut_apply_ext_on(Device &d, const tfhe_gpu_lut_set &set, uint32_t eta
     HIPCHK(d, launch_lut_combine(d.K, pool, desc + off_at, desc + src_at, reinterpret_cast<const int32_t *>(desc + coef_at),
                                  desc + konst_at, x, B, d.stream));
     if ((rc = blind_rotate_ext_launch(d, eta, x, set.tables, desc + lut_at, acc, /*all*/ false, B))) return rc;
-    HIPCHK(d, launch_sample_extract(acc, desc + zero_at, 1, lv1, B, d.stream));
-    KsGemm G;
-    if ((rc = ks_gemm_args(f, B, G))) return rc;
-    HIPCHK(d, launch_key_switch(d.K, lv1, d.d_ksk, out, B, d.stream, d.opts, &d.last_ks, &G));
+    if ((rc = ext_extract_ks(d, f, acc, desc + zero_at, lv1, out, B))) return rc;
     return io.finish();
 }
 
@@ -573,6 +651,16 @@ int tfhe_gpu_lut_apply_ext_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, uin
                                size_t P, const uint32_t *term_off, const uint32_t *term_src, const int32_t *term_coef,
                                const uint32_t *konst, const uint32_t *lut, uint32_t *out_dev, size_t B) {
     return apply_ext_entry(c, set, eta, pool_dev, P, term_off, term_src, term_coef, konst, lut, out_dev, B, true);
+}
+
+int tfhe_gpu_bootstrap_lut_each_ext_batch(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in, const uint32_t *testvecs,
+                                          uint32_t *out, size_t B) {
+    return each_ext_entry(c, eta, in, testvecs, out, B, false);
+}
+
+int tfhe_gpu_bootstrap_lut_each_ext_dev(tfhe_gpu_ctx *c, uint32_t eta, const uint32_t *in_dev,
+                                        const uint32_t *testvecs_dev, uint32_t *out_dev, size_t B) {
+    return each_ext_entry(c, eta, in_dev, testvecs_dev, out_dev, B, true);
 }
 
 int tfhe_gpu_lut_spread_batch(tfhe_gpu_ctx *c, const uint32_t *in, uint32_t w, uint32_t rot, uint32_t *out, size_t B) {
@@ -724,6 +812,45 @@ int tfhe_gpu_lut_select_dev(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uin
                             const uint32_t *konst, const uint32_t *sel_src, const uint32_t *sel_konst, uint32_t *out_dev,
                             size_t B) {
     return select_entry(c, pk, m, pool_dev, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out_dev, B, true);
+}
+
+int tfhe_gpu_lut_select_ext_batch(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, uint32_t eta,
+                                  const uint32_t *pool, size_t P, const uint32_t *term_off, const uint32_t *term_src,
+                                  const int32_t *term_coef, const uint32_t *konst, const uint32_t *sel_src,
+                                  const uint32_t *sel_konst, uint32_t *out, size_t B) {
+    return select_entry(c, pk, m, pool, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out, B, false, eta);
+}
+
+int tfhe_gpu_lut_select_ext_dev(tfhe_gpu_ctx *c, const tfhe_gpu_packing_key *pk, uint32_t m, uint32_t eta,
+                                const uint32_t *pool_dev, size_t P, const uint32_t *term_off, const uint32_t *term_src,
+                                const int32_t *term_coef, const uint32_t *konst, const uint32_t *sel_src,
+                                const uint32_t *sel_konst, uint32_t *out_dev, size_t B) {
+    return select_entry(c, pk, m, pool_dev, P, term_off, term_src, term_coef, konst, sel_src, sel_konst, out_dev, B, true,
+                        eta);
+}
+
+// eta == NULL: the _select entry
+int tfhe_gpu_lut_circuit_eval_ext(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk, uint32_t m,
+                                  size_t n_inputs, const uint32_t *inputs, size_t n_nodes, const uint32_t *term_off,
+                                  const uint32_t *term_wire, const int32_t *term_coef, const uint32_t *konst,
+                                  const uint32_t *lut, const uint32_t *theta, const uint32_t *sel_off,
+                                  const uint32_t *sel_wire, const uint32_t *sel_konst, const uint32_t *eta,
+                                  size_t n_outputs, const uint32_t *out_wires, uint32_t *outputs, uint32_t *levels) {
+    const LutSelect sel{m, sel_off, sel_wire, sel_konst};
+    return circuit_entry(c, set, n_inputs, inputs, n_nodes, term_off, term_wire, term_coef, konst, lut, theta, n_outputs,
+                         out_wires, outputs, levels, false, pk, sel_off ? &sel : nullptr, eta);
+}
+
+int tfhe_gpu_lut_circuit_eval_ext_dev(tfhe_gpu_ctx *c, const tfhe_gpu_lut_set *set, const tfhe_gpu_packing_key *pk,
+                                      uint32_t m, size_t n_inputs, const uint32_t *inputs_dev, size_t n_nodes,
+                                      const uint32_t *term_off, const uint32_t *term_wire, const int32_t *term_coef,
+                                      const uint32_t *konst, const uint32_t *lut, const uint32_t *theta,
+                                      const uint32_t *sel_off, const uint32_t *sel_wire, const uint32_t *sel_konst,
+                                      const uint32_t *eta, size_t n_outputs, const uint32_t *out_wires,
+                                      uint32_t *outputs_dev, uint32_t *levels) {
+    const LutSelect sel{m, sel_off, sel_wire, sel_konst};
+    return circuit_entry(c, set, n_inputs, inputs_dev, n_nodes, term_off, term_wire, term_coef, konst, lut, theta,
+                         n_outputs, out_wires, outputs_dev, levels, true, pk, sel_off ? &sel : nullptr, eta);
 }
 
 }  // extern "C"

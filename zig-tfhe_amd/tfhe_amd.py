@@ -273,6 +273,20 @@ _SIGS = {
                                                C.c_size_t]),
     "tfhe_gpu_lut_apply_ext_dev": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_size_t, u32p, u32p, i32p, u32p, u32p, vp,
                                              C.c_size_t]),
+    "tfhe_gpu_bootstrap_lut_each_ext_batch": (C.c_int, [vp, C.c_uint32, u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_bootstrap_lut_each_ext_dev": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_size_t]),
+    "tfhe_gpu_lut_select_ext_batch": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, u32p, C.c_size_t, u32p, u32p, i32p, u32p,
+                                                u32p, u32p, u32p, C.c_size_t]),
+    "tfhe_gpu_lut_select_ext_dev": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, u32p, u32p, i32p, u32p,
+                                              u32p, u32p, vp, C.c_size_t]),
+    "tfhe_gpu_lut_circuit_eval_ext": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, u32p, C.c_size_t, u32p, u32p, i32p,
+                                                u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_size_t, u32p, u32p,
+                                                C.POINTER(C.c_uint32)]),
+    "tfhe_gpu_lut_circuit_eval_ext_dev": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, vp, C.c_size_t, u32p, u32p,
+                                                    i32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, C.c_size_t, u32p,
+                                                    vp, C.POINTER(C.c_uint32)]),
+    "tfhe_lut_circuit_schedule_ext": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, u32p, C.c_uint32, u32p, u32p, u32p,
+                                                u32p, C.POINTER(C.c_uint32), u32p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -1110,6 +1124,76 @@ class Context:
                                                     src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p), vp(out_ptr),
                                                     d.B), "lut_select_dev")
 
+    # ---- extended nodes: an eta per node, select nodes on extended tables (include/tfhe_gpu.h "Extended nodes") ----
+    def bootstrap_lut_each_ext(self, eta: int, cts, testvecs):
+        """tfhe_gpu_bootstrap_lut_each_ext_batch: the extended bootstrap of item i with its one test vector
+        testvecs[i] (any a) in all 2^eta components: cts (B, n+1), testvecs (B, 2N) -> (B, n+1)."""
+        cts, cp = _u32(np.asarray(cts, np.uint32).reshape(-1, self.n1))
+        tv, tvp = _u32(np.asarray(testvecs, np.uint32).reshape(-1, 2 * self.params.N))
+        if tv.shape[0] != cts.shape[0]:
+            raise ValueError(f"bootstrap_lut_each_ext: {cts.shape[0]} ciphertexts need as many test vectors, got {tv.shape[0]}")
+        out = np.zeros_like(cts)
+        self.check(self.lib.tfhe_gpu_bootstrap_lut_each_ext_batch(self.h, eta, cp, tvp, out.ctypes.data_as(u32p),
+                                                                  cts.shape[0]), "bootstrap_lut_each_ext")
+        return out
+
+    def bootstrap_lut_each_ext_dev(self, eta: int, in_ptr, tv_ptr, out_ptr, B):
+        """tfhe_gpu_bootstrap_lut_each_ext_dev: inputs, the B test vectors and outputs in HBM, async."""
+        self.check(self.lib.tfhe_gpu_bootstrap_lut_each_ext_dev(self.h, eta, vp(in_ptr), vp(tv_ptr), vp(out_ptr), B),
+                   "bootstrap_lut_each_ext_dev")
+
+    def lut_select_ext(self, packing_key: "PackingKey", m: int, eta: int, pool, nodes):
+        """tfhe_gpu_lut_select_ext_batch: lut_select with the extended bootstrap, so m may be 32 (eta = 1) or 64
+        (eta = 2) at the UINT4 key's margin; nodes as lut_select takes them.  pool (P, n+1) -> (B, n+1)."""
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        d, src, konst = _select_nodes(nodes, m)
+        out = np.zeros((d.B, self.n1), np.uint32)
+        self.check(self.lib.tfhe_gpu_lut_select_ext_batch(self.h, packing_key.h, m, eta, pp, pool.shape[0],
+                                                          *d.pointers()[:4], src.ctypes.data_as(u32p),
+                                                          konst.ctypes.data_as(u32p), out.ctypes.data_as(u32p), d.B),
+                   "lut_select_ext")
+        return out
+
+    def lut_select_ext_dev(self, packing_key: "PackingKey", m: int, eta: int, pool_ptr, P, nodes, out_ptr):
+        """tfhe_gpu_lut_select_ext_dev: the pool and the B outputs in HBM, async."""
+        d, src, konst = _select_nodes(nodes, m)
+        self.check(self.lib.tfhe_gpu_lut_select_ext_dev(self.h, packing_key.h, m, eta, vp(pool_ptr), P, *d.pointers()[:4],
+                                                        src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p),
+                                                        vp(out_ptr), d.B), "lut_select_ext_dev")
+
+    def lut_circuit_eval_ext(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs, nodes, theta, select,
+                             eta, out_wires):
+        """tfhe_gpu_lut_circuit_eval_ext: lut_circuit_eval_select with eta per node (None: that call); an ordinary
+        node with eta > 0 reads the extended table lut of the set, a select node with eta > 0 runs the extended
+        bootstrap on its packed table -> (outputs, depth)."""
+        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        _, etp = _theta(eta, d.B)
+        sel = _select_arrays(select, d.B)
+        ow, owp = _u32(out_wires)
+        out = np.zeros((ow.size, self.n1), np.uint32)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_ext(
+            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m or 0, inputs.shape[0], ip, d.B,
+            *d.pointers(), thp, *sel[1], etp, ow.size, owp, out.ctypes.data_as(u32p), C.byref(depth)),
+            "lut_circuit_eval_ext")
+        return out, depth.value
+
+    def lut_circuit_eval_ext_dev(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs_ptr, n_inputs, nodes,
+                                 theta, select, eta, out_wires, outputs_ptr):
+        """tfhe_gpu_lut_circuit_eval_ext_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
+        d = pack_lut_nodes(nodes)
+        _, thp = _theta(theta, d.B)
+        _, etp = _theta(eta, d.B)
+        sel = _select_arrays(select, d.B)
+        ow, owp = _u32(out_wires)
+        depth = C.c_uint32(0)
+        self.check(self.lib.tfhe_gpu_lut_circuit_eval_ext_dev(
+            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m or 0, n_inputs, vp(inputs_ptr), d.B,
+            *d.pointers(), thp, *sel[1], etp, ow.size, owp, vp(outputs_ptr), C.byref(depth)), "lut_circuit_eval_ext_dev")
+        return depth.value
+
 
 @dataclass
 class SecretKey:
@@ -1531,6 +1615,7 @@ class LutCircuit:
         self.theta = []  # per node: log2 of its output count
         self.sel = []    # per node: None, or a select node's m entries (a wire or ("const", word) each)
         self.m = None    # the select nodes' m (one per circuit)
+        self.eta = []    # per node: 0, or the extended bootstrap's eta (1 or 2)
         self.n_wires = 0
         self.outputs = []
 
@@ -1541,11 +1626,14 @@ class LutCircuit:
         self.n_wires += 1
         return self.n_inputs - 1
 
-    def node(self, lut: int, terms=(), const: int = 0, outputs: int = 1):
+    def node(self, lut: int, terms=(), const: int = 0, outputs: int = 1, eta: int = 0):
         """-> the node's wire; with outputs = 2, 4 or 8 (a multi-output node: lut is a lut_interleave table, the
-        input is rounded to log2(outputs) fewer bits) the list of its wires, one per interleaved table."""
+        input is rounded to log2(outputs) fewer bits) the list of its wires, one per interleaved table.  eta = 1 or
+        2: the extended bootstrap, lut naming the extended table (lut_generate_ext's 2^eta entries from lut * 2^eta)."""
         if outputs not in (1, 2, 4, 8):
             raise ValueError("a node has 1, 2, 4 or 8 outputs")
+        if eta not in (0, 1, 2) or (eta and outputs != 1):
+            raise ValueError("a node's eta is 0, 1 or 2, and an extended node has one output")
         w = self.n_wires
         terms = [(int(s), int(c)) for s, c in terms]
         if any(not 0 <= s < w for s, _ in terms):
@@ -1553,13 +1641,18 @@ class LutCircuit:
         self.nodes.append((int(lut), terms, int(const)))
         self.theta.append(outputs.bit_length() - 1)
         self.sel.append(None)
+        self.eta.append(eta)
         self.n_wires += outputs
         return w if outputs == 1 else list(range(w, w + outputs))
 
-    def select(self, terms, entries, const: int = 0) -> int:
+    def select(self, terms, entries, const: int = 0, eta: int = 0) -> int:
         """A select node: the digit x = sum coef * wire over terms (+ const) picks one of the m = len(entries)
         entries, each an earlier wire or ("const", word); the table is packed from the entries on the device
-        (tfhe_gpu_lut_circuit_eval_select).  -> the node's wire, which decrypts to what entry number x decrypts to."""
+        (tfhe_gpu_lut_circuit_eval_select).  -> the node's wire, which decrypts to what entry number x decrypts to.
+        eta = 1 or 2: x is read by the extended bootstrap (tfhe_gpu_lut_circuit_eval_ext), which keeps the margin
+        of m = 16 at m = 32 or 64 on the UINT4 key."""
+        if eta not in (0, 1, 2):
+            raise ValueError("a node's eta is 0, 1 or 2")
         entries = list(entries)
         m = len(entries)
         if m < 2 or m & (m - 1) or (self.m is not None and m != self.m):
@@ -1574,27 +1667,30 @@ class LutCircuit:
         self.nodes.append((0, terms, int(const)))
         self.theta.append(0)
         self.sel.append(entries)
+        self.eta.append(eta)
         self.n_wires += 1
         return w
 
-    def node2(self, lut_base: int, x_terms, y_terms, m: int) -> int:
+    def node2(self, lut_base: int, x_terms, y_terms, m: int, eta: int = 0) -> int:
         """A bivariate node f(x, y) over two m-ary digits: m ordinary nodes with the tables lut_base + i
-        (y -> f(i, y), lut_generate2's rows) over y_terms and one select node over x_terms -> its wire."""
+        (y -> f(i, y), lut_generate2's rows) over y_terms and one select node over x_terms -> its wire.  eta is the
+        select node's: x may then be an m-ary digit with m up to 64; the m nodes over y stay ordinary."""
         if self.m is not None and m != self.m:
             raise ValueError(f"node2: the circuit's select nodes have m = {self.m}, got {m}")
-        return self.select(x_terms, [self.node(lut_base + i, y_terms) for i in range(m)])
+        return self.select(x_terms, [self.node(lut_base + i, y_terms) for i in range(m)], eta=eta)
 
-    def lookup(self, digit_terms_list, lut_base: int, m: int) -> int:
+    def lookup(self, digit_terms_list, lut_base: int, m: int, eta: int = 0) -> int:
         """A k-digit lookup over plaintext tables: digit_terms_list holds the terms of the k digits, most
         significant first, and the set the m^(k-1) tables f(i_1, .., i_{k-1}, .) from lut_base in row-major order.
-        m^(k-1) ordinary nodes on the last digit, then nested select nodes for the earlier digits -> the wire."""
+        m^(k-1) ordinary nodes on the last digit, then nested select nodes for the earlier digits -> the wire.
+        eta is the select nodes'; the nodes on the last digit stay ordinary."""
         digits = list(digit_terms_list)
         if not digits:
             raise ValueError("lookup: no digits")
         k = len(digits)
         row = [self.node(lut_base + i, digits[-1]) for i in range(m ** (k - 1))]
         for terms in reversed(digits[:-1]):
-            row = [self.select(terms, row[j * m:(j + 1) * m]) for j in range(len(row) // m)]
+            row = [self.select(terms, row[j * m:(j + 1) * m], eta=eta) for j in range(len(row) // m)]
         return row[0]
 
     @property
@@ -1604,6 +1700,10 @@ class LutCircuit:
     @property
     def has_select(self) -> bool:
         return any(e is not None for e in self.sel)
+
+    @property
+    def has_ext(self) -> bool:
+        return any(self.eta)
 
     def select_arrays(self):
         """(sel_off, sel_wire, sel_konst) of tfhe_gpu_lut_circuit_eval_select, or None without select nodes."""
@@ -1650,6 +1750,8 @@ class LutCircuit:
         d = self.packed()
         levels = np.zeros(max(d.B, 1), np.uint32)
         depth = C.c_uint32(0)
+        if self.has_ext:
+            return self.schedule_ext()[:2]
         if self.has_select:
             sel, selp = _select_arrays(self.select_arrays(), d.B)
             rc = lib.tfhe_lut_circuit_schedule_select(self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p),
@@ -1666,6 +1768,22 @@ class LutCircuit:
             raise TfheError(f"lut_circuit_schedule: status {rc}", rc)
         return levels[:d.B], depth.value
 
+    def schedule_ext(self):
+        """tfhe_lut_circuit_schedule_ext (host only) -> (levels, depth, groups): groups[lv - 1, e] is the number of
+        level lv's nodes with eta = e, the items of that level's launch for e."""
+        d = self.packed()
+        levels = np.zeros(max(d.B, 1), np.uint32)
+        groups = np.zeros(3 * max(d.B, 1), np.uint32)
+        depth = C.c_uint32(0)
+        sel, selp = _select_arrays(self.select_arrays(), d.B)
+        rc = load_library().tfhe_lut_circuit_schedule_ext(
+            self.n_inputs, d.B, d.term_off.ctypes.data_as(u32p), d.src.ctypes.data_as(u32p), _theta(self.theta, d.B)[1],
+            self.m or 0, selp[0], selp[1], _theta(self.eta, d.B)[1], levels.ctypes.data_as(u32p), C.byref(depth),
+            groups.ctypes.data_as(u32p))
+        if rc:
+            raise TfheError(f"lut_circuit_schedule_ext: status {rc}", rc)
+        return levels[:d.B], depth.value, groups[:3 * depth.value].reshape(-1, 3)
+
     def _select_m(self, packing_key, m):
         if packing_key is None:
             raise ValueError("a circuit with select nodes needs a packing_key")
@@ -1678,6 +1796,10 @@ class LutCircuit:
         inputs = np.asarray(inputs, np.uint32).reshape(-1, ctx.params.n + 1)
         if inputs.shape[0] != self.n_inputs:
             raise ValueError(f"circuit has {self.n_inputs} inputs, got {inputs.shape[0]}")
+        if self.has_ext:
+            m = self._select_m(packing_key, m) if self.has_select else 0
+            return ctx.lut_circuit_eval_ext(lut_set, packing_key, m, inputs, self.packed(), self.theta,
+                                            self.select_arrays(), self.eta, np.array(self.outputs, np.uint32))
         if self.has_select:
             m = self._select_m(packing_key, m)
             return ctx.lut_circuit_eval_select(lut_set, packing_key, m, inputs,
@@ -1691,6 +1813,11 @@ class LutCircuit:
     def run_dev(self, ctx: "Context", lut_set: LutSet, inputs_ptr, outputs_ptr, packing_key: "PackingKey" = None,
                 m: int = None):
         """Inputs (n_inputs TLWELv0) and outputs in HBM; returns the bootstrap depth."""
+        if self.has_ext:
+            m = self._select_m(packing_key, m) if self.has_select else 0
+            return ctx.lut_circuit_eval_ext_dev(lut_set, packing_key, m, inputs_ptr, self.n_inputs, self.packed(),
+                                                self.theta, self.select_arrays(), self.eta,
+                                                np.array(self.outputs, np.uint32), outputs_ptr)
         if self.has_select:
             m = self._select_m(packing_key, m)
             return ctx.lut_circuit_eval_select_dev(lut_set, packing_key, m, inputs_ptr,
