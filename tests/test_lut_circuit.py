@@ -174,14 +174,16 @@ def test_tail_split_shifts_the_selectors(oracle):
 
 def test_recompute_reads_the_items_table(oracle):
     """The margin guard's recompute launch carries the selector: under the crafted near-tie key
-    (conftest.crafted_near_tie_case, zero KSK) and a set {random table, crafted test vector}, the
+    (conftest.crafted_near_tie_case) and a set {random table, crafted test vector}, the
     crafted ciphertext selects table 1 and the others table 0.  Forced fused arithmetic flags the
     crafted item, the reference-tree recompute redoes it (near_tie_items rises), and every output is
-    the oracle's reference-mode words for its own table."""
+    the oracle's reference-mode words for its own table.  The KSK is the seeded key's: the fused
+    arithmetic parts from the reference in accumulator words other than a[0] and b[0] only
+    (tests/test_margin_guard_cpu.py), and a zero KSK's key switch returns (0, ..., 0, b[0])."""
     from oracle import CloudKeyArrays
     p = get_keys(oracle, "128").p
     tv, bk, ct = crafted_near_tie_case(oracle, p)
-    ksk = np.zeros((p.N * p.iks_t * (1 << p.basebit), p.n + 1), np.uint32)
+    ksk = get_keys(oracle, "128").ck.ksk
     off = oracle.decomposition_offset(p)
     g = rng(1304)
     u32 = lambda *shape: g.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
@@ -198,10 +200,10 @@ def test_recompute_reads_the_items_table(oracle):
             with c.options(br_form=form, arith=tfhe_amd.ARITH_FUSED_FORCED):
                 got = c.lut_apply(ls, cts, nodes)
                 assert c.last_kernels().split(" + ")[0].endswith("fused)")
-            assert c.near_tie_items() > before, form
-            before = c.near_tie_items()
             bad = np.flatnonzero((got != want).any(axis=1))
             assert bad.size == 0, (form, bad.tolist())
+            assert c.near_tie_items() > before, form
+            before = c.near_tie_items()
         ls.close()
     finally:
         c.close()
