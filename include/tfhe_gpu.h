@@ -74,7 +74,21 @@ enum {
     TFHE_GATE_COPY = 255       /* no pre-combination: bootstrap input a as is */
 };
 
-/* Runtime form of params.zig SecurityParams (:36-67).  N must be 1024. */
+/* Runtime form of params.zig SecurityParams (:36-67).  N must be 1024.
+ * The parameter check (every tfhe_gpu_create*, and the host-only calls that take params): N = 1024,
+ * nbit = 10, n in [1, 1024], L in {1, 2, 3}, bgbit in [1, 31] with L * bgbit <= 32, and a key switch
+ * of basebit 2 with 7..9 levels or basebit 3..8 with 2..4 levels, basebit * iks_t < 31.  Anything
+ * else: TFHE_ERR_INVALID, the reason in tfhe_gpu_last_error(NULL) after a create.
+ *  - bgbit = 32 (L = 1) is refused: Bg = 2^32 does not fit the 32-bit words the decomposition offset
+ *    and the digit mask are computed in (1u << 32 is undefined), and the device's bit-field extract
+ *    reads a width of 32 as 0.
+ *  - L = 1 with bgbit 29..31 is accepted, but the values the external product rounds (typically around
+ *    2^(34 + bgbit) under a generated key; at most 2 N Bg/2 2^31) reach 2^63 there, beyond the i64
+ *    range of the reference's @intFromFloat: the reference's result is undefined at such values and
+ *    this library reproduces the x86-64 behaviour (low word 0; torus_from_f64, tfhe_device.hpp), so
+ *    parity with the reference is platform-defined in that region.
+ *  - L = 3 with bgbit 9 or 10 (4 * bgbit > 32) has no whole-form blind rotation: every batch runs the
+ *    latency form, and TFHE_OPT_BR_FORM 1 is refused. */
 typedef struct {
     uint32_t n;        /* TLWE lv0 dimension (tlwe_lv0.n)   */
     uint32_t N;        /* polynomial size (trgsw_lv1.n)     */
@@ -176,7 +190,8 @@ int tfhe_gpu_near_tie_items(const tfhe_gpu_ctx *ctx, uint64_t *count);
  * fastest forms).  Set on a context before use; a multi-device context
  * passes them to every device.  TFHE_ERR_INVALID for an unknown key or value. */
 enum {
-    TFHE_OPT_BR_FORM = 1,         /* blind rotation: 0 auto (default), 1 whole, 3 latency, 5 octo (8 items
+    TFHE_OPT_BR_FORM = 1,         /* blind rotation: 0 auto (default), 1 whole (refused at L = 3 with
+                                     4 * bgbit > 32, where it does not exist), 3 latency, 5 octo (8 items
                                      per workgroup, two gate waves per SIMD; L = 1 only).  2 split and 4
                                      pair were removed in round 4; 6 duo, 7 the split-transform latency
                                      form, 8 round 4's whole form and 9-40 development copies of the L = 3
@@ -192,7 +207,10 @@ enum {
     TFHE_OPT_KS_ITEM_GROUPS = 5,  /* basebit >= 5: 0 auto (above 64 items the ring form: 4 item groups
                                      share a 4-deep DMA ring), 1, 2, 4, 8 forces the lane form with
                                      that many item groups per block */
-    TFHE_OPT_KS_SEL_ITEMS = 6,    /* select / gather form: items per block, 8 (default), 16, 32 */
+    TFHE_OPT_KS_SEL_ITEMS = 6,    /* select / gather form: items per block, 8 (default), 16, 32; any other
+                                     value is refused (TFHE_ERR_INVALID) and the option keeps its value.
+                                     tfhe_gpu_last_kernels names k_key_switch_sel / _gather at 8 and
+                                     k_key_switch_sel<t,16>, <t,32> (_gather alike) at the others */
     TFHE_OPT_CIRCUIT_PACK = 7,    /* circuit_eval round packing: 1 (default), 0 off */
     TFHE_OPT_TWIDDLES = 8,        /* cos/sin source of the FFT tables: TFHE_TWIDDLES_* (set before a key
                                      is generated: keygen transforms the key with these tables) */
@@ -994,6 +1012,9 @@ int tfhe_lookup_table_pack_bits(const tfhe_params *params, const uint64_t *value
  * words (tfhe_packed_lookup_plan), trivial TRLWELv1 (a = 0), +-1/8 per bit as above, unused coefficients 0. */
 int tfhe_lookup_table_pack_slots(const tfhe_params *params, const uint64_t *values /*2^k*/, uint32_t k, uint32_t width,
                                  uint32_t *table /*trlwes*2N*/);
+/* genDecompositionOffset (key.zig:121-131): sum over l < L of Bg/2 * 2^(32 - (l+1) bgbit), the
+ * CloudKey.decomposition_offset that tfhe_gpu_load_cloud_key takes. */
+int tfhe_decomposition_offset(const tfhe_params *params, uint32_t *offset);
 /* SecretKey.new (key.zig:41-57) from DefaultPrng(seed): n lv0 bits, then N lv1 bits. */
 int tfhe_secret_key_new(const tfhe_params *params, uint64_t seed, uint32_t *key_lv0, uint32_t *key_lv1);
 /* TLWELv0.encryptBool (tlwe.zig:52-55 -> encryptF64 :34-49); item i uses

@@ -19,7 +19,10 @@ bool params_ok(const tfhe_params *p, std::string &why) {
     if (p->N != 1024 || p->nbit != 10) { why = "only N=1024 (nbit=10) is supported"; return false; }
     if (p->n == 0 || p->n > 1024) { why = "n must be in [1, 1024]"; return false; }
     if (p->L < 1 || p->L > 3) { why = "L must be 1, 2 or 3"; return false; }
-    if (p->bgbit < 1 || p->bgbit * p->L > 32) { why = "bgbit*L must be <= 32"; return false; }
+    // bgbit = 32 (L = 1) is no gadget this code can hold: Bg = 2^32 does not fit the 32-bit words the
+    // offset, the digit mask and the device's bit-field extracts (width 32 reads as 0) work in
+    if (p->bgbit < 1 || p->bgbit > 31) { why = "bgbit must be in [1, 31] (Bg = 2^bgbit must fit a 32-bit word)"; return false; }
+    if (p->bgbit * p->L > 32) { why = "bgbit*L must be <= 32"; return false; }
     // the select form takes basebit 2 with t in [7, 9] (128/80-bit), the gather form
     // basebit 3..8 with t in [2, 4] (Uint sets); the shapes with faster forms are
     // listed once, in KS_SHAPES (tfhe_kernels.hip)
@@ -744,6 +747,13 @@ int tfhe_cloud_key_read(const char *path, const tfhe_params *p, uint32_t *offset
     if (rc) return rc;
     if (key_checksum(p, tv_a, tv_b, bsk, bsk_len, ksk, ksk_len) != h.checksum) return TFHE_ERR_INVALID;
     *offset = h.offset;
+    return TFHE_OK;
+}
+
+int tfhe_decomposition_offset(const tfhe_params *p, uint32_t *offset) {
+    std::string why;
+    if (!params_ok(p, why) || !offset) return TFHE_ERR_INVALID;
+    *offset = decomposition_offset(*p);
     return TFHE_OK;
 }
 

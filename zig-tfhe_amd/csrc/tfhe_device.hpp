@@ -983,7 +983,10 @@ DEV void load_digits_pair0_regs(C2 (*d)[8], const uint32_t *tA, const uint32_t *
 
 // Digits of rows (2rp, 2rp+1), rp = 1, 2 at L = 3, from packed tmp words kept in
 // registers (round 4): tbx[m] = tmp_b's word m with tmp_a's level-2 field moved
-// into its unused low bits (tmp_b's fields sit at bits >= 32 - 3 bgbit > bgbit).
+// into its unused low bits.  tmp_b's fields sit at bits >= 32 - 3 bgbit, so the low bgbit
+// bits are unused only while 4 bgbit <= 32: the whole form is launched at no other L = 3
+// gadget (whole_form_packs, tfhe_internal.hpp; launch_blind_rotate runs the latency form at
+// (3, 9) and (3, 10)).
 // Row 2 (a, level 2) reads bits [0, bgbit), rows 3-5 (b, levels 0-2) their own
 // fields: one v_bfe_i32 per digit as before, and no tmp round trip through LDS
 // (32 ds_write_b32 + 48 ds_read_b32 per step fewer; 6.25-6.32 -> 6.12-6.18 ms,

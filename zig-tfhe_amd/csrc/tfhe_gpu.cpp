@@ -1063,8 +1063,11 @@ static bool option_ok(const Device &d, int key, int64_t v, std::string &why) {
         // 2 split, 4 pair: removed in round 4; 6 duo, 7 split-transform latency
         // form, 8 the whole form without loader assist, 30 the latency form with row
         // counters: A/B libraries only (tools/ab/); 5 octo: L = 1 only
-        ok = v == 0 || v == 1 || v == 3 || (v == 5 && d.P.L == 1) ||
+        ok = v == 0 || (v == 1 && whole_form_packs((int)d.P.L, (int)d.P.bgbit)) || v == 3 || (v == 5 && d.P.L == 1) ||
              ((v == 6 || v == 7 || v == 8 || v == 30) && ab_forms_linked());
+        if (!ok && v == 1)
+            why = "TFHE_OPT_BR_FORM 1 (whole form) does not exist at L = 3 with 4*bgbit > 32: its packed tmp words "
+                  "need bgbit <= 8; the latency form runs there";
         if (!ok && v == 5) why = "TFHE_OPT_BR_FORM 5 (octo form) exists at L = 1 only";
         if (!ok && v >= 6 && v <= 8) why = "TFHE_OPT_BR_FORM " + std::to_string(v) + ": an A/B-only form, not in the product library (tools/ab/)";
         break;

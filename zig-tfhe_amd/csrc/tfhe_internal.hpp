@@ -123,6 +123,13 @@ inline bool fused_allowed(const LaunchOpts &O) {
     return O.arith_strict == 2 || (O.arith_strict == 0 && O.key_fused_ok != 0);
 }
 
+// The whole form exists for this gadget.  At L = 3 its gate waves keep tmp_a's level-2 field
+// in the low bgbit bits of tmp_b's word (load_digits_pair_tbx, tfhe_device.hpp), which are
+// free only while tmp_b's own lowest field starts at or above them: 32 - 3 bgbit >= bgbit.
+// (3, 9) and (3, 10) run the latency form for every batch (launch_blind_rotate), and
+// TFHE_OPT_BR_FORM 1 is refused there (option_ok).
+inline bool whole_form_packs(int L, int bgbit) { return L != 3 || 4 * bgbit <= 32; }
+
 // An A/B build (any -D define that changes the kernels or their timing:
 // tools/ab_forms.sh, tools/libvar_build.sh, tools/phase_prof.hip, a Makefile
 // EXTRA) compiles every unit with TFHE_AB_BUILD; tfhe_gpu_create refuses such a

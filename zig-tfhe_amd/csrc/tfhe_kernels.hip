@@ -1451,6 +1451,7 @@ static hipError_t launch_br_form(const KParams &P, const DevTables &T, const BrB
     const bool small = small_products(P), fused = small && fused_allowed(O);
     if (form == 'a')
         return ab_launch_blind_rotate ? ab_launch_blind_rotate(O.br_form, P, T, b, s, fused, used) : hipErrorInvalidValue;
+    if (form == 'w' && !whole_form_packs(P.L, P.bgbit)) return hipErrorInvalidValue;  // launch_blind_rotate never asks
     return launch_br(br_kernel(form, P.L, small, fused, P.tv_sel != nullptr), br_geometry(form, b.B), P, T, b, s, used);
 }
 
@@ -1554,7 +1555,12 @@ hipError_t launch_blind_rotate(const KParams &P, const DevTables &T, const BrBat
     const bool fused = small_products(P) && fused_allowed(O);
     if (!fused) Q.tie_flags = nullptr;
     hipError_t e;
-    if (O.br_form) {  // forced form (TFHE_OPT_BR_FORM): the whole batch in one launch
+    if (!whole_form_packs(P.L, P.bgbit) && O.br_form <= 1) {
+        // L = 3 with 4 bgbit > 32 has no whole form (whole_form_packs): the latency form for every
+        // batch size, correct and slower above BR_WIDE_MAX_ITEMS.  Never fused (small_products
+        // ends at bgbit 6), so no recompute follows.
+        e = launch_br_form(Q, T, b, s, 'W', O, used);
+    } else if (O.br_form) {  // forced form (TFHE_OPT_BR_FORM): the whole batch in one launch
         const char f = O.br_form == 3 ? 'W' : O.br_form == 5 ? 'o' : O.br_form >= 6 ? 'a' : 'w';  // 6-8, 30: A/B forms
         if (f == 'a' && Q.tv_sel) return hipErrorInvalidValue;  // the A/B forms read one test vector per launch
         e = launch_br_form(Q, T, b, s, f, O, used);
@@ -1658,6 +1664,14 @@ static const char *ks_name() {
         r.back() = '>';
         return K == KK_GEMM ? r + " + k_ks_gemm_reduce" : r;  // the packing path's epilogue names itself
     }();
+    return name.c_str();
+}
+
+// k_key_switch_sel<T,G> / k_key_switch_gather<T,G>
+template <bool SEL, int T, int G>
+static const char *ks_sel_name() {
+    static const std::string name = std::string(SEL ? "k_key_switch_sel<" : "k_key_switch_gather<") + std::to_string(T) +
+                                    "," + std::to_string(G) + ">";
     return name.c_str();
 }
 
@@ -1817,24 +1831,26 @@ hipError_t launch_key_switch(const KParams &P, const uint32_t *lv1, const uint32
         return launch_ks_gemm(P, P.iks_t, P.basebit, 1024, 1025, lv1, *KG, out, B, s, used);
     if (O.ks_form != 1 && launch_ks_lanes(P, P.iks_t, P.basebit, lv1, 1024, 1025, ksk, out, B, s, O, used))
         return hipGetLastError();
-    // items per block: TFHE_OPT_KS_SEL_ITEMS in {8, 16, 32} (default 8)
-    if (used) *used = P.basebit == 2 ? "k_key_switch_sel" : "k_key_switch_gather";
+    // items per block: TFHE_OPT_KS_SEL_ITEMS in {8, 16, 32} (default 8; tfhe_gpu_set_option refuses
+    // any other value)
+    const bool sel = P.basebit == 2;
+    if (used) *used = sel ? "k_key_switch_sel" : "k_key_switch_gather";
     auto with_items = [&](auto f) {
         if (O.ks_sel_items == 16) f(std::integral_constant<int, 16>());
         else if (O.ks_sel_items == 32) f(std::integral_constant<int, 32>());
         else f(std::integral_constant<int, 8>());
     };
-    auto launch = [&](auto kernel, int G) {
+    auto launch = [&](auto kernel, const char *name, int G) {
         dim3 grid((unsigned)((P.n + 1 + 255) / 256), (unsigned)((B + G - 1) / G)), block(256);
         hipLaunchKernelGGL(kernel, grid, block, 0, s, P, lv1, ksk, out, B);
+        if (used && G != 8) *used = name;  // the default keeps its bare name; 16 and 32 name their instantiation
     };
     const bool found =
-        P.basebit == 2
-            ? ks_with_shape<KS_SEL>(P.iks_t, 2, [&](auto T, auto) {
-                  with_items([&](auto G) { launch(k_key_switch_sel<T(), G()>, G()); });
+        sel ? ks_with_shape<KS_SEL>(P.iks_t, 2, [&](auto T, auto) {
+                  with_items([&](auto G) { launch(k_key_switch_sel<T(), G()>, ks_sel_name<true, T(), G()>(), G()); });
               })
             : ks_with_shape<KS_GATHER>(P.iks_t, KS_ANY_BASEBIT, [&](auto T, auto) {
-                  with_items([&](auto G) { launch(k_key_switch_gather<T(), G()>, G()); });
+                  with_items([&](auto G) { launch(k_key_switch_gather<T(), G()>, ks_sel_name<false, T(), G()>(), G()); });
               });
     return found ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -176,6 +176,7 @@ _SIGS = {
     "tfhe_lut_generate": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, u32p, u32p]),
     "tfhe_lut_generate_scaled": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, C.c_double, u32p, u32p]),
     "tfhe_lut_generate_full": (C.c_int, [C.POINTER(TfheParams), C.c_uint32, u32p, u32p]),
+    "tfhe_decomposition_offset": (C.c_int, [C.POINTER(TfheParams), u32p]),
     "tfhe_secret_key_new": (C.c_int, [C.POINTER(TfheParams), C.c_uint64, u32p, u32p]),
     "tfhe_gpu_reenc_key_load": (C.c_int, [vp, u32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "tfhe_gpu_reenc_key_destroy": (None, [vp]),
@@ -1242,6 +1243,15 @@ class SecretKey:
         if rc:
             raise TfheError(f"decrypt_lwe_message: {rc}")
         return out
+
+
+def decomposition_offset(params: TfheParams) -> int:
+    """genDecompositionOffset (key.zig:121-131) of a parameter set (tfhe_decomposition_offset)."""
+    v = C.c_uint32()
+    rc = load_library().tfhe_decomposition_offset(C.byref(params), C.byref(v))
+    if rc:
+        raise TfheError(f"decomposition_offset: {rc}")
+    return v.value
 
 
 def secret_key_new(params: TfheParams, seed: int) -> SecretKey:
