@@ -326,6 +326,9 @@ def _f64(a):
     return a, a.ctypes.data_as(f64p)
 
 
+_ABSENT = object()  # an argument the C entry does not take (None is one it takes as NULL)
+
+
 def build_id() -> str:
     """tfhe_gpu_build_id: hash of the gfx950 kernels object the loaded library carries."""
     return load_library().tfhe_gpu_build_id().decode()
@@ -913,23 +916,65 @@ class Context:
         return self.pack_tlwe(key, x.reshape(plan.trlwes, slots * width, self.n1), coef)
 
     # ---- LUT circuits: linear combination, then bootstrap with the node's own table ----
+    def _lut_batch(self, what, head, pool, nodes, theta=_ABSENT, m=None, dev=None):
+        """The flat node batches, tfhe_gpu_<what>_batch(h, *head, pool, P, <nodes>, out, B): the nodes are lut_apply's
+        with theta behind them where the entry takes one, or with m lut_select's.  pool (P, n+1) -> (outputs, n+1);
+        with dev = (P, out_ptr) tfhe_gpu_<what>_dev on the pool pointer, nothing returned."""
+        if m is None:
+            d = pack_lut_nodes(nodes)
+            desc = d.pointers()
+        else:
+            d, src, konst = _select_nodes(nodes, m)
+            desc = (*d.pointers()[:4], src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p))
+        n_out = d.B
+        if theta is not _ABSENT:
+            th, thp = _theta(theta, d.B)
+            desc += (thp,)
+            n_out = d.B if th is None else int((1 << th.astype(np.uint64)).sum())
+        if dev:
+            self.check(getattr(self.lib, f"tfhe_gpu_{what}_dev")(self.h, *head, vp(pool), dev[0], *desc, vp(dev[1]), d.B),
+                       what + "_dev")
+            return None
+        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
+        out = np.zeros((n_out, self.n1), np.uint32)
+        self.check(getattr(self.lib, f"tfhe_gpu_{what}_batch")(self.h, *head, pp, pool.shape[0], *desc,
+                                                                out.ctypes.data_as(u32p), d.B), what)
+        return out
+
+    def _lut_circuit(self, what, lut_set, inputs, nodes, out_wires, key=(), theta=_ABSENT, select=_ABSENT, eta=_ABSENT,
+                     dev=None):
+        """The lut_circuit_eval family, tfhe_gpu_<what>: key = (packing_key, m) and theta, select, eta where the entry
+        takes them.  inputs (n_inputs, n+1) -> (outputs, depth); with dev = (n_inputs, outputs_ptr) tfhe_gpu_<what>_dev
+        on the inputs pointer -> depth."""
+        d = pack_lut_nodes(nodes)
+        more = [] if theta is _ABSENT else [_theta(theta, d.B)[1]]
+        if select is not _ABSENT:
+            more += _select_arrays(select, d.B)[1]
+        if eta is not _ABSENT:
+            more.append(_theta(eta, d.B)[1])
+        head = [self.h, lut_set.h] + ([key[0].h if key[0] is not None else None, key[1]] if key else [])
+        ow, owp = _u32(out_wires)
+        depth = C.c_uint32(0)
+        if dev:
+            self.check(getattr(self.lib, f"tfhe_gpu_{what}_dev")(*head, dev[0], vp(inputs), d.B, *d.pointers(), *more,
+                                                                  ow.size, owp, vp(dev[1]), C.byref(depth)), what + "_dev")
+            return depth.value
+        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
+        out = np.zeros((ow.size, self.n1), np.uint32)
+        self.check(getattr(self.lib, f"tfhe_gpu_{what}")(*head, inputs.shape[0], ip, d.B, *d.pointers(), *more, ow.size,
+                                                          owp, out.ctypes.data_as(u32p), C.byref(depth)), what)
+        return out, depth.value
+
     def lut_apply(self, lut_set: "LutSet", pool, nodes):
         """tfhe_gpu_lut_apply_batch: node i = (lut, terms[, const]) computes x = sum coef * pool[src] over its
         terms [(src, coef), ...] plus const on the b word (wrapping u32), then bootstraps x with lut_set[lut].
         pool (P, n+1) -> (B, n+1)."""
-        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        out = np.zeros((d.B, self.n1), np.uint32)
-        self.check(self.lib.tfhe_gpu_lut_apply_batch(self.h, lut_set.h, pp, pool.shape[0], *d.pointers(),
-                                                     out.ctypes.data_as(u32p), d.B), "lut_apply")
-        return out
+        return self._lut_batch("lut_apply", (lut_set.h,), pool, nodes)
 
     def lut_apply_dev(self, lut_set: "LutSet", pool_ptr, P, nodes, out_ptr):
         """tfhe_gpu_lut_apply_dev: the pool (P TLWELv0) and the B outputs in HBM (the nodes stay a host
         description), async on the context stream."""
-        d = pack_lut_nodes(nodes)
-        self.check(self.lib.tfhe_gpu_lut_apply_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), vp(out_ptr), d.B),
-                   "lut_apply_dev")
+        self._lut_batch("lut_apply", (lut_set.h,), pool_ptr, nodes, dev=(P, out_ptr))
 
     def blind_rotate_ext(self, eta: int, cts, testvecs):
         """tfhe_gpu_blind_rotate_ext_batch (stage entry): the extended blind rotation of (B, n+1) TLWELv0 under one
@@ -945,37 +990,21 @@ class Context:
     def lut_apply_ext(self, lut_set: "LutSet", eta: int, pool, nodes):
         """tfhe_gpu_lut_apply_ext_batch: lut_apply with the extended bootstrap; node i's lut names the extended table
         lut_set[lut * E .. lut * E + E - 1], E = 2^eta (lut_generate_ext).  eta = 0 is lut_apply."""
-        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        out = np.zeros((d.B, self.n1), np.uint32)
-        self.check(self.lib.tfhe_gpu_lut_apply_ext_batch(self.h, lut_set.h, eta, pp, pool.shape[0], *d.pointers(),
-                                                         out.ctypes.data_as(u32p), d.B), "lut_apply_ext")
-        return out
+        return self._lut_batch("lut_apply_ext", (lut_set.h, eta), pool, nodes)
 
     def lut_apply_ext_dev(self, lut_set: "LutSet", eta: int, pool_ptr, P, nodes, out_ptr):
         """tfhe_gpu_lut_apply_ext_dev: the pool and the B outputs in HBM, async on the context stream."""
-        d = pack_lut_nodes(nodes)
-        self.check(self.lib.tfhe_gpu_lut_apply_ext_dev(self.h, lut_set.h, eta, vp(pool_ptr), P, *d.pointers(),
-                                                       vp(out_ptr), d.B), "lut_apply_ext_dev")
+        self._lut_batch("lut_apply_ext", (lut_set.h, eta), pool_ptr, nodes, dev=(P, out_ptr))
 
     def lut_apply_multi(self, lut_set: "LutSet", pool, nodes, theta=None):
         """tfhe_gpu_lut_apply_multi_batch: lut_apply with theta[i] per node (None: all 0); node i gives the 2^theta[i]
         outputs of its interleaved table lut_set[lut] (lut_interleave) from one blind rotation of the rounded x.
         pool (P, n+1) -> (sum 2^theta, n+1), node-major."""
-        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        th, thp = _theta(theta, d.B)
-        out = np.zeros((d.B if th is None else int((1 << th.astype(np.uint64)).sum()), self.n1), np.uint32)
-        self.check(self.lib.tfhe_gpu_lut_apply_multi_batch(self.h, lut_set.h, pp, pool.shape[0], *d.pointers(), thp,
-                                                           out.ctypes.data_as(u32p), d.B), "lut_apply_multi")
-        return out
+        return self._lut_batch("lut_apply_multi", (lut_set.h,), pool, nodes, theta=theta)
 
     def lut_apply_multi_dev(self, lut_set: "LutSet", pool_ptr, P, nodes, theta, out_ptr):
         """tfhe_gpu_lut_apply_multi_dev: the pool and the sum 2^theta outputs in HBM, async on the context stream."""
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        self.check(self.lib.tfhe_gpu_lut_apply_multi_dev(self.h, lut_set.h, vp(pool_ptr), P, *d.pointers(), thp,
-                                                         vp(out_ptr), d.B), "lut_apply_multi_dev")
+        self._lut_batch("lut_apply_multi", (lut_set.h,), pool_ptr, nodes, theta=theta, dev=(P, out_ptr))
 
     # ---- bivariate LUT bootstrap: spread, a test vector per item, the fused node ----
     def lut_spread(self, trlwes, w: int, rot: int):
@@ -1031,48 +1060,20 @@ class Context:
 
     def lut_circuit_eval_multi(self, lut_set: "LutSet", inputs, nodes, theta, out_wires):
         """tfhe_gpu_lut_circuit_eval_multi: node g drives 2^theta[g] consecutive wires -> (outputs, depth)."""
-        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        ow, owp = _u32(out_wires)
-        out = np.zeros((ow.size, self.n1), np.uint32)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_multi(self.h, lut_set.h, inputs.shape[0], ip, d.B, *d.pointers(),
-                                                            thp, ow.size, owp, out.ctypes.data_as(u32p),
-                                                            C.byref(depth)), "lut_circuit_eval_multi")
-        return out, depth.value
+        return self._lut_circuit("lut_circuit_eval_multi", lut_set, inputs, nodes, out_wires, theta=theta)
 
     def lut_circuit_eval_multi_dev(self, lut_set: "LutSet", inputs_ptr, n_inputs, nodes, theta, out_wires, outputs_ptr):
         """tfhe_gpu_lut_circuit_eval_multi_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        ow, owp = _u32(out_wires)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_multi_dev(self.h, lut_set.h, n_inputs, vp(inputs_ptr), d.B,
-                                                                *d.pointers(), thp, ow.size, owp, vp(outputs_ptr),
-                                                                C.byref(depth)), "lut_circuit_eval_multi_dev")
-        return depth.value
+        return self._lut_circuit("lut_circuit_eval_multi", lut_set, inputs_ptr, nodes, out_wires, theta=theta,
+                                 dev=(n_inputs, outputs_ptr))
 
     def lut_circuit_eval(self, lut_set: "LutSet", inputs, nodes, out_wires):
         """tfhe_gpu_lut_circuit_eval: nodes as in lut_apply with wires for sources -> (outputs, depth)."""
-        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        ow, owp = _u32(out_wires)
-        out = np.zeros((ow.size, self.n1), np.uint32)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval(self.h, lut_set.h, inputs.shape[0], ip, d.B, *d.pointers(), ow.size,
-                                                      owp, out.ctypes.data_as(u32p), C.byref(depth)), "lut_circuit_eval")
-        return out, depth.value
+        return self._lut_circuit("lut_circuit_eval", lut_set, inputs, nodes, out_wires)
 
     def lut_circuit_eval_dev(self, lut_set: "LutSet", inputs_ptr, n_inputs, nodes, out_wires, outputs_ptr):
         """tfhe_gpu_lut_circuit_eval_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
-        d = pack_lut_nodes(nodes)
-        ow, owp = _u32(out_wires)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_dev(self.h, lut_set.h, n_inputs, vp(inputs_ptr), d.B, *d.pointers(),
-                                                          ow.size, owp, vp(outputs_ptr), C.byref(depth)),
-                   "lut_circuit_eval_dev")
-        return depth.value
+        return self._lut_circuit("lut_circuit_eval", lut_set, inputs_ptr, nodes, out_wires, dev=(n_inputs, outputs_ptr))
 
     # ---- select nodes: a node whose table is made of wires (include/tfhe_gpu.h "Select nodes") ----
     def lut_circuit_eval_select(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs, nodes, theta,
@@ -1080,50 +1081,24 @@ class Context:
         """tfhe_gpu_lut_circuit_eval_select: select = (sel_off, sel_wire, sel_konst), node g being a select node
         over its m entries sel_wire[sel_off[g] : sel_off[g+1]] (LUT_ENTRY_CONST: the constant sel_konst[j]), or
         None for lut_circuit_eval_multi -> (outputs, depth)."""
-        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        sel = _select_arrays(select, d.B)
-        ow, owp = _u32(out_wires)
-        out = np.zeros((ow.size, self.n1), np.uint32)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_select(
-            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m, inputs.shape[0], ip, d.B,
-            *d.pointers(), thp, *sel[1], ow.size, owp, out.ctypes.data_as(u32p), C.byref(depth)),
-            "lut_circuit_eval_select")
-        return out, depth.value
+        return self._lut_circuit("lut_circuit_eval_select", lut_set, inputs, nodes, out_wires, key=(packing_key, m),
+                                 theta=theta, select=select)
 
     def lut_circuit_eval_select_dev(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs_ptr, n_inputs,
                                     nodes, theta, select, out_wires, outputs_ptr):
         """tfhe_gpu_lut_circuit_eval_select_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        sel = _select_arrays(select, d.B)
-        ow, owp = _u32(out_wires)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_select_dev(
-            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m, n_inputs, vp(inputs_ptr), d.B,
-            *d.pointers(), thp, *sel[1], ow.size, owp, vp(outputs_ptr), C.byref(depth)), "lut_circuit_eval_select_dev")
-        return depth.value
+        return self._lut_circuit("lut_circuit_eval_select", lut_set, inputs_ptr, nodes, out_wires, key=(packing_key, m),
+                                 theta=theta, select=select, dev=(n_inputs, outputs_ptr))
 
     def lut_select(self, packing_key: "PackingKey", m: int, pool, nodes):
         """tfhe_gpu_lut_select_batch: node b = (terms, entries[, const]) bootstraps x = sum coef * pool[src] + const
         with the test vector packed from its m entries, each a pool index or ("const", word): the output decrypts
         to what entry number x decrypts to.  pool (P, n+1) -> (B, n+1)."""
-        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
-        d, src, konst = _select_nodes(nodes, m)
-        out = np.zeros((d.B, self.n1), np.uint32)
-        self.check(self.lib.tfhe_gpu_lut_select_batch(self.h, packing_key.h, m, pp, pool.shape[0], *d.pointers()[:4],
-                                                      src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p),
-                                                      out.ctypes.data_as(u32p), d.B), "lut_select")
-        return out
+        return self._lut_batch("lut_select", (packing_key.h, m), pool, nodes, m=m)
 
     def lut_select_dev(self, packing_key: "PackingKey", m: int, pool_ptr, P, nodes, out_ptr):
         """tfhe_gpu_lut_select_dev: the pool and the B outputs in HBM (the nodes stay a host description), async."""
-        d, src, konst = _select_nodes(nodes, m)
-        self.check(self.lib.tfhe_gpu_lut_select_dev(self.h, packing_key.h, m, vp(pool_ptr), P, *d.pointers()[:4],
-                                                    src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p), vp(out_ptr),
-                                                    d.B), "lut_select_dev")
+        self._lut_batch("lut_select", (packing_key.h, m), pool_ptr, nodes, m=m, dev=(P, out_ptr))
 
     # ---- extended nodes: an eta per node, select nodes on extended tables (include/tfhe_gpu.h "Extended nodes") ----
     def bootstrap_lut_each_ext(self, eta: int, cts, testvecs):
@@ -1146,54 +1121,25 @@ class Context:
     def lut_select_ext(self, packing_key: "PackingKey", m: int, eta: int, pool, nodes):
         """tfhe_gpu_lut_select_ext_batch: lut_select with the extended bootstrap, so m may be 32 (eta = 1) or 64
         (eta = 2) at the UINT4 key's margin; nodes as lut_select takes them.  pool (P, n+1) -> (B, n+1)."""
-        pool, pp = _u32(np.asarray(pool, np.uint32).reshape(-1, self.n1))
-        d, src, konst = _select_nodes(nodes, m)
-        out = np.zeros((d.B, self.n1), np.uint32)
-        self.check(self.lib.tfhe_gpu_lut_select_ext_batch(self.h, packing_key.h, m, eta, pp, pool.shape[0],
-                                                          *d.pointers()[:4], src.ctypes.data_as(u32p),
-                                                          konst.ctypes.data_as(u32p), out.ctypes.data_as(u32p), d.B),
-                   "lut_select_ext")
-        return out
+        return self._lut_batch("lut_select_ext", (packing_key.h, m, eta), pool, nodes, m=m)
 
     def lut_select_ext_dev(self, packing_key: "PackingKey", m: int, eta: int, pool_ptr, P, nodes, out_ptr):
         """tfhe_gpu_lut_select_ext_dev: the pool and the B outputs in HBM, async."""
-        d, src, konst = _select_nodes(nodes, m)
-        self.check(self.lib.tfhe_gpu_lut_select_ext_dev(self.h, packing_key.h, m, eta, vp(pool_ptr), P, *d.pointers()[:4],
-                                                        src.ctypes.data_as(u32p), konst.ctypes.data_as(u32p),
-                                                        vp(out_ptr), d.B), "lut_select_ext_dev")
+        self._lut_batch("lut_select_ext", (packing_key.h, m, eta), pool_ptr, nodes, m=m, dev=(P, out_ptr))
 
     def lut_circuit_eval_ext(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs, nodes, theta, select,
                              eta, out_wires):
         """tfhe_gpu_lut_circuit_eval_ext: lut_circuit_eval_select with eta per node (None: that call); an ordinary
         node with eta > 0 reads the extended table lut of the set, a select node with eta > 0 runs the extended
         bootstrap on its packed table -> (outputs, depth)."""
-        inputs, ip = _u32(np.asarray(inputs, np.uint32).reshape(-1, self.n1))
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        _, etp = _theta(eta, d.B)
-        sel = _select_arrays(select, d.B)
-        ow, owp = _u32(out_wires)
-        out = np.zeros((ow.size, self.n1), np.uint32)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_ext(
-            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m or 0, inputs.shape[0], ip, d.B,
-            *d.pointers(), thp, *sel[1], etp, ow.size, owp, out.ctypes.data_as(u32p), C.byref(depth)),
-            "lut_circuit_eval_ext")
-        return out, depth.value
+        return self._lut_circuit("lut_circuit_eval_ext", lut_set, inputs, nodes, out_wires, key=(packing_key, m or 0),
+                                 theta=theta, select=select, eta=eta)
 
     def lut_circuit_eval_ext_dev(self, lut_set: "LutSet", packing_key: "PackingKey", m: int, inputs_ptr, n_inputs, nodes,
                                  theta, select, eta, out_wires, outputs_ptr):
         """tfhe_gpu_lut_circuit_eval_ext_dev: inputs and outputs in HBM, async; returns the bootstrap depth."""
-        d = pack_lut_nodes(nodes)
-        _, thp = _theta(theta, d.B)
-        _, etp = _theta(eta, d.B)
-        sel = _select_arrays(select, d.B)
-        ow, owp = _u32(out_wires)
-        depth = C.c_uint32(0)
-        self.check(self.lib.tfhe_gpu_lut_circuit_eval_ext_dev(
-            self.h, lut_set.h, packing_key.h if packing_key is not None else None, m or 0, n_inputs, vp(inputs_ptr), d.B,
-            *d.pointers(), thp, *sel[1], etp, ow.size, owp, vp(outputs_ptr), C.byref(depth)), "lut_circuit_eval_ext_dev")
-        return depth.value
+        return self._lut_circuit("lut_circuit_eval_ext", lut_set, inputs_ptr, nodes, out_wires, key=(packing_key, m or 0),
+                                 theta=theta, select=select, eta=eta, dev=(n_inputs, outputs_ptr))
 
 
 @dataclass
